@@ -14,7 +14,7 @@ of them drawn from the local shards (all 30 LF steps in the shard they come from
 random (terminate early).  `value` counts (query x shard) searches per second = S/s; Q/s = S/s /
 shards.  `--shards-per-gpu 1` is configs[1] (one shard, deepest k-mer table).
 
-    python bench.py [--gpus N --steps K --warmup W] [--runs R --queries Q --shards-per-gpu S]
+    python bench.py [--gpus N --steps K --warmup W] [--runs R --queries Q --shards-per-gpu S] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches its own N ranks
@@ -134,6 +134,15 @@ def parse():
                     help="rehearsal aid: hold this much HBM while the k-mer tables are sized, as rank 0 of an N-GPU "
                          "job holds the gathered intervals (12.8 GB of 10-byte records at N = 8; 20.5 GB unpacked)")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure as well: the per-launch counters and the roofline, the other mix "
+                         "and the valid / deep popBWT legs, the single-shard check, the CPU baseline with the compiled reference, "
+                         "the oracle checks of --mode 1mm / extract, the gather checks and the one-process leg of an N > 1 run.  "
+                         "Without it a run builds, warms up, times --steps batches and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed batch returned as DIR/lower.npy and DIR/upper.npy "
+                         "(float64, [shards][m]: every shard's interval ends of a fixed seeded sample of m of the batch's queries, "
+                         "m chosen so that the files stay near 32 MB; --counts: DIR/count.npy).  Exact search, per-rank host only")
     a = ap.parse_args()
     if a.same_shards:
         a.mix = "population"
@@ -154,6 +163,32 @@ def total(t):
     f = t.reshape(-1)
     return sum(int(f[i:i + (1 << 27)].sum(dtype=f.dtype if f.dtype.is_floating_point else __import__("torch").int64).item())
                for i in range(0, max(f.numel(), 1), 1 << 27)) if f.numel() else 0
+
+
+def dump_outputs(out_dir, blocks, Q, counts=False, separate=False):
+    """--dump-outputs: a batch's results as float64 .npy files, [shards][m] over a fixed seeded sample of m of its Q queries
+    (the same sample whatever the build, so that two builds compare output for output; float64 holds every value exactly:
+    all lie below 2^53 in magnitude).
+    blocks: one per rank, rank order -- [S, Q, 2] {lower, upper} pairs, [2, S, Q] with `separate`, [S, Q] with `counts`."""
+    import torch
+    names = ("count",) if counts else ("lower", "upper")
+    n_rows = sum(b.shape[1 if separate else 0] for b in blocks)
+    m = min(Q, max(1, (32 << 20) // (8 * len(names) * n_rows)))
+    pick = np.sort(np.random.default_rng(20261016).choice(Q, m, replace=False))
+    cols = {n: [] for n in names}
+    for b in blocks:
+        idx = torch.from_numpy(pick).to(b.device)
+        if counts:
+            cols["count"].append(b[:, idx])
+        elif separate:
+            cols["lower"].append(b[0][:, idx])
+            cols["upper"].append(b[1][:, idx])
+        else:
+            cols["lower"].append(b[:, idx, 0])
+            cols["upper"].append(b[:, idx, 1])
+    os.makedirs(out_dir, exist_ok=True)
+    for n, parts in cols.items():
+        np.save(os.path.join(out_dir, n + ".npy"), torch.cat([p.to(torch.float64).cpu() for p in parts]).numpy())
 
 
 def mode_source_sha():
@@ -426,7 +461,7 @@ def run_exact(a, c, mix, steps, warmup, headline):
     rank, world, local, dev, cdev, sp = c.rank, c.world, c.local, c.dev, c.cdev, c.sp
     R, Q, k, S = int(a.runs), int(a.queries), a.k, a.shards_per_gpu
     t_build0 = time.time()
-    want_cpu = headline and rank == 0 and world == 1 and a.cpu_sample > 0  # the CPU baseline is an N = 1 leg
+    want_cpu = a.full and headline and rank == 0 and world == 1 and a.cpu_sample > 0  # the CPU baseline is an N = 1 leg
     # what this rank will hold, item by item, against what the device has free -- BEFORE the first shard is built: a
     # job that cannot fit (rank 0 of an N-GPU job also holds every rank's gathered blocks) stops here with the table,
     # not with an out-of-memory error between two shards or in the first gather (readserver_amd/sharded.py, hbm_plan)
@@ -553,16 +588,17 @@ def run_exact(a, c, mix, steps, warmup, headline):
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- exact work of one step (counting mode, untimed) -----------------------------------------
-    ok(c, L.rsbwt_set_set_counting(sset._s, 1))
-    step()
-    torch.cuda.synchronize()
-    w = (C.c_uint64 * 16)()
-    ok(c, L.rsbwt_set_last_search_counters(sset._s, w))
-    ok(c, L.rsbwt_set_set_counting(sset._s, 0))
-    lf, oc, ln, kt, hops, npass = w[0], w[1], w[2], w[3], w[11], w[10]
-    phases = {"passes": npass, "cycles_per_pass": [round(w[4 + i] / max(npass, 1)) for i in range(6)],
-              "names": ["setup", "issue", "wait", "rank", "exchange", "update"]}
+    # ---- exact work of one step (counting mode, untimed; --full: the roofline's counts) --------------
+    if a.full:
+        ok(c, L.rsbwt_set_set_counting(sset._s, 1))
+        step()
+        torch.cuda.synchronize()
+        w = (C.c_uint64 * 16)()
+        ok(c, L.rsbwt_set_last_search_counters(sset._s, w))
+        ok(c, L.rsbwt_set_set_counting(sset._s, 0))
+        lf, oc, ln, kt, hops, npass = w[0], w[1], w[2], w[3], w[11], w[10]
+        phases = {"passes": npass, "cycles_per_pass": [round(w[4 + i] / max(npass, 1)) for i in range(6)],
+                  "names": ["setup", "issue", "wait", "rank", "exchange", "update"]}
 
     if a.counts:  # the counts of a launch against the interval pairs of the same batch
         pr = gat.pair(0)
@@ -594,8 +630,8 @@ def run_exact(a, c, mix, steps, warmup, headline):
 
     # the gathered blocks are what the ranks sent: checksums of the last batch, rank by rank
     gather_verified = None
-    if world > 1:
-        last = step_no[0] - 1
+    last = step_no[0] - 1
+    if world > 1 and a.full:
         sent = gat.wire(last) if wire_packed else gat.pair(last)
         mine_sum = torch.tensor([total(sent)], dtype=torch.int64, device=cdev)
         exact = torch.ones(1, dtype=torch.int64, device=cdev)
@@ -612,20 +648,38 @@ def run_exact(a, c, mix, steps, warmup, headline):
             got = gat.result(last)
             gather_verified = bool(exact.item()) and all(total(got[r]) == int(sums[r].item()) for r in range(world))
 
+    if headline and rank == 0 and a.dump_outputs:
+        blocks = [d_counts] if a.counts else gat.result(last)
+        if wire_packed:
+            blocks = [gat.unpack_block(b.to(dev)) for b in blocks]
+        dump_outputs(a.dump_outputs, blocks, Q, counts=a.counts, separate=a.separate_arrays)
+
     searches = world * S * Q * steps
     value = searches / dt
     ms_per_step = dt / steps * 1e3
-    avg_kernel_ms = float(np.mean(k_ms))
-    alg_bytes = ln * LINE_BYTES + S * Q * SEARCH_BYTES  # per launch, the search kernel's own reads and writes
-    achieved = alg_bytes / (avg_kernel_ms * 1e-3) / 1e9
-    # the whole step: + packing (k + 8 wpq + 1 B per query) and the start records (8-byte table read +
-    # 16 B written per search)
-    step_bytes = alg_bytes + Q * (k + 8 * wpq + 1) + S * Q * 24
     hbm = sum(int(g.hbm_bytes()) for g in shards)
+    roofline = None
+    if a.full:
+        avg_kernel_ms = float(np.mean(k_ms))
+        alg_bytes = ln * LINE_BYTES + S * Q * SEARCH_BYTES  # per launch, the search kernel's own reads and writes
+        achieved = alg_bytes / (avg_kernel_ms * 1e-3) / 1e9
+        # the whole step: + packing (k + 8 wpq + 1 B per query) and the start records (8-byte table read +
+        # 16 B written per search)
+        step_bytes = alg_bytes + Q * (k + 8 * wpq + 1) + S * Q * 24
+        roofline = {
+            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS,
+            "traffic": _pmc_traffic(R, Q, S, k, a.stream, mix) if headline else None,
+            "kernel": search_kernel_name(S, int(n_sym), shards[0].ktab_depth(), shards[0].window_span()), "kernel_ms": avg_kernel_ms,
+            "algorithmic_bytes_per_launch": alg_bytes, "line_reads_per_launch": ln,
+            "continuation_line_reads_per_launch": hops, "occ_lookups_per_launch": oc,
+            "ktab_starts_per_launch": kt, "phase_stamps": phases,
+            "frac_of_step": step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+        }
 
     # ---- configs[1] on the same resident data: shard 0 alone (same kernel, one shard) -----------
     single = None
-    if headline and S > 1 and not a.no_single_check:
+    if a.full and headline and S > 1 and not a.no_single_check:
         g0 = shards[0]
         pr1 = torch.empty((Q, 2), dtype=torch.int64, device=dev)  # {lower, upper} pairs, as the headline's launch writes them
         ok(c, L.rsbwt_set_counting(g0.handle, 1))
@@ -656,7 +710,7 @@ def run_exact(a, c, mix, steps, warmup, headline):
     res = {
         "mix": mix, "value": value, "queries_per_s_all_shards": value / (world * S), "ms_per_step": ms_per_step,
         "steps": steps, "warmup": warmup,
-        "mean_lf_steps_per_search": lf / (S * Q), "lines_per_lf_step": ln / max(lf, 1),
+        "mean_lf_steps_per_search": lf / (S * Q) if a.full else None, "lines_per_lf_step": ln / max(lf, 1) if a.full else None,
         **ktab_config(shards), "window_span": shards[0].window_span(),
         "symbols_per_shard": int(n_sym), "far_lines_per_shard": int(shards[0].far_lines()),
         "spilled_position_fraction": shards[0].spilled_symbols() / max(int(n_sym), 1),
@@ -669,16 +723,7 @@ def run_exact(a, c, mix, steps, warmup, headline):
                  "(rsbwt_set_prepare_dev / rsbwt_set_find_interval_pairs_prepared_dev)" if piped else
                  "pack + start records + search, batches alternating between two streams" if two else
                  "pack + start records + search, one after the other on one stream"),
-        "roofline": {
-            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS,
-            "traffic": _pmc_traffic(R, Q, S, k, a.stream, mix) if headline else None,
-            "kernel": search_kernel_name(S, int(n_sym), shards[0].ktab_depth(), shards[0].window_span()), "kernel_ms": avg_kernel_ms,
-            "algorithmic_bytes_per_launch": alg_bytes, "line_reads_per_launch": ln,
-            "continuation_line_reads_per_launch": hops, "occ_lookups_per_launch": oc,
-            "ktab_starts_per_launch": kt, "phase_stamps": phases,
-            "frac_of_step": step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-        },
+        "roofline": roofline,
     }
     if want_cpu and host_runs is not None:
         pair = gat.pair(step_no[0] - 1).to(dev)
@@ -761,6 +806,8 @@ def main():
         # library leaves 32 of its 1,024 workgroups out (csrc/search_lines.hip, RSBWT_SEARCH_SPARE_WGS: measured at
         # N = 1, no cost: 18.51 against 18.60 ms per launch, profiles/r05q_*) -- a workgroup slot on 32 CUs.
         os.environ.setdefault("RSBWT_SEARCH_SPARE_WGS", "32")
+    if a.dump_outputs and (a.mode != "exact" or a.host != "ranks"):
+        raise SystemExit("bench.py --dump-outputs: the exact search (--mode exact) on the per-rank host")
     if a.host == "cxx":
         if a.mode != "exact":
             raise SystemExit("bench.py --host cxx: the exact search (configs[1] / configs[2])")
@@ -774,17 +821,18 @@ def main():
     else:
         S, world = a.shards_per_gpu, c.world
         head = run_exact(a, c, a.mix, a.steps, a.warmup, headline=True)
+        roof = head["roofline"] or {}
         mixes = {a.mix: {k: head[k] for k in ("value", "queries_per_s_all_shards", "ms_per_step", "mean_lf_steps_per_search",
-                                                 "lines_per_lf_step", "ktab_depth")} | {"roofline_frac": head["roofline"]["frac"],
-                                                                                        "kernel_ms": head["roofline"]["kernel_ms"], "what": MIX_NOTE[a.mix]}}
+                                                 "lines_per_lf_step", "ktab_depth")} | {"roofline_frac": roof.get("frac"),
+                                                                                        "kernel_ms": roof.get("kernel_ms"), "what": MIX_NOTE[a.mix]}}
         other = "disjoint" if a.mix == "population" else "population"
-        if world == 1 and not a.no_second_mix and not a.counts and S > 1:
+        if a.full and world == 1 and not a.no_second_mix and not a.counts and S > 1:
             o = run_exact(a, c, other, max(3, a.steps // 2), 1, headline=False)
             mixes[other] = {k: o[k] for k in ("value", "queries_per_s_all_shards", "ms_per_step", "mean_lf_steps_per_search",
                                               "lines_per_lf_step", "ktab_depth")} | {"roofline_frac": o["roofline"]["frac"],
                                                                                      "kernel_ms": o["roofline"]["kernel_ms"], "what": MIX_NOTE[other]}
         vsym = a.valid_popbwt_symbols if a.valid_popbwt_symbols >= 0 else (3e9 if a.runs >= 1e10 else 0)
-        if world == 1 and vsym > 0 and not a.no_second_mix and not a.counts and S > 1:
+        if a.full and world == 1 and vsym > 0 and not a.no_second_mix and not a.counts and S > 1:
             # the same search on a VALID population BWT (the shards above are a random run stream): reads of 64 haplotypes,
             # RLO sort + dedup, suffix shards, per-shard suffix sort on the GPU -- and the oracle on a sample of it
             try:
@@ -807,7 +855,7 @@ def main():
             except Exception as e:  # the headline stands whatever happens to this leg
                 mixes["valid_popbwt"] = {"error": repr(e)}
         dsym = a.deep_popbwt_symbols if a.deep_popbwt_symbols >= 0 else (3e9 if a.runs >= 1e10 else 0)
-        if world == 1 and dsym > 0 and not a.no_second_mix and not a.counts and S > 1:
+        if a.full and world == 1 and dsym > 0 and not a.no_second_mix and not a.counts and S > 1:
             # the population north_star quotes its target on (~2.7k genomes): every shard holds the reads of 512 haplotypes at
             # 420x, so a genomic 31-mer ends on an interval tens of rows wide and the two ends of an interval part ways more
             # often (more lines per LF step) -- the regime VERDICT r04 (missing #3) asks to see in the driver's own line
@@ -887,7 +935,7 @@ def main():
         }
         if "shards_matching_oracle" in head:
             out["config"]["shards_matching_oracle"] = head["shards_matching_oracle"]
-        if world > 1 and not a.no_cxx_leg:
+        if a.full and world > 1 and not a.no_cxx_leg:
             # second leg: the same workload driven by ONE process over all the GPUs (the C++ host's shape).  Every rank has
             # closed its shards; rank 0 PRINTS THE HEADLINE LINE FIRST, then starts the leg as a child bounded by what is
             # left of the run's budget, and prints the line again with the leg's record: the first line stands whatever
@@ -994,24 +1042,25 @@ def run_rows(a, c):
             gat_h.submit(i)
             gat_t.submit(i)
 
-        for h in shards:
-            ok(c, L.rsbwt_set_counting(h.handle, 1))
-        ok(c, L.rsbwt_set_set_counting(sset._s, 1))
-        step()
-        torch.cuda.synchronize()
-        w = [0] * 16
-        for h in shards:
-            wi = (C.c_uint64 * 16)()
-            ok(c, L.rsbwt_last_search_counters(h.handle, wi))  # the resumed search of the variants, per shard
-            ok(c, L.rsbwt_set_counting(h.handle, 0))
-            w = [x + int(y) for x, y in zip(w, wi)]
-        # ... or of all the set's shards in ONE launch (csrc/sets.hip, set_hits_1mm_fused): the set's own counters
-        ws = (C.c_uint64 * 16)()
-        ok(c, L.rsbwt_set_last_search_counters(sset._s, ws))
-        ok(c, L.rsbwt_set_set_counting(sset._s, 0))
         fused = bool(L.rsbwt_set_hits_1mm_is_fused(sset._s, M, k))
-        if fused:
-            w = [int(x) for x in ws]
+        if a.full:  # one untimed step in counting mode: the roofline's counts
+            for h in shards:
+                ok(c, L.rsbwt_set_counting(h.handle, 1))
+            ok(c, L.rsbwt_set_set_counting(sset._s, 1))
+            step()
+            torch.cuda.synchronize()
+            w = [0] * 16
+            for h in shards:
+                wi = (C.c_uint64 * 16)()
+                ok(c, L.rsbwt_last_search_counters(h.handle, wi))  # the resumed search of the variants, per shard
+                ok(c, L.rsbwt_set_counting(h.handle, 0))
+                w = [x + int(y) for x, y in zip(w, wi)]
+            # ... or of all the set's shards in ONE launch (csrc/sets.hip, set_hits_1mm_fused): the set's own counters
+            ws = (C.c_uint64 * 16)()
+            ok(c, L.rsbwt_set_last_search_counters(sset._s, ws))
+            ok(c, L.rsbwt_set_set_counting(sset._s, 0))
+            if fused:
+                w = [int(x) for x in ws]
         for _ in range(a.warmup):
             step()
         gat_h.drain(); gat_t.drain(); barrier()
@@ -1030,7 +1079,7 @@ def run_rows(a, c):
         tot_local = (d_t[last % 2] if d_t is not None else gat_t.result(last)[0] if world == 1 else gat_t.acquire(last)).clone()
         hits_local = int(tot_local.sum().item())
         verified = None
-        if world > 1:  # rank 0: the lists side by side in global shard order; every rank's checksum must be in it
+        if world > 1 and a.full:  # rank 0: the lists side by side in global shard order; every rank's checksum must be in it
             sent_h = gat_h.acquire(last)
             mine = torch.tensor([total(sent_h), int(tot_local.sum().item())], dtype=torch.int64, device=cdev)
             sums = [torch.empty_like(mine) for _ in range(world)]
@@ -1042,7 +1091,7 @@ def run_rows(a, c):
                             and int(first[-1]) == sum(int(x[1].item()) for x in sums) and rec.shape[0] == int(first[-1]))
         overflowed = bool((tot_local > cap).any().item())  # (a list longer than its buffer keeps its count and drops records)
         cpu_base = None
-        if world == 1 and a.verify_rows > 0:
+        if a.full and world == 1 and a.verify_rows > 0:
             # shard 0's list of the last batch against the oracle's exact search of every variant of the first k-mers -- and
             # that search, timed, is the CPU baseline of this mode (the composition SURVEY 8 f3 defines: 3k + 1 findInterval
             # calls per 31-mer, query.cpp:24-41, on every core this process may use)
@@ -1072,7 +1121,7 @@ def run_rows(a, c):
                         "exact_searches_per_s": nv * V / t_c, "gpu_matches_oracle_on_sample": verified}
             oix.close()
         hits_local = int(torch.minimum(tot_local, torch.full_like(tot_local, cap)).sum().item())  # (what the lists hold)
-        alg = w[2] * LINE_BYTES + S * M * V * 24 + hits_local * 48
+        alg = w[2] * LINE_BYTES + S * M * V * 24 + hits_local * 48 if a.full else None
         # below 2^26 variant searches per shard the set's shards work side by side on streams of their own
         # (csrc/sets.hip): their kernels overlap, so the sum of their durations says nothing -- the step is priced
         side_by_side = (not fused and S > 1 and M * V < (1 << int(os.environ.get("RSBWT_SET_1MM_SIDE_LOG2", "26")))
@@ -1094,7 +1143,7 @@ def run_rows(a, c):
                            f"({S} per GPU), {V} variants per 31-mer resumed from the k-mer's traced search; output = every shard's "
                            "ordered hit list" + (", gathered on rank 0 and concatenated in shard order" if world > 1 else ""),
                            kmers_per_batch=M, variants_per_kmer=V, hits_per_batch_this_rank=hits_local,
-                           lf_steps_per_variant=w[0] / (S * M * V), hit_lists_verified=verified,
+                           lf_steps_per_variant=w[0] / (S * M * V) if a.full else None, hit_lists_verified=verified,
                            travels=(None if world == 1 else f"[{S}][{cap}] 32-byte records + {S} counts per rank and batch")),
             "roofline": {"bound": "hbm", "achieved": alg / (kms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": alg / (kms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": _pmc_traffic_mode("1mm", int(a.runs), S, M) if fused else None,
@@ -1107,7 +1156,7 @@ def run_rows(a, c):
                                     "search_lines_kernel (the k-mers traced, their variants resumed): the shards side by side, priced on the whole step"
                                     if side_by_side else
                                     "search_lines_kernel (the k-mers traced, their variants resumed), summed over the rank's shards"),
-                         "kernel_ms": kms, "algorithmic_bytes_per_launch": alg, "line_reads_per_launch": w[2]},
+                         "kernel_ms": kms, "algorithmic_bytes_per_launch": alg, "line_reads_per_launch": w[2]} if a.full else None,
             "cpu_baseline": cpu_base,
         }
     else:
@@ -1162,20 +1211,16 @@ def run_rows(a, c):
                 gat_o.drain()
                 gat_l.drain()
 
-        ok(c, L.rsbwt_set_set_counting(sset._s, 1))
-        step()
-        torch.cuda.synchronize()
-        xw = (C.c_uint64 * 16)()
-        ok(c, L.rsbwt_set_last_search_counters(sset._s, xw))  # the walk kernels' counters: one launch sequence walks every shard of the GPU
-        ok(c, L.rsbwt_set_set_counting(sset._s, 0))
-        names = ["passes", "lanes_with_a_row", "steps", "lanes_on_a_continuation", "lines_fetched", "cycles", "cycles_fetch_to_landed", "steps_from_line_hint"]
-        walk = {"prefix": dict(zip(names, [int(v) for v in xw[:8]])), "postfix": dict(zip(names, [int(v) for v in xw[8:]]))}
-        lens0 = d_lenb[0].reshape(-1)
-        ln = lens0.cpu().numpy().view(np.uint32)
-        fits = ln != 0xFFFFFFFF
-        bases = int(ln[fits].astype(np.int64).sum())
-        # one line per symbol and the two '$' steps of every read that fits; walks cut at the buffer's end took `stride` steps
-        steps_alg = bases + 2 * int(fits.sum()) + int((~fits).sum()) * stride
+        walk = None
+        if a.full:  # one untimed step in counting mode: the walk kernels' counters
+            ok(c, L.rsbwt_set_set_counting(sset._s, 1))
+            step()
+            torch.cuda.synchronize()
+            xw = (C.c_uint64 * 16)()
+            ok(c, L.rsbwt_set_last_search_counters(sset._s, xw))  # the walk kernels' counters: one launch sequence walks every shard of the GPU
+            ok(c, L.rsbwt_set_set_counting(sset._s, 0))
+            names = ["passes", "lanes_with_a_row", "steps", "lanes_on_a_continuation", "lines_fetched", "cycles", "cycles_fetch_to_landed", "steps_from_line_hint"]
+            walk = {"prefix": dict(zip(names, [int(v) for v in xw[:8]])), "postfix": dict(zip(names, [int(v) for v in xw[8:]]))}
         for _ in range(a.warmup):
             step()
         drain(); barrier()
@@ -1188,9 +1233,15 @@ def run_rows(a, c):
         drain(); barrier()
         dt = max_over_ranks(time.perf_counter() - t1)
         k_ms = ev0.elapsed_time(ev1) / a.steps  # the walk kernels of one batch (current stream; the gather runs beside them)
+        # every batch extracts the same rows: the read lengths of the last one
+        ln = d_lenb[(step_no[0] - 1) % 2].reshape(-1).cpu().numpy().view(np.uint32)
+        fits = ln != 0xFFFFFFFF
+        bases = int(ln[fits].astype(np.int64).sum())
+        # one line per symbol and the two '$' steps of every read that fits; walks cut at the buffer's end took `stride` steps
+        steps_alg = bases + 2 * int(fits.sum()) + int((~fits).sum()) * stride
         verified = None
         cpu_base = None
-        if world == 1 and a.verify_rows > 0:
+        if a.full and world == 1 and a.verify_rows > 0:
             # reads of shard 0 of the last batch against the oracle's extractPrefix + extractPostfix of the same rows -- and
             # that walk, timed, is the CPU baseline of this mode (query.cpp:43-85 per row)
             oix = oracle_of_shard0(a, c, mix)
@@ -1224,7 +1275,7 @@ def run_rows(a, c):
                         "host_cpus_visible": os.cpu_count(),
                         "bases_per_s": int(c_len[fit_c].astype(np.int64).sum()) / t_c, "gpu_matches_oracle_on_sample": verified}
             oix.close()
-        if world > 1:
+        if world > 1 and a.full:
             last = step_no[0] - 1
             sent, sent_l = gat_o.acquire(last), gat_l.acquire(last)
             # the 2-bit form carries this rank's reads exactly: unpacked, it is the ASCII bytes up to every read's length

@@ -202,13 +202,11 @@ def test_service_config_reader(rsb, tmp_path):
     q.write_text('prefix = "a"\nsuffix = nope;')
     assert L.rsbwt_service_config_load(str(q).encode(), C.byref(h)) == -3 and b"line 2" in L.rsbwt_last_error()
     assert L.rsbwt_service_config_load(str(tmp_path / "missing.cfg").encode(), C.byref(h)) == -2
-    # the reference's own template parses (build container only)
-    import os
-    tpl = "/root/reference/demo/TEMPLATE.service.cfg"
-    if os.path.exists(tpl):
-        assert L.rsbwt_service_config_load(tpl.encode(), C.byref(h)) == 0
-        assert L.rsbwt_service_config_array_len(h, b"rocksdb") == 64 and L.rsbwt_service_config_get(h, b"suffix") == b""
-        L.rsbwt_service_config_free(h)
+    # the reference's own template parses (its demo/TEMPLATE.service.cfg, kept as a fixture)
+    tpl = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "service_template.cfg")
+    assert L.rsbwt_service_config_load(tpl.encode(), C.byref(h)) == 0
+    assert L.rsbwt_service_config_array_len(h, b"rocksdb") == 64 and L.rsbwt_service_config_get(h, b"suffix") == b""
+    L.rsbwt_service_config_free(h)
 
 
 def _libzmq():

@@ -8,7 +8,7 @@ set -uo pipefail
 tag="$1"; shift
 out="$PWD/gpurun_out/ab_valu_$tag"; mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
-ARGS="--cpu-sample 0 --no-single-check --no-second-mix ${BENCH_ARGS:-}"
+ARGS="--full --cpu-sample 0 --no-single-check --no-second-mix ${BENCH_ARGS:-}"
 : > "$out.jsonl"
 for lib in "$@"; do
   name="$(basename "$lib" .so)"

@@ -9,7 +9,7 @@ mkdir -p gpurun_out
 for v in "${vals[@]}"; do
   out="gpurun_out/sweep_${var}_${v}"
   rm -f "$out.json"
-  if env "$var=$v" timeout -k 10 600 python bench.py --cpu-sample 0 "$@" > "$out.json" 2> "$out.err"; then
+  if env "$var=$v" timeout -k 10 600 python bench.py --full --cpu-sample 0 "$@" > "$out.json" 2> "$out.err"; then
     echo "$var=$v $(python tools/bench_brief.py "$out.json")"
   else
     rc=$?

@@ -428,6 +428,26 @@ int rsbwt_set_find_intervals_var(rsbwt_set_t *s, const char *text, const uint64_
 int rsbwt_set_count_var(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *counts);
 int rsbwt_set_query_var(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *first, uint32_t *read_shard,
                         char *reads, uint32_t read_stride, uint32_t *read_len, size_t cap_reads, size_t *nreads);
+/* KmerMatch (src/service/service.cpp:466-502, find_kmer_reads; KmerTask::run :871-960) over every shard: query q =
+ * text[off[q] .. off[q+1]) is tiled as get_tiles(q, k, skip) does (:232-246), every all-ACGT tile goes through
+ * find_reads with no suffix filter (:714-797, min / max_read_length: 0 = 73 / 100), and the reads are folded into a
+ * std::unordered_set<std::string> in the reference's insertion order.  The reads of query q in shard p are
+ * first[q*S+p] .. first[q*S+p+1] (first has Q*S + 1 entries), in that set's iteration order; read r is read_len[r]
+ * bytes at reads + r*read_stride (UINT32_MAX: longer than read_stride).  cap_reads = 0 sizes the buffers (RSBWT_ERANGE,
+ * *nreads set).  k <= 0, skip < 0 or a query shorter than k: no reads.  Every candidate row is mapped to its read on the
+ * device first and each distinct read is extracted once; rsbwt_set_kmer_last_work tells the work of the calling
+ * thread's last call: {candidate rows, rows walked to '$', LF steps of those walks, distinct read identities, reads
+ * extracted}. */
+int rsbwt_set_kmer_reads(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, int32_t k, int32_t skip,
+                         uint32_t min_read_length, uint32_t max_read_length, uint64_t *first, char *reads, uint32_t read_stride,
+                         uint32_t *read_len, size_t cap_reads, size_t *nreads);
+/* counts[q*S+p] = the size of that set (KmerTask::run's Count, :889-897) */
+int rsbwt_set_kmer_count(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, int32_t k, int32_t skip,
+                         uint32_t min_read_length, uint32_t max_read_length, uint64_t *counts);
+void rsbwt_set_kmer_last_work(uint64_t *work5);
+/* the same call's wall time: {total, inside the calls that wait for the device (search, exact-match, identity walks,
+ * extraction), the rest = host work} in ms */
+void rsbwt_set_kmer_last_times(double *ms3);
 /* Device-resident forms, for a set on ONE device (one process per GPU: bench.py --mode 1mm|extract).
  * d_hits [num_shards][cap_per_shard] x 32-byte records (rsbwt_hits_1mm_dev's), d_totals u64[num_shards];
  * d_rows [num_shards][n] (row numbers are per shard), d_out [num_shards][n][stride], d_len / d_prefix_len [num_shards][n]. */
@@ -474,6 +494,18 @@ size_t rsbwt_proto_encode_count_reply(uint8_t *out, size_t cap, int request_type
  * bytes needed (written when out != NULL and they fit cap); 0 = bad arguments. */
 size_t rsbwt_proto_encode_reads_reply(uint8_t *out, size_t cap, int request_type, const char *q, size_t qlen, int revcomp,
                                       const char *const *reads, const size_t *read_len, size_t nreads);
+
+/* Reply{rt = KmerMatch (3), t = (ReplyType) return_type, q, ...} as KmerTask::run sends it (src/service/service.cpp:
+ * 871-960): return_type Count (1): c = ReplyCount{forward_matches | revcomp_matches = ResultCount{c = nreads}} (the
+ * reads are not used); Reads (2): r = ReplyReads{...: one ResultReads per read}, present even when empty; All (3):
+ * a = ReplyAll{...: one ResultAll{r} per read}, present even when empty.  Returns the bytes needed; 0 = bad arguments. */
+size_t rsbwt_proto_encode_kmer_reply(uint8_t *out, size_t cap, int return_type, const char *q, size_t qlen, int revcomp,
+                                     const char *const *reads, const size_t *read_len, size_t nreads);
+/* Request fields 4 and 5 (k, s: readserver.proto:9-10); *has_k / *has_s = 0 when absent (then 0) */
+int rsbwt_proto_decode_request_ks(const uint8_t *msg, size_t len, int32_t *k, int *has_k, int32_t *s, int *has_s);
+/* The Reply a reference service sends for a request it finds nothing for: for Request type t and return type rt,
+ * strand revcomp -- what rsbwt_service_set_unserved answers with (0 = bad arguments / no such reply). */
+size_t rsbwt_proto_encode_empty_reply(uint8_t *out, size_t cap, int t, int rt, const char *q, size_t qlen, int revcomp);
 
 /* The service's configuration file: the libconfig subset the reference's service.cfg uses
  * (`key = "value";`, `key = [ "a", ... ];`, comments; demo/TEMPLATE.service.cfg).  Loading fails with
@@ -542,6 +574,15 @@ void rsbwt_service_set_reads(rsbwt_service_t *s, int enable, uint32_t min_read_l
  * a tile is looked up only in the partitions whose suffix it ends with (is_suffix_of, service.cpp:228-230,759). */
 int rsbwt_service_set_suffixes(rsbwt_service_t *s, const char *const *suffix, size_t n);
 uint64_t rsbwt_service_read_requests(const rsbwt_service_t *s); /* Reads requests answered so far */
+uint64_t rsbwt_service_kmer_requests(const rsbwt_service_t *s); /* KmerMatch Count / Reads requests answered so far */
+/* KmerMatch requests with return type Count or Reads (`/kmermatch`): answered in the window (rsbwt_set_kmer_reads'
+ * path; service.cfg `kmermatch = "on"`), 2 replies per partition on `push`, woven into the window's replies in arrival
+ * order.  Needs every shard opened with RSBWT_OPEN_READS: RSBWT_EINVAL otherwise.  Default off. */
+int rsbwt_service_set_kmermatch(rsbwt_service_t *s, int enable);
+/* Requests nothing in this loop answers and no `other` handler takes (ExactMatch / KmerMatch with All or Samples,
+ * SiteMatch; service.cfg `unserved = "empty"`): 2 replies per partition on `push` carrying no matches, as the
+ * reference sends for an empty result.  The first such request is logged once.  Default off. */
+void rsbwt_service_set_unserved(rsbwt_service_t *s, int empty);
 /* The loop is a pipeline: the thread that runs it receives and cuts the windows, `workers` threads answer a whole
  * window each (decode, one batched search per query length, Reply bytes -- the set's entry points are re-entrant),
  * a sender thread sends the windows' Replies in window order, so replies still leave in arrival order.  Default 8,

@@ -421,6 +421,50 @@ class ShardSet:
                 raise RsbwtError(-1, "a read does not fit read_stride")
         return [[(int(sh[r]), reads[r, :ln[r]].tobytes().decode()) for r in range(int(first[q]), int(first[q + 1]))] for q in range(Q)]
 
+    def kmer_reads(self, queries, k, skip=0, min_read_length=73, max_read_length=100, read_stride=256):
+        """KmerMatch / Reads (find_kmer_reads, src/service/service.cpp:466-502) of every query in every shard: [query][shard]
+        -> the distinct reads, in the reference's unordered_set order (rsbwt_set_kmer_reads)"""
+        text, off = self._var_text(queries)
+        Q, S = len(queries), len(self.shards)
+        first = np.zeros(Q * S + 1, np.uint64)
+        n = C.c_size_t()
+        rc = lib().rsbwt_set_kmer_reads(self._s, _ptr(text), _ptr(off), Q, k, skip, min_read_length, max_read_length, _ptr(first), None,
+                                        read_stride, None, 0, C.byref(n))
+        if rc not in (0, -7):
+            check(rc)
+        total = n.value
+        reads = np.zeros((max(total, 1), read_stride), np.uint8)
+        ln = np.zeros(max(total, 1), np.uint32)
+        if total:
+            check(lib().rsbwt_set_kmer_reads(self._s, _ptr(text), _ptr(off), Q, k, skip, min_read_length, max_read_length, _ptr(first),
+                                             _ptr(reads), read_stride, _ptr(ln), total, C.byref(n)))
+            if (ln[:total] == 0xFFFFFFFF).any():
+                raise RsbwtError(-1, "a read does not fit read_stride")
+        return [[[reads[r, :ln[r]].tobytes().decode() for r in range(int(first[q * S + p]), int(first[q * S + p + 1]))] for p in range(S)]
+                for q in range(Q)]
+
+    def kmer_count(self, queries, k, skip=0, min_read_length=73, max_read_length=100):
+        """KmerMatch / Count: [query][shard] -> the number of distinct reads (rsbwt_set_kmer_count)"""
+        text, off = self._var_text(queries)
+        Q, S = len(queries), len(self.shards)
+        out = np.zeros(Q * S, np.uint64)
+        check(lib().rsbwt_set_kmer_count(self._s, _ptr(text), _ptr(off), Q, k, skip, min_read_length, max_read_length, _ptr(out)))
+        return out.reshape(Q, S)
+
+    @staticmethod
+    def kmer_last_work():
+        """{candidates, walked, lf_steps, identities, extracted} of this thread's last kmer call"""
+        w = np.zeros(5, np.uint64)
+        lib().rsbwt_set_kmer_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return dict(zip(("candidates", "walked", "lf_steps", "identities", "extracted"), (int(x) for x in w)))
+
+    @staticmethod
+    def kmer_last_times():
+        """{total_ms, device_ms, host_ms} of this thread's last kmer call (device_ms: inside the calls that wait for the GPU)"""
+        t = (C.c_double * 3)()
+        lib().rsbwt_set_kmer_last_times(t)
+        return dict(total_ms=t[0], device_ms=t[1], host_ms=t[2])
+
     # -- BASELINE configs[3] / configs[4] over the set: per-shard results side by side, the way the front-end
     # concatenates its partitions' replies (src/service/server.cpp:199-261)
     def hits_1mm(self, kmers):

@@ -19,6 +19,8 @@ int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 struct service_request {
     int t = 0, rt = 0;  // Request.RequestType / ReturnType (readserver.proto:4-5)
     std::string q;
+    int32_t k = 0, s = 0;  // optional int32 k = 4, s = 5 (readserver.proto:9-10); 0 when absent, as protobuf reads them
+    bool has_k = false, has_s = false;
 };
 
 bool service_decode(const uint8_t *msg, size_t len, service_request *out);
@@ -48,6 +50,15 @@ int service_reads_batch(rsbwt_set_t *set, const std::vector<service_request> &rq
 // the same requests answered with EMPTY read lists (a failed batch: the front-end has no timeout, server.cpp:469)
 void service_reads_empty(const std::vector<service_request> &rq, size_t rows, reply_arena *replies, std::vector<char> *handled);
 inline bool service_is_reads_request(const service_request &r) { return r.t == 2 && r.rt == 2; }  // ExactMatch + Reads
+
+// KmerMatch with return type Count or Reads (KmerTask::run, service.cpp:871-960 around find_kmer_reads :466-502): per
+// request, partition (or once, summed) and strand one Reply{rt = KmerMatch, t = (ReplyType) rt, q, c | r}.
+inline bool service_is_kmer_request(const service_request &r) { return r.t == 3 && (r.rt == 1 || r.rt == 2); }
+int service_kmer_batch(rsbwt_set_t *set, const std::vector<service_request> &rq, bool per_partition, const reads_config &cfg,
+                       reply_arena *replies, std::vector<char> *handled);
+// appends the 2 x rows Replies (per row: forward, reverse complement) a reference service sends for request r when it
+// finds nothing: KmerTask / QueryTask / GtTask with an empty result (service.cpp:871-960, 1260-1360, 1023-1170)
+void service_append_empty(const service_request &r, size_t rows, reply_arena *replies);
 
 // What the loop needs of ZeroMQ: the SUB socket it receives Requests on (service.cpp:1495-1497) and
 // the two PUSH sockets it answers on (push for ExactMatch, push_count for CountReads: :1499-1502,1568).

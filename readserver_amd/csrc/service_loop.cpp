@@ -38,6 +38,7 @@
 
 #include "../../include/rsbwt.h"
 #include "service.h"
+#include "kmer_reads.h"
 
 #include "capi_guard.h"
 
@@ -424,6 +425,12 @@ struct rsbwt_service {
     bool serve_reads = true;
     reads_config reads_cfg;
     std::atomic<uint64_t> read_requests{0};
+    // KmerMatch Count / Reads (KmerTask, service.cpp:1537-1544 -> find_kmer_reads :466-502): answered here when on
+    bool serve_kmer = false;
+    std::atomic<uint64_t> kmer_requests{0};
+    // requests nothing here answers and no `other` handler takes: 2 x P empty Replies when on
+    bool unserved_empty = false;
+    std::atomic<bool> unserved_logged{false};
     std::atomic<bool> stop{false};
     std::thread worker;
     // statistics
@@ -497,32 +504,86 @@ struct rsbwt_service {
             }
             job.rep.first[n] = job.rep.off.size() - 1;
         }
-        if (!any_reads) return;
-        // the window's ExactMatch-Reads requests (find_reads, service.cpp:714-797): their Replies are woven into the
-        // window's in arrival order.  A failed batch is answered with empty read lists, for the same reason as above.
-        reply_arena rr;
-        std::vector<char> handled_r;
-        rc = service_reads_batch(set, job.rq, per_partition, reads_cfg, &rr, &handled_r);
-        if (rc != RSBWT_OK) {
-            note_failure(rc, n, "read");
-            service_reads_empty(job.rq, rows, &rr, &handled_r);
+        // the window's ExactMatch-Reads requests (find_reads, service.cpp:714-797) and, when on, its KmerMatch Count / Reads
+        // requests (find_kmer_reads, :466-502): their Replies are woven into the window's in arrival order.  A failed batch
+        // is answered with empty read lists / zero counts, for the same reason as above.
+        bool any_kmer = false, any_unserved = false;
+        for (size_t i = 0; i < n; ++i) {
+            if (!job.parsed[i] || job.handled[i]) continue;
+            if (serve_kmer && service_is_kmer_request(job.rq[i])) any_kmer = true;
+            else if (!(serve_reads && service_is_reads_request(job.rq[i]))) any_unserved = true;
+        }
+        any_unserved = any_unserved && unserved_empty && !other;
+        if (!any_reads && !any_kmer && !any_unserved) return;
+        reply_arena rr, kr;
+        std::vector<char> handled_r(n, 0), handled_k(n, 0);
+        if (any_reads) {
+            rc = service_reads_batch(set, job.rq, per_partition, reads_cfg, &rr, &handled_r);
+            if (rc != RSBWT_OK) {
+                note_failure(rc, n, "read");
+                service_reads_empty(job.rq, rows, &rr, &handled_r);
+            }
+        }
+        if (any_kmer) {
+            rc = service_kmer_batch(set, job.rq, per_partition, reads_cfg, &kr, &handled_k);
+            if (rc != RSBWT_OK) {
+                note_failure(rc, n, "kmer");
+                kmer_empty(job, rows, &kr, &handled_k);
+            }
         }
         reply_arena all;
         all.off.assign(1, 0);
         all.first.assign(n + 1, 0);
-        all.bytes.reserve(job.rep.bytes.size() + rr.bytes.size());
+        all.bytes.reserve(job.rep.bytes.size() + rr.bytes.size() + kr.bytes.size());
         for (size_t i = 0; i < n; ++i) {
             all.first[i] = all.off.size() - 1;
-            const reply_arena *src = job.handled[i] ? &job.rep : handled_r[i] ? &rr : nullptr;
-            if (!src) continue;
+            const reply_arena *src = job.handled[i] ? &job.rep : handled_r[i] ? &rr : handled_k[i] ? &kr : nullptr;
+            if (!src) {
+                if (any_unserved && job.parsed[i] && is_unserved(job.rq[i])) {
+                    note_unserved(job.rq[i]);
+                    service_append_empty(job.rq[i], rows, &all);
+                    job.handled[i] = 4;
+                }
+                continue;
+            }
             for (size_t j = src->first[i]; j < src->first[i + 1]; ++j) {
                 all.bytes.insert(all.bytes.end(), src->bytes.begin() + src->off[j], src->bytes.begin() + src->off[j + 1]);
                 all.off.push_back(all.bytes.size());
             }
             if (handled_r[i]) { job.handled[i] = 2; read_requests++; }
+            if (handled_k[i]) { job.handled[i] = 3; kmer_requests++; }
         }
         all.first[n] = all.off.size() - 1;
         job.rep = std::move(all);
+    }
+
+    // a request of a type the reference answers (ExactMatch, KmerMatch, SiteMatch with return types 1..4) that nothing
+    // here takes
+    bool is_unserved(const service_request &r) const {
+        if (r.t < 2 || r.t > 4 || r.rt < 1 || r.rt > 4) return false;
+        if (r.t == 2 && (r.rt == 1 || (serve_reads && r.rt == 2))) return false;
+        if (serve_kmer && service_is_kmer_request(r)) return false;
+        return true;
+    }
+    void note_unserved(const service_request &r) {
+        bool expected = false;
+        if (unserved_logged.compare_exchange_strong(expected, true))
+            fprintf(stderr, "rsbwt service: answering requests this service does not serve (first: type %d, return type %d) with empty results\n",
+                    r.t, r.rt);
+    }
+    void kmer_empty(const window_job &job, size_t rows, reply_arena *kr, std::vector<char> *handled_k) {
+        const size_t n = job.rq.size();
+        kr->bytes.clear();
+        kr->off.assign(1, 0);
+        kr->first.assign(n + 1, 0);
+        handled_k->assign(n, 0);
+        for (size_t i = 0; i < n; ++i) {
+            kr->first[i] = kr->off.size() - 1;
+            if (!job.parsed[i] || job.handled[i] || !service_is_kmer_request(job.rq[i])) continue;
+            (*handled_k)[i] = 1;
+            service_append_empty(job.rq[i], rows, kr);
+        }
+        kr->first[n] = kr->off.size() - 1;
     }
 
     void note_failure(int rc, size_t n, const char *what) {
@@ -630,6 +691,12 @@ struct rsbwt_service {
                         all.bytes.insert(all.bytes.end(), rr.bytes.begin() + rr.off[j], rr.bytes.begin() + rr.off[j + 1]);
                         all.off.push_back(all.bytes.size());
                     }
+                }  else if (serve_kmer && job.parsed[i] && service_is_kmer_request(job.rq[i])) {
+                    job.handled[i] = 3;
+                    service_append_empty(job.rq[i], rows, &all);
+                } else if (unserved_empty && !other && job.parsed[i] && is_unserved(job.rq[i])) {
+                    job.handled[i] = 4;
+                    service_append_empty(job.rq[i], rows, &all);
                 }
             }
             all.first[n] = all.off.size() - 1;
@@ -905,6 +972,23 @@ void rsbwt_service_set_reads(rsbwt_service_t *s, int enable, uint32_t min_read_l
     if (max_read_length) s->reads_cfg.max_read_length = max_read_length;
 }
 
+int rsbwt_service_set_kmermatch(rsbwt_service_t *s, int enable) {
+    return guarded("rsbwt_service_set_kmermatch", [&]() -> int {
+        if (!s) return fail(RSBWT_EINVAL, "null service");
+        if (enable && !kmer_engine_hooks.opened_for_reads) return fail(RSBWT_ENODEV, "the k-mer path is not part of this build");
+        if (enable)
+            for (size_t i = 0; i < rsbwt_set_size(s->set); ++i)
+                if (!kmer_engine_hooks.opened_for_reads(rsbwt_set_shard(s->set, i)))
+                    return fail(RSBWT_EINVAL, "kmermatch needs every shard opened with RSBWT_OPEN_READS; shard %zu was not", i);
+        s->serve_kmer = enable != 0;
+        return RSBWT_OK;
+    });
+}
+
+void rsbwt_service_set_unserved(rsbwt_service_t *s, int empty) {
+    if (s) s->unserved_empty = empty != 0;
+}
+
 int rsbwt_service_set_suffixes(rsbwt_service_t *s, const char *const *suffix, size_t n) {
     return guarded("rsbwt_service_set_suffixes", [&]() -> int {
         if (!s || (!suffix && n)) return fail(RSBWT_EINVAL, "null argument");
@@ -972,5 +1056,6 @@ void rsbwt_service_stats(const rsbwt_service_t *s, uint64_t *stats6) {
 }
 
 uint64_t rsbwt_service_read_requests(const rsbwt_service_t *s) { return s ? s->read_requests.load() : 0; }
+uint64_t rsbwt_service_kmer_requests(const rsbwt_service_t *s) { return s ? s->kmer_requests.load() : 0; }
 
 }  // extern "C"

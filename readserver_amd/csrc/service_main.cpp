@@ -1,8 +1,9 @@
 // service_main.cpp -- `rsbwt_service <service.cfg>`: the GPU twin of ReadServer's `service` process for
 // the BWT-only paths (src/service/service.cpp:1366-1583).  Reads the same configuration file, loads the
 // BWT(s) into HBM, connects the same three sockets and answers CountReads, ExactMatch-Count and ExactMatch-Reads
-// requests in micro-batches (`GET /get?output=count|reads`); requests of other types are left unanswered (they
-// belong to the RocksDB-backed paths of the reference's service, which can run beside this process on `push`).
+// requests in micro-batches (`GET /get?output=count|reads`), and KmerMatch Count / Reads when `kmermatch = "on"`;
+// requests of other types are left unanswered unless `unserved = "empty"` (they belong to the RocksDB-backed paths of
+// the reference's service, which can run beside this process on `push`).
 //
 // One process may hold many partitions: besides the reference's `prefix` (one BWT), the engine reads
 //   shards  = [ "<prefix of shard 0>", ... ];     one .bwt per suffix partition (64)
@@ -11,6 +12,9 @@
 //   query_threads = "8";                          windows answered at once (the reference's query pool: service.cpp:88)
 //   suffixes = [ "<suffix of shard 0>", ... ];    the partitions' `suffix` values (default: `suffix` for a single shard)
 //   reads = "on" | "off";                         off: ExactMatch-Reads requests are not answered here
+//   kmermatch = "on" | "off";                     on: KmerMatch Count / Reads requests are answered here (default off)
+//   unserved = "empty";                           requests of any other kind get 2 x shards Replies with no matches
+//                                                 (default: no reply, as before)
 // and then sends 2 x shards replies per request (front-end `workers` = 2 x shards) or 2 (`summed`).
 #include <stdio.h>
 #include <stdlib.h>
@@ -36,6 +40,17 @@ int main(int argc, char **argv) {
         fprintf(stderr, "%s\n", rsbwt_last_error());
         return EXIT_FAILURE;
     }
+    // the two opt-in keys, checked before anything is connected or loaded
+    const char *kmermatch = get(cfg, "kmermatch", "off"), *unserved = get(cfg, "unserved", "");
+    if (strcmp(kmermatch, "on") != 0 && strcmp(kmermatch, "off") != 0) {
+        fprintf(stderr, "service.cfg: kmermatch = \"%s\": \"on\" or \"off\"\n", kmermatch);
+        return EXIT_FAILURE;
+    }
+    if (*unserved && strcmp(unserved, "empty") != 0) {
+        fprintf(stderr, "service.cfg: unserved = \"%s\": the one value known is \"empty\"\n", unserved);
+        return EXIT_FAILURE;
+    }
+    const bool serve_kmer = strcmp(kmermatch, "on") == 0;
     printf("starting server for %s\n", get(cfg, "suffix", ""));
     // the sockets first: a box without libzmq should say so before minutes are spent loading shards into HBM
     // (connecting is asynchronous in ZeroMQ: nothing is received until the loop polls)
@@ -63,7 +78,8 @@ int main(int argc, char **argv) {
     // (shards that serve reads are laid out with a psi hint in every window line and their select samples, built at open:
     // include/rsbwt.h, RSBWT_OPEN_READS)
     const bool serve_reads = strcmp(get(cfg, "reads", "on"), "off") != 0;
-    if (rsbwt_set_open(cpaths.data(), cpaths.size(), devs.data(), RSBWT_OPEN_KTAB_GROUPED | (serve_reads ? RSBWT_OPEN_READS : 0u), &set) != RSBWT_OK) {
+    if (rsbwt_set_open(cpaths.data(), cpaths.size(), devs.data(),
+                       RSBWT_OPEN_KTAB_GROUPED | (serve_reads || serve_kmer ? RSBWT_OPEN_READS : 0u), &set) != RSBWT_OK) {
         fprintf(stderr, "%s\n", rsbwt_last_error());
         return EXIT_FAILURE;
     }
@@ -78,6 +94,11 @@ int main(int argc, char **argv) {
     rsbwt_service_set_workers(svc, atoi(get(cfg, "query_threads", "8")));
     // min_read_length / max_read_length: service.cpp:1417-1420 (defaults 73 / 100, :56-57)
     rsbwt_service_set_reads(svc, serve_reads ? 1 : 0, (uint32_t)atoi(get(cfg, "min_read_length", "0")), (uint32_t)atoi(get(cfg, "max_read_length", "0")));
+    if (rsbwt_service_set_kmermatch(svc, serve_kmer ? 1 : 0) != RSBWT_OK) {
+        fprintf(stderr, "%s\n", rsbwt_last_error());
+        return EXIT_FAILURE;
+    }
+    rsbwt_service_set_unserved(svc, *unserved ? 1 : 0);
     {
         std::vector<std::string> suf;
         const size_t nsuf = rsbwt_service_config_array_len(cfg, "suffixes");

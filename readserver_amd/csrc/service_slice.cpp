@@ -29,6 +29,7 @@
 #include "../../include/rsbwt.h"
 #include "service.h"
 #include "capi_guard.h"
+#include "kmer_reads.h"
 
 namespace {
 
@@ -36,7 +37,8 @@ struct request_view {
     int t = 0, rt = 0;      // Request.RequestType / ReturnType (readserver.proto:4-5)
     const char *q = nullptr;
     size_t qlen = 0;
-    bool has_t = false, has_rt = false, has_q = false;
+    int32_t k = 0, s = 0;   // KmerMatch / SiteMatch: optional int32 k = 4, s = 5 (readserver.proto:9-10)
+    bool has_t = false, has_rt = false, has_q = false, has_k = false, has_s = false;
 };
 
 bool get_varint(const uint8_t *&p, const uint8_t *end, uint64_t &v) {
@@ -60,6 +62,8 @@ bool decode_request(const uint8_t *p, size_t n, request_view &r) {
             if (!get_varint(p, end, v)) return false;
             if (field == 1) { r.t = (int)v; r.has_t = true; }
             else if (field == 2) { r.rt = (int)v; r.has_rt = true; }
+            else if (field == 4) { r.k = (int32_t)(uint32_t)v; r.has_k = true; }  // (int32: a negative value arrives sign-extended)
+            else if (field == 5) { r.s = (int32_t)(uint32_t)v; r.has_s = true; }
         } else if (wt == 2) {
             uint64_t len;
             if (!get_varint(p, end, len) || len > (uint64_t)(end - p)) return false;
@@ -131,6 +135,16 @@ int rsbwt_proto_decode_request(const uint8_t *msg, size_t len, int *t, int *rt, 
     if (rt) *rt = r.rt;
     if (q) *q = r.q;
     if (qlen) *qlen = r.qlen;
+    return RSBWT_OK;
+}
+
+int rsbwt_proto_decode_request_ks(const uint8_t *msg, size_t len, int32_t *k, int *has_k, int32_t *s, int *has_s) {
+    request_view r;
+    if (!msg || !decode_request(msg, len, r)) return RSBWT_EFORMAT;
+    if (k) *k = r.k;
+    if (has_k) *has_k = r.has_k ? 1 : 0;
+    if (s) *s = r.s;
+    if (has_s) *has_s = r.has_s ? 1 : 0;
     return RSBWT_OK;
 }
 
@@ -608,12 +622,132 @@ int service_reads_batch(rsbwt_set_t *set, const std::vector<service_request> &rq
     return RSBWT_OK;
 }
 
+// ---- KmerMatch Count / Reads: find_kmer_reads (service.cpp:466-502) batched, KmerTask::run's replies (:871-960) ------
+kmer_engine kmer_engine_hooks = {nullptr, nullptr};
+
+namespace {
+
+// Reply{rt, t = 3 | 4, q, a = ReplyAll{forward_matches | revcomp_matches = ResultAll{r}}*} (readserver.proto:25-28,51-54)
+size_t all_body_len(const std::vector<const std::string *> &reads) { return reads_body_len(reads); }  // ResultAll{r} = ResultReads{r} on the wire
+uint8_t *encode_all_reply(uint8_t *p, int request_type, int reply_type, const std::string &q, bool revcomp,
+                          const std::vector<const std::string *> &reads, size_t body) {
+    *p++ = 0x08; p = put_varint(p, (uint64_t)request_type);
+    *p++ = 0x10; p = put_varint(p, (uint64_t)reply_type);
+    *p++ = 0x1A; p = put_varint(p, q.size());
+    if (!q.empty()) memcpy(p, q.data(), q.size());
+    p += q.size();
+    *p++ = 0x32; p = put_varint(p, body);  // a
+    for (const std::string *s : reads) {
+        const size_t rr = 1 + varint_len(s->size()) + s->size();
+        *p++ = revcomp ? 0x12 : 0x0A; p = put_varint(p, rr);
+        *p++ = 0x0A; p = put_varint(p, s->size());
+        if (!s->empty()) memcpy(p, s->data(), s->size());
+        p += s->size();
+    }
+    return p;
+}
+size_t all_reply_len(int request_type, int reply_type, size_t qlen, size_t body) {
+    return 1 + varint_len((uint64_t)request_type) + 1 + varint_len((uint64_t)reply_type) + 1 + varint_len(qlen) + qlen + 1 + varint_len(body) + body;
+}
+
+// KmerTask::run's Reply for return type rt (1 Count: c = the set's size; 2 Reads: r; else a) appended to *out
+void append_kmer_reply(std::vector<uint8_t> *out, int request_type, int rt, const std::string &q, bool revcomp,
+                       const std::vector<const std::string *> &reads, uint64_t count) {
+    const size_t at = out->size();
+    if (rt == 1) {
+        const int32_t c = (int32_t)(uint32_t)count;  // set_c(vsize): narrowed to int32 (readserver.proto:31-33)
+        out->resize(at + count_reply_len(request_type, q.size(), c));
+        encode_count_reply(out->data() + at, request_type, q.data(), q.size(), revcomp, c);
+    } else if (rt == 2) {
+        const size_t body = reads_body_len(reads);
+        out->resize(at + reads_reply_len(request_type, q.size(), body));
+        encode_reads_reply(out->data() + at, request_type, q, revcomp, reads, body);
+    } else {
+        const size_t body = all_body_len(reads);
+        out->resize(at + all_reply_len(request_type, rt, q.size(), body));
+        encode_all_reply(out->data() + at, request_type, rt, q, revcomp, reads, body);
+    }
+}
+
+}  // namespace
+
+void service_append_empty(const service_request &r, size_t rows, reply_arena *replies) {
+    const std::vector<const std::string *> none;
+    for (size_t row = 0; row < rows; ++row)
+        for (int strand = 0; strand < 2; ++strand) {
+            append_kmer_reply(&replies->bytes, r.t, r.rt, r.q, strand == 1, none, 0);
+            replies->off.push_back(replies->bytes.size());
+        }
+}
+
+int service_kmer_batch(rsbwt_set_t *set, const std::vector<service_request> &rq, bool per_partition, const reads_config &cfg,
+                       reply_arena *replies, std::vector<char> *handled) {
+    const size_t n = rq.size(), S = rsbwt_set_size(set);
+    handled->assign(n, 0);
+    replies->bytes.clear();
+    replies->off.assign(1, 0);
+    replies->first.assign(n + 1, 0);
+    std::vector<kmer_job> jobs;
+    for (size_t i = 0; i < n; ++i) {
+        if (!service_is_kmer_request(rq[i])) continue;
+        (*handled)[i] = 1;
+        for (int strand = 0; strand < 2; ++strand) {
+            kmer_job j;
+            j.w = strand ? rev_comp(rq[i].q.data(), rq[i].q.size()) : rq[i].q;  // KmerTask::run, service.cpp:883-885
+            j.k = rq[i].k;     // (size_t) request->k(): a negative k never tiles (get_tiles :236-239)
+            j.skip = rq[i].s;  // a negative skip: answered empty
+            jobs.push_back(std::move(j));
+        }
+    }
+    if (jobs.empty()) return RSBWT_OK;
+    static const bool timing = getenv("RSBWT_SERVICE_TIMING") != nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<std::vector<std::vector<std::string>>> res;
+    std::vector<char> failed;
+    kmer_work wk;
+    const uint32_t stride = (uint32_t)std::max<size_t>(256, (2 * cfg.max_read_length + 63) & ~(size_t)15);
+    if (!kmer_engine_hooks.batch) return fail(RSBWT_ENODEV, "the k-mer path is not part of this build");
+    const int rc = kmer_engine_hooks.batch(set, jobs, cfg.min_read_length, cfg.max_read_length, stride, &res, &failed, &wk);
+    if (rc != RSBWT_OK) return rc;
+    const size_t rows = per_partition ? S : 1;
+    size_t ji = 0;
+    std::vector<const std::string *> l;
+    for (size_t i = 0; i < n; ++i) {
+        replies->first[i] = replies->off.size() - 1;
+        if (!(*handled)[i]) continue;
+        for (size_t r = 0; r < rows; ++r)
+            for (int strand = 0; strand < 2; ++strand) {
+                // per partition: that shard's set; summed: counts added up, lists joined in shard order
+                l.clear();
+                uint64_t count = 0;
+                for (size_t p = per_partition ? r : 0; p < (per_partition ? r + 1 : S); ++p) {
+                    for (const std::string &x : res[ji + strand][p]) l.push_back(&x);
+                    count += res[ji + strand][p].size();
+                }
+                append_kmer_reply(&replies->bytes, rq[i].t, rq[i].rt, rq[i].q, strand == 1, l, count);
+                replies->off.push_back(replies->bytes.size());
+            }
+        ji += 2;
+    }
+    replies->first[n] = replies->off.size() - 1;
+    if (timing)
+        fprintf(stderr, "rsbwt kmer window: %zu requests, %.1f ms, %llu candidate rows, %llu walked to '$', %llu LF steps, %llu identities, %llu extracted\n",
+                jobs.size() / 2, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(),
+                (unsigned long long)wk.candidates, (unsigned long long)wk.walked, (unsigned long long)wk.lf_steps,
+                (unsigned long long)wk.identities, (unsigned long long)wk.extracted);
+    return RSBWT_OK;
+}
+
 bool service_decode(const uint8_t *msg, size_t len, service_request *out) {
     request_view r;
     if (!decode_request(msg, len, r)) return false;
     out->t = r.t;
     out->rt = r.rt;
     out->q.assign(r.q ? r.q : "", r.qlen);
+    out->k = r.k;
+    out->s = r.s;
+    out->has_k = r.has_k;
+    out->has_s = r.has_s;
     return true;
 }
 
@@ -657,6 +791,37 @@ int rsbwt_service_counts(rsbwt_set_t *set, const uint8_t *requests, size_t reque
     return rsb::guarded("rsbwt_service_counts", [&]() -> int { return rsbwt_service_counts_body(set, requests, requests_len, req_off, n, replies, cap, rep_off, needed); });
 }
 
+
+size_t rsbwt_proto_encode_kmer_reply(uint8_t *out, size_t cap, int return_type, const char *q, size_t qlen, int revcomp,
+                                     const char *const *reads, const size_t *read_len, size_t nreads) {
+    if ((!q && qlen) || ((!reads || !read_len) && nreads) || return_type < 1 || return_type > 4) return 0;
+    try {
+        std::vector<std::string> own(nreads);
+        std::vector<const std::string *> l(nreads);
+        for (size_t i = 0; i < nreads; ++i) {
+            own[i].assign(reads[i] ? reads[i] : "", read_len[i]);
+            l[i] = &own[i];
+        }
+        std::vector<uint8_t> b;
+        rsb::append_kmer_reply(&b, 3, return_type, std::string(q ? q : "", qlen), revcomp != 0, l, nreads);
+        if (out && b.size() <= cap) memcpy(out, b.data(), b.size());
+        return b.size();
+    } catch (const std::bad_alloc &) {
+        return 0;
+    }
+}
+
+size_t rsbwt_proto_encode_empty_reply(uint8_t *out, size_t cap, int t, int rt, const char *q, size_t qlen, int revcomp) {
+    if ((!q && qlen) || t < 1 || t > 4 || rt < 1 || rt > 4) return 0;
+    try {
+        std::vector<uint8_t> b;
+        rsb::append_kmer_reply(&b, t, rt, std::string(q ? q : "", qlen), revcomp != 0, {}, 0);
+        if (out && b.size() <= cap) memcpy(out, b.data(), b.size());
+        return b.size();
+    } catch (const std::bad_alloc &) {
+        return 0;
+    }
+}
 
 size_t rsbwt_proto_encode_reads_reply(uint8_t *out, size_t cap, int request_type, const char *q, size_t qlen, int revcomp,
                                       const char *const *reads, const size_t *read_len, size_t nreads) {

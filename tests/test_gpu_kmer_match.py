@@ -8,54 +8,11 @@ import numpy as np
 import pytest
 
 import proto_schema
+from kmer_reference import _bwt_runs, _expected, _rc
 
 pytestmark = pytest.mark.gpu
 
 MINL, MAXL = 50, 70
-
-
-def _rc(s):
-    return s[::-1].translate(str.maketrans("ACGT", "TGCA"))
-
-
-def _tiles(w, k, skip):
-    if k <= 0 or skip < 0 or len(w) < k:
-        return []
-    return sorted({w[i:i + k] for i in range(0, len(w) - k + 1, skip + 1)})
-
-
-def _rows_reads(oix, t):
-    lo, up = oix.find_interval(t)
-    out = []
-    for r in range(lo, up + 1):
-        pre, post = oix.extract(r)
-        out.append(pre + post)
-    return out
-
-
-def _find_reads(oix, t, minl, maxl):
-    """find_reads(pBWT, t, "") (service.cpp:714-797) as a set of strings"""
-    def is_read(x):  # query_exactmatch (query.cpp:102-120)
-        return x in _rows_reads(oix, x)
-    if len(t) < minl:
-        return set(_rows_reads(oix, t))
-    got = set()
-    if len(t) < maxl:
-        if len(t) != minl:
-            got |= {x for x in _tiles(t, minl, 0) if is_read(x)}
-        return got | set(_rows_reads(oix, t))
-    got |= {x for x in _tiles(t, maxl, 0) if is_read(x)}
-    if minl != maxl:
-        got |= {x for x in _tiles(t, minl, 0) if is_read(x)}
-    return got
-
-
-def _expected(oix, w, k, skip, minl=73, maxl=100):
-    got = set()
-    for t in _tiles(w, k, skip):
-        if set(t) <= set("ACGT"):
-            got |= _find_reads(oix, t, minl, maxl)
-    return got
 
 
 @pytest.fixture(scope="module")
@@ -142,22 +99,6 @@ def test_gpu_kmer_work_counters_show_one_extraction_per_read(rsb, kshards):
     assert 0 < t["device_ms"] <= t["total_ms"]
     assert w["walked"] < w["candidates"]
     assert w["lf_steps"] > 0
-
-
-def _bwt_runs(reads):
-    """the run bytes of the multi-string BWT of `reads` (RLUnit: symbol rank << 5 | length), duplicates kept: suffixes
-    ordered by their string, '$' lowest, equal ones by read index"""
-    rank = {"$": 0, "A": 1, "C": 2, "G": 3, "T": 4}
-    tr = str.maketrans("ACGT", "BCDE")  # (keeps '$' below every base)
-    suf = sorted((r[j:].translate(tr) + "$", i, j) for i, r in enumerate(reads) for j in range(len(r) + 1))
-    runs = []
-    for _, i, j in suf:
-        c = rank[reads[i][j - 1]] if j else 0
-        if runs and runs[-1] >> 5 == c and runs[-1] & 31 < 31:
-            runs[-1] += 1
-        else:
-            runs.append((c << 5) | 1)
-    return np.array(runs, np.uint8)
 
 
 def test_gpu_kmer_duplicate_reads_collapse_as_strings(rsb, oracle):

@@ -151,6 +151,10 @@ int rsbwt_ktab_info(const rsbwt_t *h, uint32_t *format, uint64_t *bytes, uint64_
 /* Test hook (RSBWT_ENABLE_TEST_HOOKS): n bytes of the resident index (region 0: the lines, 1: an owned k-mer table)
  * copied out, the reading twin of rsbwt_debug_poke. */
 int rsbwt_debug_peek(rsbwt_t *h, int region, uint64_t offset, void *bytes, size_t n);
+/* Test hook (RSBWT_ENABLE_TEST_HOOKS=1): the '$' count of rsbwt_read_copies on {lower, upper} pairs given by hand,
+ * u64[Q][2]: copies[q] = Occ('$', upper) - Occ('$', lower - 1) with Occ(., -1) = 0 and ending[q] = upper - lower + 1 (may
+ * be NULL) for lower <= upper < BWLen, zeros otherwise.  Answers no query. */
+int rsbwt_debug_dollar_count(rsbwt_t *h, const uint64_t *pairs, size_t Q, uint64_t *copies, uint64_t *ending);
 int rsbwt_device(const rsbwt_t *h);          /* the GPU the shard is resident on */
 /* The device number the shard was opened with.  Equal to rsbwt_device() except under the TEST HOOK
  * RSBWT_TEST_DEVICE_ALIASES=N (honoured only while RSBWT_ENABLE_TEST_HOOKS is set; read at every rsbwt_open*):
@@ -209,6 +213,25 @@ int rsbwt_extract(rsbwt_t *h, const uint64_t *rows, size_t n, char *out, uint32_
  * of its interval), else 0 -- also for a string holding a symbol outside ACGT (query.cpp:103-105). */
 int rsbwt_query_exactmatch(rsbwt_t *h, const char *kmers, size_t Q, uint32_t k, size_t stride,
                            uint8_t *found);
+/* Whole-read matches by backward search from the terminator rows (csrc/read_lookup.hip).  In SGA's multi-string BWT
+ * the rows [0, num_strings) are the suffixes that begin with a terminator; stepping w backwards from that row range ends
+ * on the rows whose suffix is w$ -- the reads that END with w -- and such a row holds '$' in the BWT exactly when its
+ * read also begins there:
+ *     copies[q] = Occ('$', upper) - Occ('$', lower - 1) = how many indexed reads EQUAL k-mer q,
+ *     ending[q] = upper - lower + 1                     = how many END with it (may be NULL).
+ * |w| LF steps and one line fetch, whatever the width of w's own interval; no read is extracted, so none of these calls
+ * needs RSBWT_OPEN_READS, select samples or psi hints, and none causes them to be built.  A k-mer that is empty, holds
+ * a symbol outside ACGT or is longer than 65,535 symbols gives 0 / 0; so does every k-mer on a shard without
+ * terminator rows.  Null arguments, stride < k, an empty index and a box without GPU: as rsbwt_find_intervals.
+ * The _dev form takes rsbwt_pack_kmers_dev's packing, writes u64[Q] arrays on `stream` and synchronises nothing. */
+int rsbwt_read_copies(rsbwt_t *h, const char *kmers, size_t Q, uint32_t k, size_t stride, uint64_t *copies,
+                      uint64_t *ending);
+int rsbwt_read_copies_dev(rsbwt_t *h, const void *d_packed, const void *d_valid, size_t Q, uint32_t k, void *d_copies,
+                          void *d_ending, void *stream);
+/* on != 0: rsbwt_query_exactmatch on this handle answers found[q] = copies[q] > 0 through rsbwt_read_copies instead of
+ * extracting and comparing the reads of w's interval (the same booleans; default 0). */
+int rsbwt_exactmatch_by_search(rsbwt_t *h, int on);
+int rsbwt_exactmatch_is_by_search(const rsbwt_t *h);
 /* query.cpp:87-100  vector<string> query(const BWT*, const string& w), batched: every read that
  * contains k-mer q, in SA-row order (extractPrefix(i) + extractPostfix(i) for i = lower..upper).
  * first[Q+1] receives the offsets of each k-mer's reads in the output (first[Q] = their number, also
@@ -426,6 +449,13 @@ int rsbwt_set_query(rsbwt_set_t *s, const char *kmers, size_t Q, uint32_t k, siz
  * one with a symbol outside ACGT or one longer than 65,535 symbols ends as the empty interval (1, 0) / count 0 / no reads. */
 int rsbwt_set_find_intervals_var(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *lower, uint64_t *upper);
 int rsbwt_set_count_var(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *counts);
+/* rsbwt_read_copies for queries of lengths of their own, on every shard: copies / ending [num_shards][Q] in the set's shard
+ * order (ending may be NULL); several device groups work as in rsbwt_set_count_var. */
+int rsbwt_set_read_copies_var(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *copies,
+                              uint64_t *ending);
+/* rsbwt_exactmatch_by_search on every shard of the set (the service's Reads and KmerMatch paths ask
+ * rsbwt_query_exactmatch of the shards). */
+int rsbwt_set_exactmatch_by_search(rsbwt_set_t *s, int on);
 int rsbwt_set_query_var(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *first, uint32_t *read_shard,
                         char *reads, uint32_t read_stride, uint32_t *read_len, size_t cap_reads, size_t *nreads);
 /* KmerMatch (src/service/service.cpp:466-502, find_kmer_reads; KmerTask::run :871-960) over every shard: query q =

@@ -16,6 +16,7 @@ from .bwt import (  # noqa: F401
     extractPrefix,
     find_intervals,
     find_intervals_1mm,
+    read_copies,
     hits_1mm,
     hits_1mm_batch,
     findInterval,

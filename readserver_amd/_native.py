@@ -80,6 +80,12 @@ SIGNATURES = {
     "rsbwt_hits_1mm": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rsbwt_extract": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint32, _vp, _vp]),
     "rsbwt_query_exactmatch": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, C.c_size_t, _vp]),
+    "rsbwt_read_copies": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, C.c_size_t, _vp, _vp]),
+    "rsbwt_read_copies_dev": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp, _vp]),
+    "rsbwt_exactmatch_by_search": (C.c_int, [_vp, C.c_int]),
+    "rsbwt_exactmatch_is_by_search": (C.c_int, [_vp]),
+    "rsbwt_set_read_copies_var": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "rsbwt_set_exactmatch_by_search": (C.c_int, [_vp, C.c_int]),
     "rsbwt_query": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, C.c_size_t, _vp, _vp, C.c_uint32, _vp, C.c_size_t,
                               C.POINTER(C.c_size_t)]),
     "rsbwt_pack_kmers_dev": (C.c_int, [_vp, C.c_size_t, C.c_uint32, C.c_size_t, _vp, _vp, C.c_int, _vp]),
@@ -195,6 +201,7 @@ SIGNATURES = {
     "rsbwt_ktab_group_selftest_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
     "rsbwt_debug_fast_window": (C.c_int, [_vp, C.c_size_t, C.c_uint32, _vp, _vp, C.c_int]),
     "rsbwt_debug_poke": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, C.c_size_t]),
+    "rsbwt_debug_dollar_count": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp]),
     "rsbwt_set_shard": (_vp, [_vp, C.c_size_t]),
     "rsbwt_set_find_intervals": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, C.c_size_t, _vp, _vp]),
     "rsbwt_set_count": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, C.c_size_t, _vp]),

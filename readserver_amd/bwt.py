@@ -177,6 +177,16 @@ class GpuBWT:
     def hbm_bytes(self):
         return lib().rsbwt_hbm_bytes(self._h)
 
+    @property
+    def exactmatch_by_search(self):
+        """True: query_exactmatch on this shard answers by backward search from the terminator rows
+        (rsbwt_exactmatch_by_search) instead of extracting and comparing reads."""
+        return bool(lib().rsbwt_exactmatch_is_by_search(self._h))
+
+    @exactmatch_by_search.setter
+    def exactmatch_by_search(self, on):
+        check(lib().rsbwt_exactmatch_by_search(self._h, 1 if on else 0))
+
 
 # ---- query.h (src/bwt/query.cpp) ------------------------------------------------------------
 
@@ -197,6 +207,17 @@ def count_kmers(pBWT, kmers):
     out = np.empty(Q, np.uint64)
     check(lib().rsbwt_count(pBWT.handle, _ptr(a), Q, k, max(k, 1), _ptr(out)))
     return out
+
+
+def read_copies(pBWT, kmers):
+    """Whole-read matches by backward search from the terminator rows (rsbwt_read_copies): (copies, ending) uint64
+    arrays -- how many indexed reads equal each k-mer, and how many end with it."""
+    a, k = _kmer_matrix(kmers)
+    Q = a.shape[0]
+    copies = np.empty(Q, np.uint64)
+    ending = np.empty(Q, np.uint64)
+    check(lib().rsbwt_read_copies(pBWT.handle, _ptr(a), Q, k, max(k, 1), _ptr(copies), _ptr(ending)))
+    return copies, ending
 
 
 def find_intervals_1mm(pBWT, kmers):
@@ -401,6 +422,20 @@ class ShardSet:
         out = np.empty(len(queries), np.uint64)
         check(lib().rsbwt_set_count_var(self._s, _ptr(text), _ptr(off), len(queries), _ptr(out)))
         return out
+
+    def read_copies_var(self, queries):
+        """(copies, ending) of shape (shards, Q): per shard, how many of its reads equal / end with each query
+        (rsbwt_set_read_copies_var)"""
+        text, off = self._var_text(queries)
+        Q, S = len(queries), len(self.shards)
+        copies = np.empty((S, Q), np.uint64)
+        ending = np.empty((S, Q), np.uint64)
+        check(lib().rsbwt_set_read_copies_var(self._s, _ptr(text), _ptr(off), Q, _ptr(copies), _ptr(ending)))
+        return copies, ending
+
+    def exactmatch_by_search(self, on):
+        """rsbwt_query_exactmatch of every shard of the set by search (True) or by extraction (False, the default)"""
+        check(lib().rsbwt_set_exactmatch_by_search(self._s, 1 if on else 0))
 
     def query_var(self, queries, read_stride=256):
         """per query: [(shard, read)] of every read containing it, shard 0's first (rsbwt_set_query_var)"""

@@ -560,6 +560,31 @@ int rsbwt_debug_peek(rsbwt_t *h, int region, uint64_t offset, void *bytes, size_
     return e == hipSuccess ? RSBWT_OK : fail_hip(e, "rsbwt_debug_peek");
 }
 
+// Test hook: the '$' count of rsbwt_read_copies (read_lookup.hip) on {lower, upper} pairs GIVEN BY HAND, u64[Q][2] --
+// among them what no search from the terminator rows can leave (lower = 0: after a step lower >= C['A'] >= 1), intervals
+// that span many windows, rows past the index.  copies / ending u64[Q] (ending may be NULL).  Answers no query.
+int rsbwt_debug_dollar_count(rsbwt_t *h, const uint64_t *pairs, size_t Q, uint64_t *copies, uint64_t *ending) {
+    if (!h || ((!pairs || !copies) && Q)) return fail(RSBWT_EINVAL, "null argument");
+    if (getenv("RSBWT_ENABLE_TEST_HOOKS") == nullptr) return fail(RSBWT_EINVAL, "rsbwt_debug_dollar_count is a test hook: set RSBWT_ENABLE_TEST_HOOKS=1");
+    if (Q == 0) return RSBWT_OK;
+    int rc = use_device(h->device);
+    if (rc != RSBWT_OK) return rc;
+    if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index");
+    ctx_guard g(h->pool);
+    if (!g.c) return fail(RSBWT_EHIP, "cannot create a HIP stream");
+    if ((rc = g.c->stage(Q * 32)) != RSBWT_OK) return rc;
+    hipStream_t st = g.c->st[0];
+    uint8_t *d_pairs = (uint8_t *)g.c->d_stage, *d_cp = d_pairs + Q * 16, *d_en = d_cp + Q * 8;
+    HIP_OK(hipMemcpyAsync(d_pairs, pairs, Q * 16, hipMemcpyHostToDevice, st));
+    if (h->counting) HIP_OK(hipMemsetAsync(h->d_work, 0, WORK_WORDS * sizeof(unsigned long long), st));
+    hipError_t e = launch_dollar_count(h->d_view, 1, d_pairs, Q, d_cp, ending ? d_en : nullptr, h->counting ? h->d_work : nullptr, st);
+    if (e != hipSuccess) return fail_hip(e, "terminator-count kernel launch");
+    HIP_OK(hipMemcpyAsync(copies, d_cp, Q * 8, hipMemcpyDeviceToHost, st));
+    if (ending) HIP_OK(hipMemcpyAsync(ending, d_en, Q * 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return RSBWT_OK;
+}
+
 // ---- class BWT mirrors ------------------------------------------------------------------------
 
 // The sampled select table (getOccAt, read extraction): built once -- at open for a shard opened with
@@ -1149,6 +1174,167 @@ int rsbwt_count(rsbwt_t *h, const char *kmers, size_t Q, uint32_t k, size_t stri
     return search_host(h, kmers, Q, k, stride, counts, nullptr, true);
 }
 
+// ---- whole-read matches by backward search from the terminator rows (read_lookup.hip) ----------
+
+}  // extern "C"
+
+namespace rsb {
+
+int read_copies_launch(search_meter &m, const shard_view *d_views, uint32_t nshards, int num_cus, const void *d_packed,
+                       const void *d_valid, const void *d_len, size_t Q, uint32_t k, void *d_scratch, void *d_copies, void *d_ending,
+                       hipStream_t stream) {
+    if (Q == 0 || nshards == 0) return RSBWT_OK;
+    uint8_t *d_rec = (uint8_t *)d_scratch, *d_pairs = d_rec + (size_t)nshards * Q * 16;
+    hipError_t e = launch_read_seed(d_views, nshards, d_valid, d_len, Q, k, d_rec, stream);
+    if (e != hipSuccess) return fail_hip(e, "start-record kernel launch");
+    search_extra ex;
+    ex.d_init = d_rec;
+    ex.pairs = true;
+    // narrow: a batch that fills the launch (Q * nshards >= lanes of the grid: search_lines.hip, launch_search) runs one lane
+    // per search -- the start interval is the widest there is, but it shrinks fourfold a step and |w| - 6 or so of a
+    // tile's steps find both positions in one line; a smaller batch runs on lane pairs whatever this says
+    ex.narrow = true;
+    int rc = search_launch(m, d_views, nshards, num_cus, d_packed, d_valid, Q, k, d_pairs, nullptr, false, stream, &ex);
+    if (rc) return rc;
+    e = launch_dollar_count(d_views, nshards, d_pairs, Q, d_copies, d_ending, m.counting ? m.d_work : nullptr, stream);
+    if (e != hipSuccess) return fail_hip(e, "terminator-count kernel launch");
+    return RSBWT_OK;
+}
+
+// Host buffers, every query k symbols (1 <= k <= 65535): slices of the batch go up, through the three launches and
+// back one after the other on one stream of the call's context.
+int read_copies_host_views(search_meter &m, ctx_pool &pool, const shard_view *d_views, uint32_t nshards, int num_cus,
+                           const char *kmers, size_t Q, uint32_t k, size_t stride, uint64_t *copies, uint64_t *ending) {
+    const uint32_t wpq = words_per_kmer(k);
+    ctx_guard g(pool);
+    if (!g.c) return fail(RSBWT_EHIP, "cannot create a HIP stream");
+    hipStream_t st = g.c->st[0];
+    const size_t SLICE = std::max<size_t>(1u << 16, (1u << 20) / nshards);
+    const size_t m_max = std::min(SLICE, Q);
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t a_ascii = al((m_max - 1) * stride + k), a_pk = al(m_max * wpq * 8), a_ok = al(m_max),
+                 a_scr = al(read_copies_scratch_bytes(nshards, m_max)), a_res = al((size_t)nshards * m_max * 8);
+    int rc;
+    if ((rc = g.c->stage(a_ascii + a_pk + a_ok + a_scr + 2 * a_res)) != RSBWT_OK) return rc;
+    uint8_t *d_ascii = (uint8_t *)g.c->d_stage, *d_pk = d_ascii + a_ascii, *d_ok = d_pk + a_pk, *d_scr = d_ok + a_ok,
+            *d_cp = d_scr + a_scr, *d_en = d_cp + a_res;
+    for (size_t q0 = 0; q0 < Q; q0 += SLICE) {
+        const size_t mq = std::min(SLICE, Q - q0);
+        HIP_OK(hipMemcpyAsync(d_ascii, kmers + q0 * stride, (mq - 1) * stride + k, hipMemcpyHostToDevice, st));
+        hipError_t e = launch_pack(d_ascii, mq, k, stride, d_pk, d_ok, st);
+        if (e != hipSuccess) return fail_hip(e, "pack kernel launch");
+        if ((rc = read_copies_launch(m, d_views, nshards, num_cus, d_pk, d_ok, nullptr, mq, k, d_scr, d_cp, ending ? d_en : nullptr, st)) != RSBWT_OK)
+            return rc;
+        for (uint32_t s = 0; s < nshards; ++s) {
+            HIP_OK(hipMemcpyAsync(copies + s * Q + q0, d_cp + (size_t)s * mq * 8, mq * 8, hipMemcpyDeviceToHost, st));
+            if (ending) HIP_OK(hipMemcpyAsync(ending + s * Q + q0, d_en + (size_t)s * mq * 8, mq * 8, hipMemcpyDeviceToHost, st));
+        }
+        HIP_OK(hipStreamSynchronize(st));  // (the staging buffer is used again by the next slice)
+    }
+    return RSBWT_OK;
+}
+
+// The same for queries of lengths of their own, sliced as search_host_views_var slices them: an empty query, one with a
+// symbol outside ACGT or one longer than 65,535 symbols gives 0 / 0.
+int read_copies_host_views_var(search_meter &m, ctx_pool &pool, const shard_view *d_views, uint32_t nshards, int num_cus,
+                               const char *text, const uint64_t *off, size_t Q, uint64_t *copies, uint64_t *ending) {
+    ctx_guard g(pool);
+    if (!g.c) return fail(RSBWT_EHIP, "cannot create a HIP stream");
+    hipStream_t st = g.c->st[0];
+    const size_t SLICE = 1u << 16;
+    std::vector<uint64_t> rel;
+    for (size_t q0 = 0; q0 < Q; q0 += SLICE) {
+        const size_t mq = std::min(SLICE, Q - q0);
+        uint64_t kmax = 0;
+        for (size_t i = 0; i < mq; ++i) {
+            if (off[q0 + i + 1] < off[q0 + i]) return fail(RSBWT_EINVAL, "query %zu: its end lies before its start", q0 + i);
+            const uint64_t n = off[q0 + i + 1] - off[q0 + i];
+            if (n <= 65535ull) kmax = std::max(kmax, n);
+        }
+        if (kmax == 0) {  // nothing to search in this slice
+            for (uint32_t s = 0; s < nshards; ++s)
+                for (size_t i = 0; i < mq; ++i) {
+                    copies[s * Q + q0 + i] = 0;
+                    if (ending) ending[s * Q + q0 + i] = 0;
+                }
+            continue;
+        }
+        const uint32_t k = (uint32_t)kmax, wpq = words_per_kmer(k);
+        const size_t tb = (size_t)(off[q0 + mq] - off[q0]);
+        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t a_text = al(tb + 16), a_off = al((mq + 1) * 8), a_pk = al(mq * wpq * 8), a_ok = al(mq), a_len = al(mq * 4),
+                     a_scr = al(read_copies_scratch_bytes(nshards, mq)), a_res = al((size_t)nshards * mq * 8);
+        int rc;
+        if ((rc = g.c->stage(a_text + a_off + a_pk + a_ok + a_len + a_scr + 2 * a_res)) != RSBWT_OK) return rc;
+        uint8_t *d_text = (uint8_t *)g.c->d_stage, *d_off = d_text + a_text, *d_pk = d_off + a_off, *d_ok = d_pk + a_pk, *d_len = d_ok + a_ok,
+                *d_scr = d_len + a_len, *d_cp = d_scr + a_scr, *d_en = d_cp + a_res;
+        rel.resize(mq + 1);
+        for (size_t i = 0; i <= mq; ++i) rel[i] = off[q0 + i] - off[q0];
+        if (tb) HIP_OK(hipMemcpyAsync(d_text, text + off[q0], tb, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_off, rel.data(), (mq + 1) * 8, hipMemcpyHostToDevice, st));
+        hipError_t e = launch_pack_var(d_text, d_off, mq, wpq, d_pk, d_ok, d_len, st);
+        if (e != hipSuccess) return fail_hip(e, "pack kernel launch");
+        if ((rc = read_copies_launch(m, d_views, nshards, num_cus, d_pk, d_ok, d_len, mq, k, d_scr, d_cp, ending ? d_en : nullptr, st)) != RSBWT_OK)
+            return rc;
+        for (uint32_t s = 0; s < nshards; ++s) {
+            HIP_OK(hipMemcpyAsync(copies + s * Q + q0, d_cp + (size_t)s * mq * 8, mq * 8, hipMemcpyDeviceToHost, st));
+            if (ending) HIP_OK(hipMemcpyAsync(ending + s * Q + q0, d_en + (size_t)s * mq * 8, mq * 8, hipMemcpyDeviceToHost, st));
+        }
+        HIP_OK(hipStreamSynchronize(st));  // (rel and the staging buffer are used again by the next slice)
+    }
+    return RSBWT_OK;
+}
+
+}  // namespace rsb
+
+extern "C" {
+
+int rsbwt_read_copies(rsbwt_t *h, const char *kmers, size_t Q, uint32_t k, size_t stride, uint64_t *copies, uint64_t *ending) {
+    if (!h) return fail(RSBWT_EINVAL, "null handle");
+    if (Q == 0) return RSBWT_OK;
+    if (!kmers || !copies) return fail(RSBWT_EINVAL, "null argument");
+    if (stride < k) return fail(RSBWT_EINVAL, "stride %zu < k %u", stride, k);
+    int rc = use_device(h->device);
+    if (rc) return rc;
+    if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index");
+    if (k == 0 || k > 65535u) {  // the empty string and one too long for a start record: no read is either
+        memset(copies, 0, Q * sizeof(uint64_t));
+        if (ending) memset(ending, 0, Q * sizeof(uint64_t));
+        return RSBWT_OK;
+    }
+    return read_copies_host_views(*h, h->pool, h->d_view, 1, h->num_cus, kmers, Q, k, stride, copies, ending);
+}
+
+int rsbwt_read_copies_dev(rsbwt_t *h, const void *d_packed, const void *d_valid, size_t Q, uint32_t k, void *d_copies,
+                          void *d_ending, void *stream) {
+    if (!h) return fail(RSBWT_EINVAL, "null handle");
+    if (Q == 0) return RSBWT_OK;
+    if (!d_packed || !d_valid || !d_copies) return fail(RSBWT_EINVAL, "null argument");
+    int rc = use_device(h->device);
+    if (rc) return rc;
+    if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index");
+    hipStream_t st = (hipStream_t)stream;
+    if (k == 0 || k > 65535u) {
+        HIP_OK(hipMemsetAsync(d_copies, 0, Q * sizeof(uint64_t), st));
+        if (d_ending) HIP_OK(hipMemsetAsync(d_ending, 0, Q * sizeof(uint64_t), st));
+        return RSBWT_OK;
+    }
+    scratch_cache::lease mem;
+    hipError_t e = h->scratch.take(read_copies_scratch_bytes(1, Q), st, &mem);
+    if (e != hipSuccess) return fail_hip(e, "scratch for the start records");
+    rc = read_copies_launch(*h, h->d_view, 1, h->num_cus, d_packed, d_valid, nullptr, Q, k, mem.p, d_copies, d_ending, st);
+    h->scratch.give(mem, st);
+    return rc;
+}
+
+int rsbwt_exactmatch_by_search(rsbwt_t *h, int on) {
+    if (!h) return fail(RSBWT_EINVAL, "null handle");
+    h->exactmatch_by_search.store(on ? 1 : 0, std::memory_order_relaxed);
+    return RSBWT_OK;
+}
+
+int rsbwt_exactmatch_is_by_search(const rsbwt_t *h) { return h ? h->exactmatch_by_search.load(std::memory_order_relaxed) : 0; }
+
 // ---- 1-mismatch search ------------------------------------------------------------------------
 
 // The [m][3k+1] variant intervals of m packed k-mers (variants_kernel's order) into d_lo/d_up.
@@ -1554,6 +1740,17 @@ int rsbwt_query_exactmatch(rsbwt_t *h, const char *kmers, size_t Q, uint32_t k, 
     if (Q > 0xFFFFFFFFull) return fail(RSBWT_ERANGE, "at most 2^32 - 1 strings per call");
     memset(found, 0, Q);
     if (k == 0) return RSBWT_OK;
+    if (h->exactmatch_by_search.load(std::memory_order_relaxed)) {  // rsbwt_exactmatch_by_search: w is a read when the shard holds a copy of it
+        try {
+            std::vector<uint64_t> copies(Q);
+            int rc = rsbwt_read_copies(h, kmers, Q, k, stride, copies.data(), nullptr);
+            if (rc) return rc;
+            for (size_t q = 0; q < Q; ++q) found[q] = copies[q] != 0 ? 1 : 0;
+            return RSBWT_OK;
+        } catch (const std::bad_alloc &) {
+            return fail(RSBWT_ENOMEM, "host allocation failed");
+        }
+    }
     try {
         std::vector<uint64_t> lo(Q), up(Q), first(Q + 1), rows;
         std::vector<uint32_t> owner;

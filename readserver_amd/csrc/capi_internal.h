@@ -81,6 +81,17 @@ int search_launch_walk(search_meter &m, const shard_view *d_views, uint32_t nsha
                        const void *d_valid, size_t nkmers, uint32_t tn, void *d_worklists, void *d_counts, size_t wl_cap, uint32_t k,
                        void *d_sparse, void *d_hit_bits, hipStream_t stream);
 int meter_history_ms(search_meter &m, float *ms, size_t cap, size_t *count);
+// Whole-read matches by backward search from the terminator rows (read_lookup.hip): start records, the search launch,
+// the '$' count -- copies / ending [nshards][Q] (ending may be null).  d_len: the queries' own lengths (u32[Q]), or
+// nullptr when every query has k symbols; d_scratch: read_copies_scratch_bytes(nshards, Q) bytes the launches may use.
+inline size_t read_copies_scratch_bytes(uint32_t nshards, size_t Q) { return (size_t)nshards * Q * 32; }
+int read_copies_launch(search_meter &m, const shard_view *d_views, uint32_t nshards, int num_cus, const void *d_packed,
+                       const void *d_valid, const void *d_len, size_t Q, uint32_t k, void *d_scratch, void *d_copies, void *d_ending,
+                       hipStream_t stream);
+int read_copies_host_views(search_meter &m, ctx_pool &pool, const shard_view *d_views, uint32_t nshards, int num_cus,
+                           const char *kmers, size_t Q, uint32_t k, size_t stride, uint64_t *copies, uint64_t *ending);
+int read_copies_host_views_var(search_meter &m, ctx_pool &pool, const shard_view *d_views, uint32_t nshards, int num_cus,
+                               const char *text, const uint64_t *off, size_t Q, uint64_t *copies, uint64_t *ending);
 // 1-mismatch hit list of one shard from variants expanded once for the whole batch (sets.hip: every shard of a set
 // searches the same variants)
 size_t variants_bytes(size_t m, uint32_t k);
@@ -112,6 +123,7 @@ struct rsbwt : rsb::search_meter {
     uint64_t psi_hint_lines = 0;  // window lines that carry a psi hint
     bool ktab_owned = true;     // false: view.ktab points into a shard set's interleaved table
     uint64_t ktab_untabulated = 0;  // grouped table: T-mers whose record leaves them to the search (empty, or a group too wide)
+    std::atomic<int> exactmatch_by_search{0};  // rsbwt_exactmatch_by_search: rsbwt_query_exactmatch answers from rsbwt_read_copies
 };
 
 namespace rsb {

@@ -91,6 +91,16 @@ hipError_t launch_search(scratch_cache &scratch, const shard_view *d_shards, uin
                          unsigned long long *d_work, int num_cus, hipStream_t stream, hipEvent_t ev0 = nullptr,
                          hipEvent_t ev1 = nullptr, const search_extra *extra = nullptr);
 uint32_t trace_entries(const shard_view &ix, uint32_t k);
+// read_lookup.hip: whole-read matches by backward search from the terminator rows.  launch_read_seed writes the start
+// records [nshards][Q] of such a search (d_len: the queries' own lengths, u32[Q]; nullptr = every query has k symbols)
+// for launch_search to take as search_extra::d_init; launch_dollar_count turns its {lower, upper} pairs [nshards][Q]
+// into copies = Occ('$', upper) - Occ('$', lower - 1) and (d_ending, optional) upper - lower + 1, zeros for anything
+// that is not a proper interval.  d_work (counting mode): words 13 results ranked, 14 positions that took a
+// continuation, 15 results that needed a second line are ADDED to.
+hipError_t launch_read_seed(const shard_view *d_shards, uint32_t nshards, const void *d_valid, const void *d_len, size_t Q, uint32_t k,
+                            void *d_init, hipStream_t stream);
+hipError_t launch_dollar_count(const shard_view *d_shards, uint32_t nshards, const void *d_pairs, size_t Q, void *d_copies,
+                               void *d_ending, unsigned long long *d_work, hipStream_t stream);
 // The 1-mismatch search of a set by worklist (mm1_worklist.hip; k <= 32, 0 < tn < k, one table depth k - tn for all
 // shards).  launch_mm1_worklists takes the step of the three substitutions of every traced position (d_trace
 // [nshards][m][tn], d_own [nshards][m] pairs: the traced search's output) and appends the variants that survive it to

@@ -20,6 +20,9 @@ __device__ __forceinline__ uint32_t dword_matched(uint32_t x, uint32_t bb, uint3
 // Sum over ND dwords of runs of min(len, what is left of `rem` symbols), counting only runs of
 // symbol b.  RLEBWT::getOcc's bucket scan (src/bwt/rlebwt.cpp:281-298), 4.5 VALU per run byte:
 // SDWA operands pick the byte out of the pre-masked dwords.
+// NOT for b = 0: `acc` ("+v", no early clobber) starts at 0 and `b5` is then the constant 0 too, so hipcc may keep both in
+// one register -- the compares of pieces 2 and 3 would see the running sum.  Every caller ranks A..T; read_lookup.hip
+// scans '$' in plain C++ (rank24_dollar).  A tied constraint would cure it and move registers in every search kernel.
 template <int ND>
 __device__ __forceinline__ uint32_t runs_scan(const uint32_t *r, uint32_t b, uint32_t rem) {
     const uint32_t b5 = b << 5;

@@ -32,11 +32,7 @@ namespace rsb {
 // Start state of every (query, shard) search, computed ahead of the search so that a search
 // entering the wave costs one independent 16-byte load instead of a chain (validity byte + packed
 // word -> k-mer table entry) in front of every pass.  Record = { lower | flags, upper }.
-constexpr uint64_t INIT_INVALID = 1ull << 63;   // symbol outside ACGT: result (1, 0)
-constexpr uint64_t INIT_FALLBACK = 1ull << 62;  // not from the k-mer table: continue at symbol k-2
-constexpr uint64_t INIT_EXPLICIT = 1ull << 61;  // continue at the symbol named in bits 40..55 (1-mismatch variants)
-constexpr uint64_t INIT_NOCHECK = 1ull << 60;   // (with INIT_EXPLICIT) an initInterval: the reference looks at it only after its first update (query.cpp:33-37)
-constexpr uint64_t INIT_VAR = 1ull << 59;       // (with INIT_EXPLICIT) a query of a length of its own: bits 40..55 hold the next symbol's index + 1 (0: none left)
+// (the flag bits INIT_*: wave_lines.h -- read_lookup.hip writes such records too)
 
 __device__ __forceinline__ ulonglong2 start_record(const shard_view &ix, const uint64_t *pq, uint32_t k) {
     ulonglong2 rec;

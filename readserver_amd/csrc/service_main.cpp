@@ -13,6 +13,9 @@
 //   suffixes = [ "<suffix of shard 0>", ... ];    the partitions' `suffix` values (default: `suffix` for a single shard)
 //   reads = "on" | "off";                         off: ExactMatch-Reads requests are not answered here
 //   kmermatch = "on" | "off";                     on: KmerMatch Count / Reads requests are answered here (default off)
+//   exactmatch = "extract" | "search";            how "is this tile itself a read?" is answered (Reads, KmerMatch): by extracting
+//                                                 the reads of its interval, or by backward search from the terminator
+//                                                 rows (rsbwt_exactmatch_by_search); the replies are the same (default extract)
 //   unserved = "empty";                           requests of any other kind get 2 x shards Replies with no matches
 //                                                 (default: no reply, as before)
 // and then sends 2 x shards replies per request (front-end `workers` = 2 x shards) or 2 (`summed`).
@@ -40,7 +43,7 @@ int main(int argc, char **argv) {
         fprintf(stderr, "%s\n", rsbwt_last_error());
         return EXIT_FAILURE;
     }
-    // the two opt-in keys, checked before anything is connected or loaded
+    // the opt-in keys, checked before anything is connected or loaded
     const char *kmermatch = get(cfg, "kmermatch", "off"), *unserved = get(cfg, "unserved", "");
     if (strcmp(kmermatch, "on") != 0 && strcmp(kmermatch, "off") != 0) {
         fprintf(stderr, "service.cfg: kmermatch = \"%s\": \"on\" or \"off\"\n", kmermatch);
@@ -48,6 +51,11 @@ int main(int argc, char **argv) {
     }
     if (*unserved && strcmp(unserved, "empty") != 0) {
         fprintf(stderr, "service.cfg: unserved = \"%s\": the one value known is \"empty\"\n", unserved);
+        return EXIT_FAILURE;
+    }
+    const char *exactmatch = get(cfg, "exactmatch", "extract");
+    if (strcmp(exactmatch, "extract") != 0 && strcmp(exactmatch, "search") != 0) {
+        fprintf(stderr, "service.cfg: exactmatch = \"%s\": \"extract\" or \"search\"\n", exactmatch);
         return EXIT_FAILURE;
     }
     const bool serve_kmer = strcmp(kmermatch, "on") == 0;
@@ -80,6 +88,10 @@ int main(int argc, char **argv) {
     const bool serve_reads = strcmp(get(cfg, "reads", "on"), "off") != 0;
     if (rsbwt_set_open(cpaths.data(), cpaths.size(), devs.data(),
                        RSBWT_OPEN_KTAB_GROUPED | (serve_reads || serve_kmer ? RSBWT_OPEN_READS : 0u), &set) != RSBWT_OK) {
+        fprintf(stderr, "%s\n", rsbwt_last_error());
+        return EXIT_FAILURE;
+    }
+    if (strcmp(exactmatch, "search") == 0 && rsbwt_set_exactmatch_by_search(set, 1) != RSBWT_OK) {
         fprintf(stderr, "%s\n", rsbwt_last_error());
         return EXIT_FAILURE;
     }

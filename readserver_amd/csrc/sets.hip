@@ -537,6 +537,47 @@ int rsbwt_set_count_var(rsbwt_set_t *s, const char *text, const uint64_t *off, s
     });
 }
 
+// Whole-read matches of queries of lengths of their own (read_lookup.hip): copies / ending [num_shards][Q] in the set's
+// shard order, per device group one launch sequence over its shards, sliced as rsbwt_set_count_var is.
+static int rsbwt_set_read_copies_var_body(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *copies,
+                                          uint64_t *ending) {
+    if (!s) return fail(RSBWT_EINVAL, "null set");
+    if (Q == 0) return RSBWT_OK;
+    if (!off || !copies || (!text && off[Q] != off[0])) return fail(RSBWT_EINVAL, "null argument");
+    for (rsbwt_t *h : s->shards)
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
+    return for_each_group(s, [&](size_t gi) -> int {
+        dev_group *g = s->groups[gi];
+        int rc = use_device(g->device);
+        if (rc) return rc;
+        const size_t Sg = g->idx.size();
+        const bool contiguous = g->idx.back() - g->idx.front() + 1 == Sg;
+        if (contiguous)
+            return read_copies_host_views_var(*g, g->pool, g->d_views, (uint32_t)Sg, g->num_cus, text, off, Q, copies + g->idx.front() * Q,
+                                              ending ? ending + g->idx.front() * Q : nullptr);
+        std::vector<uint64_t> cp(Sg * Q), en(ending ? Sg * Q : 0);
+        rc = read_copies_host_views_var(*g, g->pool, g->d_views, (uint32_t)Sg, g->num_cus, text, off, Q, cp.data(), ending ? en.data() : nullptr);
+        if (rc) return rc;
+        for (size_t j = 0; j < Sg; ++j) {
+            memcpy(copies + g->idx[j] * Q, cp.data() + j * Q, Q * 8);
+            if (ending) memcpy(ending + g->idx[j] * Q, en.data() + j * Q, Q * 8);
+        }
+        return RSBWT_OK;
+    });
+}
+int rsbwt_set_read_copies_var(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *copies, uint64_t *ending) {
+    return guarded("rsbwt_set_read_copies_var", [&]() -> int { return rsbwt_set_read_copies_var_body(s, text, off, Q, copies, ending); });
+}
+// rsbwt_exactmatch_by_search on every shard of the set
+int rsbwt_set_exactmatch_by_search(rsbwt_set_t *s, int on) {
+    if (!s) return fail(RSBWT_EINVAL, "null set");
+    for (rsbwt_t *h : s->shards) {
+        const int rc = rsbwt_exactmatch_by_search(h, on);
+        if (rc) return rc;
+    }
+    return RSBWT_OK;
+}
+
 
 // counts[Q] summed over the set's shards, the way the front-end sums per-partition replies
 // (src/service/server.cpp:184-197): per device one fused search + a row sum; the per-device sums

@@ -128,6 +128,14 @@ __device__ __forceinline__ uint32_t read_chunk_dword(const staged_line &L) {
     return 2u * (((m2 >> 22) & 3u) | (((m3 >> 22) & 3u) << 2));
 }
 
+// ---- flag bits of a search's start record { lower | flags, upper } (search_lines.hip: the start-record kernels;
+// read_lookup.hip: the records of a search that starts from the terminator rows)
+constexpr uint64_t INIT_INVALID = 1ull << 63;   // symbol outside ACGT: result (1, 0)
+constexpr uint64_t INIT_FALLBACK = 1ull << 62;  // not from the k-mer table: continue at symbol k-2
+constexpr uint64_t INIT_EXPLICIT = 1ull << 61;  // continue at the symbol named in bits 40..55 (1-mismatch variants)
+constexpr uint64_t INIT_NOCHECK = 1ull << 60;   // (with INIT_EXPLICIT) an initInterval: the reference looks at it only after its first update (query.cpp:33-37)
+constexpr uint64_t INIT_VAR = 1ull << 59;       // (with INIT_EXPLICIT) a query of a length of its own: bits 40..55 hold the next symbol's index + 1 (0: none left)
+
 // ---- k-mer table lookups shared by the start-record kernels, the one-lane kernel and the worklist pre-pass
 __device__ __forceinline__ bool view_uses_ktab(const shard_view &ix, uint32_t k) {
     return ix.ktab != nullptr && ix.ktab_depth >= 2u && k >= ix.ktab_depth;

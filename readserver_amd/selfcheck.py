@@ -5,6 +5,11 @@ same walks replayed step by step with the class-BWT mirrors (rsbwt_char_batch / 
 rsbwt_occ_at_batch: thread-per-item kernels over line_format.h's scalar readers, which the tests
 hold to the oracle).  Usable at sizes the oracle cannot follow (tools/check_extract_at_scale.py: a
 20 GB shard) -- extractPrefix / extractPostfix, src/bwt/query.cpp:43-85.
+
+exactmatch_modes: rsbwt_query_exactmatch by extraction against the same call by backward search from the
+terminator rows (rsbwt_exactmatch_by_search, csrc/read_lookup.hip) on strings sampled from the index
+itself -- whole reads extracted from random terminator rows, tiles of them, and both with a base changed.
+Needs a VALID popBWT (every walk ends on a '$' row), e.g. one built on the GPU by tools/popbwt_gpu.py.
 """
 import numpy as np
 
@@ -82,3 +87,43 @@ def extraction_vs_mirrors(g, rows, stride=1024):
         first = {"row": int(rows[i]), "want_len": int(npre[i] + npost[i]), "got_len": int(ln[i]),
                  "prefix_len": [int(npre[i]), int(plen[i])]}
     return {"rows": int(nr), "mirror_steps": int(s1 + s2), "rows_differing": bad, "first_difference": first}
+
+
+def exactmatch_modes(g, n=20000, length=None, seed=0, stride=1024):
+    """Compares the two modes of rsbwt_query_exactmatch on n strings of one length (default: the commonest read length
+    of the sample) drawn from g's own reads.  Returns a dict: strings, found_by_extract, found_by_search, differing,
+    first_difference.  Leaves the handle's switch as it found it."""
+    from .bwt import extract_reads, query_exactmatch_batch
+    rng = np.random.default_rng(seed)
+    nstr = int(g.getPC("A"))  # the terminator rows: row i < num_strings walks out read i's whole text
+    if nstr == 0:
+        raise ValueError("the index has no terminator rows: not a valid popBWT")
+    rows = rng.integers(0, nstr, min(n, 4 * 4096)).astype(np.uint64)
+    reads, _ = extract_reads(g, rows, stride=stride)
+    reads = [r for r in reads if r]
+    if length is None:
+        lens, cnt = np.unique([len(r) for r in reads], return_counts=True)
+        length = int(lens[np.argmax(cnt)])
+    pool = [r for r in reads if len(r) >= length]
+    if not pool:
+        raise ValueError(f"no sampled read has {length} symbols")
+    ws = []
+    for i in range(n):
+        r = pool[int(rng.integers(len(pool)))]
+        s = int(rng.integers(0, len(r) - length + 1)) if i % 2 else 0
+        w = r[s:s + length]
+        if i % 4 >= 2:
+            j = int(rng.integers(length))
+            w = w[:j] + "ACGT"[("ACGT".index(w[j]) + 1 + int(rng.integers(3))) % 4] + w[j + 1:]
+        ws.append(w)
+    was = g.exactmatch_by_search
+    try:
+        g.exactmatch_by_search = False
+        a = query_exactmatch_batch(g, ws).astype(bool)
+        g.exactmatch_by_search = True
+        b = query_exactmatch_batch(g, ws).astype(bool)
+    finally:
+        g.exactmatch_by_search = was
+    bad = np.nonzero(a != b)[0]
+    return {"strings": n, "length": length, "found_by_extract": int(a.sum()), "found_by_search": int(b.sum()),
+            "differing": int(bad.size), "first_difference": ws[int(bad[0])] if bad.size else None}

@@ -36,6 +36,8 @@ def main():
     ap.add_argument("--haplotypes", type=int, default=16)
     ap.add_argument("--coverage", type=float, default=8.0)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--exactmatch", choices=("extract", "search"), default="extract",
+                    help="how the shards answer query_exactmatch: by extraction, or by search from the terminator rows")
     a = ap.parse_args()
     rng = np.random.default_rng(7)
     with tempfile.TemporaryDirectory() as d:
@@ -49,6 +51,7 @@ def main():
         rsb.synth_popbwt(os.path.join(d, "all.bwt"), rd, **kw)
         reads = open(rd).read().split()
         ss = rsb.ShardSet(shards)
+        ss.exactmatch_by_search(a.exactmatch == "search")
         qs = []
         for _ in range(a.queries):
             r = reads[rng.integers(len(reads))]
@@ -65,7 +68,7 @@ def main():
         work = rsb.ShardSet.kmer_last_work()
         best = min(times)
         sp = split[times.index(best)]
-        line = dict(queries=a.queries, k=a.k, skip=a.skip, qlen=a.qlen, shards=a.shards,
+        line = dict(exactmatch=a.exactmatch, queries=a.queries, k=a.k, skip=a.skip, qlen=a.qlen, shards=a.shards,
                     requests_per_s=round(a.queries / best, 1), window_ms=round(best * 1e3, 2),
                     call_ms=round(sp["total_ms"], 2), device_ms=round(sp["device_ms"], 2), host_ms=round(sp["host_ms"], 2),
                     reads_returned=sum(len(x) for row in got for x in row), **work,

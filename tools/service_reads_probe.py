@@ -5,7 +5,8 @@ process, N requests pushed into the in-process transport, the loop run to the en
 counted (2 per request and partition: forward strand, reverse complement).  Queries: substrings of reads, a third each
 shorter than min_read_length (every read containing the query: query()), of min..max (tiles of min_read_length as exact
 reads + query()), and whole reads + flanks (tiles of both lengths: query_exactmatch()).
-usage: tools/service_reads_probe.py [requests=20000] [partitions=4] [genome=300000] [coverage=8]   -> one JSON line
+usage: tools/service_reads_probe.py [requests=20000] [partitions=4] [genome=300000] [coverage=8] [--exactmatch extract|search]
+       -> one JSON line.  --exactmatch search: the shards answer query_exactmatch by search from the terminator rows.
 PROBE_COUNT=1: the same queries as CountReads requests (ReplyCount on the count socket): a window of mixed lengths in
 one search (rsbwt_set_find_intervals_var)."""
 import ctypes as C
@@ -22,6 +23,12 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import readserver_amd as rsb  # noqa: E402
 
+EXACTMATCH = "extract"
+if "--exactmatch" in sys.argv:
+    i = sys.argv.index("--exactmatch")
+    EXACTMATCH = sys.argv[i + 1]
+    assert EXACTMATCH in ("extract", "search"), "--exactmatch extract|search"
+    del sys.argv[i:i + 2]
 N = int(float(sys.argv[1])) if len(sys.argv) > 1 else 20000
 P = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 GENOME = int(float(sys.argv[3])) if len(sys.argv) > 3 else 300000
@@ -73,6 +80,7 @@ with tempfile.TemporaryDirectory() as td:
         else:
             qs.append("".join("ACGT"[x] for x in rng.integers(0, 4, 10)) + r + "".join("ACGT"[x] for x in rng.integers(0, 4, 10)))
     ss = rsb.ShardSet(shards)
+    ss.exactmatch_by_search(EXACTMATCH == "search")
     tr, svc = C.c_void_p(), C.c_void_p()
     assert L.rsbwt_transport_inproc(C.byref(tr)) == 0
     assert L.rsbwt_service_create(ss._s, tr, 2000, 4096, 1, C.byref(svc)) == 0
@@ -115,7 +123,7 @@ with tempfile.TemporaryDirectory() as td:
             nbytes += n.value
     st = (C.c_uint64 * 6)()
     L.rsbwt_service_stats(svc, st)
-    print(json.dumps({"request_type": "CountReads -> ReplyCount" if COUNT else "ExactMatch / Reads -> ReplyReads", "requests": N, "partitions": P, "reads_in_the_collection": len(reads), "read_length": READ_LEN,
+    print(json.dumps({"exactmatch": EXACTMATCH, "request_type": "CountReads -> ReplyCount" if COUNT else "ExactMatch / Reads -> ReplyReads", "requests": N, "partitions": P, "reads_in_the_collection": len(reads), "read_length": READ_LEN,
                       "min_read_length": MINL, "max_read_length": MAXL, "seconds": round(dt, 4), "requests_per_s": round(N / dt, 1),
                       "replies": replies, "replies_expected": 2 * P * N, "reply_bytes": nbytes,
                       "reply_MB_per_s": round(nbytes / dt / 1e6, 1), "windows": int(st[2]), "loop": "pipeline, 8 window workers" if threaded else "rsbwt_service_run on one thread",

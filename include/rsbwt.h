@@ -658,6 +658,37 @@ int rsbwt_debug_poke(rsbwt_t *h, int region, uint64_t offset, const void *bytes,
  * it to integer division up to the 2^40 symbols a shard may have, for every span S in 2..2944. */
 int rsbwt_debug_fast_window(const uint64_t *p, size_t n, uint32_t S, uint32_t *w, uint32_t *r, int device);
 
+/* Test hook (RSBWT_ENABLE_TEST_HOOKS, answers no query): the kernels' rank primitives (csrc/rank_device.h) on n cases given by
+ * hand, one GPU thread each.  A case is 8 dwords: the 24 piece bytes of a quarter (six dwords, piece = symbol << 5 | length),
+ * a symbol b (0..4) and one argument.  `op` names the primitive; out receives 6 dwords per case for
+ * RSBWT_PRIM_DWORD_MATCHED, 2 per case for every other op (unused ones 0):
+ *   DWORD_MATCHED     out[i] = dword_matched(dword i, b in every byte, acc = arg), i = 0..5
+ *   MATCHED24         out[0] = matched24_tab
+ *   RUNS_SCAN1 / 2    out[0] = runs_scan<1> on dword 0 / runs_scan<2> on dwords 0-1, rem = arg
+ *   RANK24            out[0] = rank24, rem = arg
+ *   RANK24_DOLLAR     out[0] = rank24_dollar, rem = arg (b is not looked at)
+ *   CHAR_RANK24       out = {c, occ} of char_rank24(rem = arg, want = 0);  _WANT: want = b
+ *   SELECT_IN24       out = {position, *left} of select_in24(b, t = arg)
+ * const_b = 0: b reaches the primitive as a run-time value; 1: through the instance compiled for that symbol, b a
+ * compile-time constant (a case whose b is above 4 then gets all-ones).  Host buffers. */
+#define RSBWT_PRIM_DWORD_MATCHED 0u
+#define RSBWT_PRIM_MATCHED24 1u
+#define RSBWT_PRIM_RUNS_SCAN1 2u
+#define RSBWT_PRIM_RUNS_SCAN2 3u
+#define RSBWT_PRIM_RANK24 4u
+#define RSBWT_PRIM_RANK24_DOLLAR 5u
+#define RSBWT_PRIM_CHAR_RANK24 6u
+#define RSBWT_PRIM_CHAR_RANK24_WANT 7u
+#define RSBWT_PRIM_SELECT_IN24 8u
+int rsbwt_debug_rank_primitives(uint32_t op, int const_b, const uint32_t *cases, size_t n, uint32_t *out, int device);
+
+/* Test hook (RSBWT_ENABLE_TEST_HOOKS, answers no query): the staged-line readers (csrc/wave_lines.h) on n positions (< BWLen,
+ * else RSBWT_ERANGE) of a resident shard, one lane per position: the lane fetches the position's window line into LDS as the
+ * search kernels do and ranks off it.  out = u64[n][13]: Occ up to and including the position of the three bases other than
+ * `orig` by staged_occ_alts, for orig = A, C, G, T in turn -- {C,G,T}, {A,G,T}, {A,C,T}, {A,C,G} -- then Occ('$') by
+ * staged_dollars.  A position past its line's own pieces (spill chunk / far line): out[i][0] = all ones, out[i][1..12] = 0. */
+int rsbwt_debug_staged_rank(rsbwt_t *h, const uint64_t *positions, size_t n, uint64_t *out);
+
 #ifdef __cplusplus
 }
 #endif

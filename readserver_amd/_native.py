@@ -202,6 +202,8 @@ SIGNATURES = {
     "rsbwt_debug_fast_window": (C.c_int, [_vp, C.c_size_t, C.c_uint32, _vp, _vp, C.c_int]),
     "rsbwt_debug_poke": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, C.c_size_t]),
     "rsbwt_debug_dollar_count": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp]),
+    "rsbwt_debug_rank_primitives": (C.c_int, [C.c_uint32, C.c_int, _vp, C.c_size_t, _vp, C.c_int]),
+    "rsbwt_debug_staged_rank": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
     "rsbwt_set_shard": (_vp, [_vp, C.c_size_t]),
     "rsbwt_set_find_intervals": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, C.c_size_t, _vp, _vp]),
     "rsbwt_set_count": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, C.c_size_t, _vp]),

@@ -313,6 +313,8 @@ hipError_t build_lines(const void *d_runs, uint64_t num_runs, uint32_t want_span
         // full a window may be depends on the spread of the run lengths, which only the data tells.
         // (a shard laid out with room for a psi hint in every window line keeps 88 of a line's 96 piece bytes: the
         // same fill of what is left)
+        // (tests/test_rank_reference.py, golden_layout, restates this rule -- the start, the steps, the attempts and the
+        // two limits of the full pass below -- on the host for the golden popBWT: change them together)
         const double L = (double)n / (double)(R ? R : 1);
         const double target = hint_room ? 88.0 * (double)HINT_PIECES / (double)LINE_PIECES : 88.0;
         span_params sp = make_span(want_span ? want_span : (uint32_t)(target * L + 0.5));

@@ -20,9 +20,8 @@ __device__ __forceinline__ uint32_t dword_matched(uint32_t x, uint32_t bb, uint3
 // Sum over ND dwords of runs of min(len, what is left of `rem` symbols), counting only runs of
 // symbol b.  RLEBWT::getOcc's bucket scan (src/bwt/rlebwt.cpp:281-298), 4.5 VALU per run byte:
 // SDWA operands pick the byte out of the pre-masked dwords.
-// NOT for b = 0: `acc` ("+v", no early clobber) starts at 0 and `b5` is then the constant 0 too, so hipcc may keep both in
-// one register -- the compares of pieces 2 and 3 would see the running sum.  Every caller ranks A..T; read_lookup.hip
-// scans '$' in plain C++ (rank24_dollar).  A tied constraint would cure it and move registers in every search kernel.
+// (`acc` is an early clobber: it is written between the reads of `b5`, and for a compile-time b = 0 both start as the
+// constant 0 -- without the `&` hipcc kept them in one register and pieces 2 and 3 were compared with the running sum.)
 template <int ND>
 __device__ __forceinline__ uint32_t runs_scan(const uint32_t *r, uint32_t b, uint32_t rem) {
     const uint32_t b5 = b << 5;
@@ -50,7 +49,7 @@ __device__ __forceinline__ uint32_t runs_scan(const uint32_t *r, uint32_t b, uin
             "v_sub_u32 %[rem], %[rem], %[t1]\n\t"
             "v_cndmask_b32 %[t1], 0, %[t1], vcc\n\t"
             "v_add3_u32 %[acc], %[acc], %[t0], %[t1]"
-            : [acc] "+v"(acc), [rem] "+v"(rem), [t0] "=&v"(t0), [t1] "=&v"(t1)
+            : [acc] "+&v"(acc), [rem] "+v"(rem), [t0] "=&v"(t0), [t1] "=&v"(t1)
             : [l] "v"(l), [sy] "v"(sy), [b5] "v"(b5)
             : "vcc");
     }
@@ -108,6 +107,38 @@ __device__ __forceinline__ uint32_t rank24(const uint32_t r[6], const sym_tab &t
         }
     }
     return mb + runs_scan<1>(&x, b, rem - base);
+}
+
+// rank24 for the terminator: how many of the first `rem` symbols of 24 pieces are '$' (t = make_sym_tab(0)).  The dword
+// totals and the choice of the dword holding the position are rank24's; the four pieces of that dword are scanned in plain
+// C++ instead of runs_scan's SDWA block.  (It was written when that block was wrong for a compile-time symbol 0 -- see
+// there -- and stays: read_dollar_count_kernel's measured code is this one.  The primitive tests hold rank24 with b = 0,
+// this and the reference to one answer.)
+__device__ __forceinline__ uint32_t rank24_dollar(const uint32_t r[6], const sym_tab &t, uint32_t rem) {
+    uint32_t cum = 0, mat = 0, x = r[0], base = 0, mb = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        if (i) {
+            const bool past = rem > cum;
+            x = past ? r[i] : x;
+            base = past ? cum : base;
+            mb = past ? mat : mb;
+        }
+        if (i < 5) {
+            const uint32_t l = r[i] & 0x1F1F1F1Fu;
+            cum = __builtin_amdgcn_udot4(l, 0x01010101u, cum, false);
+            mat = __builtin_amdgcn_udot4(l, match01(r[i], t), mat, false);
+        }
+    }
+    uint32_t left = rem - base, acc = mb;
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) {
+        const uint32_t u = (x >> (8u * j)) & 0xFFu, len = u & 31u;
+        const uint32_t take = left < len ? left : len;
+        left -= take;
+        acc += (u >> 5) == 0u ? take : 0u;
+    }
+    return acc;
 }
 
 // ---- whole-dword forms for the walk kernels (extract_lines.hip), where a lane has to find out WHICH

@@ -61,53 +61,6 @@ read_seed_var_kernel(const shard_view *__restrict__ shards, uint32_t nshards, co
     init[s * Q + q] = seed_record(shards[s], valid[q] != 0, len[q]);
 }
 
-// rank24 (rank_device.h) for the terminator: how many of the first `rem` symbols of 24 pieces are '$'.  The dword totals and
-// the choice of the dword holding the position are rank24's (v_dot4 against the symbol-0 match mask); the four pieces of
-// that dword are scanned in plain C++ instead of runs_scan's SDWA block: for symbol 0 that block's inputs `b << 5` and its
-// accumulator both start as the constant 0, its constraints let hipcc keep them in ONE register, and the compares of
-// pieces 2 and 3 then see the running sum instead of the symbol (a second '$' piece in a dword went uncounted).
-__device__ __forceinline__ uint32_t rank24_dollar(const uint32_t r[6], const sym_tab &t, uint32_t rem) {
-    uint32_t cum = 0, mat = 0, x = r[0], base = 0, mb = 0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        if (i) {
-            const bool past = rem > cum;
-            x = past ? r[i] : x;
-            base = past ? cum : base;
-            mb = past ? mat : mb;
-        }
-        if (i < 5) {
-            const uint32_t l = r[i] & 0x1F1F1F1Fu;
-            cum = __builtin_amdgcn_udot4(l, 0x01010101u, cum, false);
-            mat = __builtin_amdgcn_udot4(l, match01(r[i], t), mat, false);
-        }
-    }
-    uint32_t left = rem - base, acc = mb;
-#pragma unroll
-    for (uint32_t j = 0; j < 4u; ++j) {
-        const uint32_t u = (x >> (8u * j)) & 0xFFu, len = u & 31u;
-        const uint32_t take = left < len ? left : len;
-        left -= take;
-        acc += (u >> 5) == 0u ? take : 0u;
-    }
-    return acc;
-}
-
-// '$' among the first o symbols (1 <= o <= span) of a staged window line's own pieces: whole quarters from the header
-// (what quarters 0 and 1 hold of '$' = s2 - the four halves), an odd quarter's predecessor 4 runs per v_dot4, the
-// quarter holding the position by rank24_dollar -- the search kernels' rank with the symbol-0 table.
-__device__ __forceinline__ uint32_t staged_dollars(const staged_line &L, const line_head &h, uint32_t o) {
-    const sym_tab tab = make_sym_tab(0u);
-    const uint32_t cq = (o > h.s1 ? 1u : 0u) + (o > h.s2 ? 1u : 0u) + (o > h.s3 ? 1u : 0u);
-    const uint32_t start = cq == 0u ? 0u : cq == 1u ? h.s1 : cq == 2u ? h.s2 : h.s3;
-    uint32_t d = 0;
-    if (cq >= 2u) d = h.s2 - (read_half(L, 1u) + read_half(L, 2u) + read_half(L, 3u) + read_half(L, 4u));
-    if (cq & 1u) d += matched24(L, HDR_DWORDS + 6u * (cq & 2u), tab);
-    uint32_t r6[6];
-    load24(L, HDR_DWORDS + 6u * cq, r6);
-    return d + rank24_dollar(r6, tab, o - start);
-}
-
 // work[] words of a counting launch (beside the search launch's, search_lines.hip WORK_*)
 enum { WORK_RL_RANKED = 13, WORK_RL_CONT = 14, WORK_RL_SECOND = 15 };
 

@@ -232,5 +232,20 @@ __device__ __forceinline__ void staged_occ_alts(const staged_line &L, const line
     }
 }
 
+// '$' among the first o symbols (1 <= o <= span) of a staged window line's own pieces: whole quarters from the header
+// (what quarters 0 and 1 hold of '$' = s2 - the four halves), an odd quarter's predecessor 4 runs per v_dot4, the
+// quarter holding the position by rank24_dollar -- the search kernels' rank with the symbol-0 table.
+__device__ __forceinline__ uint32_t staged_dollars(const staged_line &L, const line_head &h, uint32_t o) {
+    const sym_tab tab = make_sym_tab(0u);
+    const uint32_t cq = (o > h.s1 ? 1u : 0u) + (o > h.s2 ? 1u : 0u) + (o > h.s3 ? 1u : 0u);
+    const uint32_t start = cq == 0u ? 0u : cq == 1u ? h.s1 : cq == 2u ? h.s2 : h.s3;
+    uint32_t d = 0;
+    if (cq >= 2u) d = h.s2 - (read_half(L, 1u) + read_half(L, 2u) + read_half(L, 3u) + read_half(L, 4u));
+    if (cq & 1u) d += matched24(L, HDR_DWORDS + 6u * (cq & 2u), tab);
+    uint32_t r6[6];
+    load24(L, HDR_DWORDS + 6u * cq, r6);
+    return d + rank24_dollar(r6, tab, o - start);
+}
+
 }  // namespace rsb
 #endif

@@ -33,7 +33,7 @@ def test_version_and_errors(rsb):
     assert L.rsbwt_strerror(-3) == b"not an SGA run-length BWT file"
 
 
-def test_no_gpu_means_loud_failure(rsb, tmp_path):
+def test_no_gpu_means_loud_failure(rsb, tmp_path, monkeypatch):
     L = rsb.lib()
     if L.rsbwt_device_count() > 0:
         pytest.skip("a GPU is present")
@@ -41,6 +41,17 @@ def test_no_gpu_means_loud_failure(rsb, tmp_path):
     with pytest.raises(rsb.RsbwtError) as e:
         rsb.GpuBWT(runs=runs, num_strings=0)
     assert e.value.code == -5 and "no CPU fallback" in str(e.value)
+    # the test hooks that compute without a handle: refused for want of a device, not answered on the CPU
+    monkeypatch.setenv("RSBWT_ENABLE_TEST_HOOKS", "1")
+    p, w = np.arange(4, dtype=np.uint64), np.zeros(4, np.uint32)
+    assert L.rsbwt_debug_fast_window(p.ctypes.data, 4, 100, w.ctypes.data, w.ctypes.data, 0) == -5
+    case, out = np.zeros((1, 8), np.uint32), np.zeros((1, 6), np.uint32)
+    for op in range(9):
+        for const_b in (0, 1):
+            assert L.rsbwt_debug_rank_primitives(op, const_b, case.ctypes.data, 1, out.ctypes.data, 0) == -5
+    assert b"no CPU fallback" in L.rsbwt_last_error()
+    # (rsbwt_debug_staged_rank takes a handle, and no handle exists without a device: the open above is its refusal)
+    assert L.rsbwt_debug_staged_rank(None, p.ctypes.data, 4, p.ctypes.data) == -1
 
 
 def test_bad_files_are_reported_not_fatal(rsb, tmp_path):

@@ -458,6 +458,24 @@ int rsbwt_set_read_copies_var(rsbwt_set_t *s, const char *text, const uint64_t *
 int rsbwt_set_exactmatch_by_search(rsbwt_set_t *s, int on);
 int rsbwt_set_query_var(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *first, uint32_t *read_shard,
                         char *reads, uint32_t read_stride, uint32_t *read_len, size_t cap_reads, size_t *nreads);
+/* rsbwt_set_query_var with a limit on the rows a query may bring: matches[q] (may be NULL) = rows of query q summed over
+ * the shards; max_rows > 0 and matches[q] > max_rows: the query contributes no read (first[q+1] == first[q]), matches[q]
+ * still says how many there are.  max_rows == 0: no limit -- the answers of rsbwt_set_query_var.  *nreads counts the kept
+ * rows only, so cap_reads = Q * max_rows always suffices.  On a set whose shards share one device the intervals never
+ * leave it: totals, limit, first[] and the rows are made there (csrc/interval_rows.hip) and the walks take the rows
+ * where they are; a set over several devices applies the limit on the host.  Same answers either way. */
+int rsbwt_set_query_var_capped(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t max_rows,
+                               uint64_t *first, uint32_t *read_shard, char *reads, uint32_t read_stride,
+                               uint32_t *read_len, size_t cap_reads, size_t *nreads, uint64_t *matches);
+/* the expansion alone, one-device set, nothing synchronised: d_pairs = {lower, upper} [num_shards][Q] x 16 B as
+ * rsbwt_set_find_interval_pairs_dev writes them; d_first u64[Q+1] and d_matches u64[Q] always written; d_shard
+ * u32[cap] / d_rows u64[cap] only when first[Q] <= cap (else left untouched).  Rows in rsbwt_set_query's order:
+ * query by query, shard ascending inside a query, SA row ascending inside a shard. */
+int rsbwt_set_interval_rows_dev(rsbwt_set_t *s, const void *d_pairs, size_t Q, uint64_t max_rows, void *d_first,
+                                void *d_matches, void *d_shard, void *d_rows, size_t cap, void *stream);
+/* calling thread's last rsbwt_set_query_var_capped: {rows expanded on the device, rows uploaded from the host,
+ * queries over the limit, bytes copied to the host before the extraction was launched} */
+void rsbwt_set_query_last_work(uint64_t *work4);
 /* KmerMatch (src/service/service.cpp:466-502, find_kmer_reads; KmerTask::run :871-960) over every shard: query q =
  * text[off[q] .. off[q+1]) is tiled as get_tiles(q, k, skip) does (:232-246), every all-ACGT tile goes through
  * find_reads with no suffix filter (:714-797, min / max_read_length: 0 = 73 / 100), and the reads are folded into a
@@ -609,6 +627,14 @@ uint64_t rsbwt_service_kmer_requests(const rsbwt_service_t *s); /* KmerMatch Cou
  * path; service.cfg `kmermatch = "on"`), 2 replies per partition on `push`, woven into the window's replies in arrival
  * order.  Needs every shard opened with RSBWT_OPEN_READS: RSBWT_EINVAL otherwise.  Default off. */
 int rsbwt_service_set_kmermatch(rsbwt_service_t *s, int enable);
+/* A limit on the reads one ExactMatch-Reads query may bring (service.cfg `max_match_reads`; the reference's front-end
+ * has a key of that name, src/service/server.cpp:129,413): each strand of a request is a query of its own, and a strand
+ * whose rows, summed over the partitions, exceed n is answered -- in every partition's Reply, or in the one summed
+ * Reply -- with rsbwt_proto_encode_empty_reply's bytes, neither tile matches nor reads; every other request of the
+ * window is answered as if the wide one were not there.  The first such request is logged once.  n = 0 (the default):
+ * no limit, the code path of the releases before the key.  RSBWT_ENODEV: a limit on a build without the engine. */
+int rsbwt_service_set_max_match_reads(rsbwt_service_t *s, uint64_t n);
+uint64_t rsbwt_service_capped_requests(const rsbwt_service_t *s); /* Reads requests with a strand over the limit so far */
 /* Requests nothing in this loop answers and no `other` handler takes (ExactMatch / KmerMatch with All or Samples,
  * SiteMatch; service.cfg `unserved = "empty"`): 2 replies per partition on `push` carrying no matches, as the
  * reference sends for an empty result.  The first such request is logged once.  Default off. */

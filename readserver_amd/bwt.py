@@ -456,6 +456,34 @@ class ShardSet:
                 raise RsbwtError(-1, "a read does not fit read_stride")
         return [[(int(sh[r]), reads[r, :ln[r]].tobytes().decode()) for r in range(int(first[q]), int(first[q + 1]))] for q in range(Q)]
 
+    def query_var_capped(self, queries, max_rows, read_stride=256):
+        """(reads, matches): reads[q][shard] = the reads containing query q that shard holds, in SA-row order -- none for a
+        query whose rows over all shards exceed max_rows (0 = no limit); matches[q] = that number of rows, over the
+        limit or not (rsbwt_set_query_var_capped)"""
+        text, off = self._var_text(queries)
+        Q, S = len(queries), len(self.shards)
+        first = np.zeros(Q + 1, np.uint64)
+        matches = np.zeros(max(Q, 1), np.uint64)
+        n = C.c_size_t()
+        rc = lib().rsbwt_set_query_var_capped(self._s, _ptr(text), _ptr(off), Q, max_rows, _ptr(first), None, None, read_stride, None, 0,
+                                              C.byref(n), _ptr(matches))
+        if rc not in (0, -7):
+            check(rc)
+        total = n.value
+        reads = np.zeros((max(total, 1), read_stride), np.uint8)
+        ln = np.zeros(max(total, 1), np.uint32)
+        sh = np.zeros(max(total, 1), np.uint32)
+        if total:
+            check(lib().rsbwt_set_query_var_capped(self._s, _ptr(text), _ptr(off), Q, max_rows, _ptr(first), _ptr(sh), _ptr(reads), read_stride,
+                                                   _ptr(ln), total, C.byref(n), _ptr(matches)))
+            if (ln[:total] == 0xFFFFFFFF).any():
+                raise RsbwtError(-1, "a read does not fit read_stride")
+        out = [[[] for _ in range(S)] for _ in range(Q)]
+        for q in range(Q):
+            for r in range(int(first[q]), int(first[q + 1])):
+                out[q][int(sh[r])].append(reads[r, :ln[r]].tobytes().decode())
+        return out, matches[:Q].copy()
+
     def kmer_reads(self, queries, k, skip=0, min_read_length=73, max_read_length=100, read_stride=256):
         """KmerMatch / Reads (find_kmer_reads, src/service/service.cpp:466-502) of every query in every shard: [query][shard]
         -> the distinct reads, in the reference's unordered_set order (rsbwt_set_kmer_reads)"""

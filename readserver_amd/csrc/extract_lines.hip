@@ -88,11 +88,14 @@ __device__ __forceinline__ bool draw_row(bool want, unsigned long long *pool, si
 // came from the psi hint of the line the previous step landed in (no sample read).
 enum { XW_PASSES = 0, XW_ACTIVE = 1, XW_STEPS = 2, XW_CONT = 3, XW_FETCHED = 4, XW_CYCLES = 5, XW_WAIT = 6, XW_PROBES = 7, XW_WORDS = 8 };
 
-template <bool COUNT_WORK>
+// RAGGED: shard sid's rows are block seg[sid * seg_stride] .. seg[(sid + 1) * seg_stride) of the arrays instead of block
+// sid of n (kernels.h, launch_extract_ragged); the padded instantiation reads neither argument.
+template <bool COUNT_WORK, bool RAGGED = false>
 __global__ void __launch_bounds__(64 * XWG_WAVES, RSB_WALK_MIN_WGS)
 extract_prefix_wave_kernel(const shard_view *__restrict__ shards, uint32_t nshards, const uint64_t *__restrict__ rows_all,
-                           size_t n, uint8_t *__restrict__ out_all, uint32_t stride, uint32_t *__restrict__ plen_all,
-                           unsigned long long *__restrict__ pools, unsigned long long *__restrict__ work, uint32_t row_chunk) {
+                           size_t n_padded, uint8_t *__restrict__ out_all, uint32_t stride, uint32_t *__restrict__ plen_all,
+                           unsigned long long *__restrict__ pools, unsigned long long *__restrict__ work, uint32_t row_chunk,
+                           const uint64_t *__restrict__ seg = nullptr, size_t seg_stride = 0) {
     __shared__ uint4 s_stage[XWG_WAVES][64 * SLOT_U4];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint4 *stage = s_stage[wave];
@@ -112,9 +115,11 @@ extract_prefix_wave_kernel(const shard_view *__restrict__ shards, uint32_t nshar
     const uint32_t S = sv->sp.S, nlines = (uint32_t)sv->nlines;
     const double inv = sv->sp.inv;
     const uint64_t ix_n = sv->n;
-    const uint64_t *__restrict__ rows = rows_all + (size_t)sid * n;
-    uint8_t *__restrict__ out = out_all + (size_t)sid * n * stride;
-    uint32_t *__restrict__ plen = plen_all + (size_t)sid * n;
+    const size_t base = RAGGED ? (size_t)seg[(size_t)sid * seg_stride] : (size_t)sid * n_padded;
+    const size_t n = RAGGED ? (size_t)seg[((size_t)sid + 1u) * seg_stride] - base : n_padded;
+    const uint64_t *__restrict__ rows = rows_all + base;
+    uint8_t *__restrict__ out = out_all + base * stride;
+    uint32_t *__restrict__ plen = plen_all + base;
     unsigned long long *pool = pools + (size_t)sid * POOL_STRIDE;  // (a line group apart: kernels.h)
     uint32_t ctab_lo, ctab_hi;  // C[1..4] in lanes 0..3, read with ds_bpermute
     {
@@ -313,12 +318,13 @@ extract_prefix_wave_kernel(const shard_view *__restrict__ shards, uint32_t nshar
 // extractPostfix (query.cpp:65-85): F / select walk right until '$', appended after the prefix.
 // tlen = length of the whole read (UINT32_MAX: it does not fit, or the prefix did not).
 // ---------------------------------------------------------------------------------------------------
-template <bool COUNT_WORK>
+template <bool COUNT_WORK, bool RAGGED = false>
 __global__ void __launch_bounds__(64 * XWG_WAVES, RSB_WALK_MIN_WGS)
 extract_postfix_wave_kernel(const shard_view *__restrict__ shards, uint32_t nshards, const uint64_t *__restrict__ rows_all,
-                            size_t n, uint8_t *__restrict__ out_all, uint32_t stride, const uint32_t *__restrict__ plen_all,
+                            size_t n_padded, uint8_t *__restrict__ out_all, uint32_t stride, const uint32_t *__restrict__ plen_all,
                             uint32_t *__restrict__ tlen_all, unsigned long long *__restrict__ pools,
-                            unsigned long long *__restrict__ work, uint32_t row_chunk) {
+                            unsigned long long *__restrict__ work, uint32_t row_chunk, const uint64_t *__restrict__ seg = nullptr,
+                            size_t seg_stride = 0) {
     __shared__ uint4 s_stage[XWG_WAVES][64 * SLOT_U4];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint4 *stage = s_stage[wave];
@@ -337,10 +343,12 @@ extract_postfix_wave_kernel(const shard_view *__restrict__ shards, uint32_t nsha
     const uint64_t ix_n = sv->n;
     const uint64_t *__restrict__ sel = sv->sel;
     const uint64_t stride_m = sv->sel_stride;
-    const uint64_t *__restrict__ rows = rows_all + (size_t)sid * n;
-    uint8_t *__restrict__ out = out_all + (size_t)sid * n * stride;
-    const uint32_t *__restrict__ plen = plen_all + (size_t)sid * n;
-    uint32_t *__restrict__ tlen = tlen_all + (size_t)sid * n;
+    const size_t base = RAGGED ? (size_t)seg[(size_t)sid * seg_stride] : (size_t)sid * n_padded;
+    const size_t n = RAGGED ? (size_t)seg[((size_t)sid + 1u) * seg_stride] - base : n_padded;
+    const uint64_t *__restrict__ rows = rows_all + base;
+    uint8_t *__restrict__ out = out_all + base * stride;
+    const uint32_t *__restrict__ plen = plen_all + base;
+    uint32_t *__restrict__ tlen = tlen_all + base;
     unsigned long long *pool = pools + (size_t)sid * POOL_STRIDE;  // (a line group apart: kernels.h)
     bool have = false;
     row_pool rp;
@@ -811,6 +819,46 @@ hipError_t launch_extract_wave(scratch_cache &scratch, const shard_view *d_shard
         hipLaunchKernelGGL(extract_postfix_wave_kernel<false>, dim3((unsigned)g), dim3(64 * XWG_WAVES), 0, stream, d_shards, nshards,
                            (const uint64_t *)d_rows, n, (uint8_t *)d_out, stride, (const uint32_t *)d_plen, (uint32_t *)d_len,
                            pool + (size_t)nshards * POOL_STRIDE, d_work + XW_WORDS, row_chunk);
+    e = hipGetLastError();
+    scratch.give(mem, stream);
+    return e;
+}
+
+// (the ragged form: the same three launches over `total` rows cut into the shards' segments)
+hipError_t launch_extract_ragged(scratch_cache &scratch, const shard_view *d_shards, uint32_t nshards, const void *d_rows, size_t total,
+                                 const void *d_seg, size_t seg_stride, void *d_out, uint32_t stride, void *d_plen, void *d_len, int num_cus,
+                                 hipStream_t stream) {
+    if (total == 0 || nshards == 0) return hipSuccess;
+    if (total >= (1ull << 31) || !d_seg) return hipErrorInvalidValue;  // (the walk kernels number a shard's rows in 32 bits)
+    scratch_cache::lease mem;
+    const size_t pool_bytes = 2 * (size_t)nshards * POOL_STRIDE * sizeof(unsigned long long);
+    hipError_t e = scratch.take(pool_bytes, stream, &mem);
+    if (e != hipSuccess) return e;
+    unsigned long long *pool = (unsigned long long *)mem.p;
+    e = hipMemsetAsync(pool, 0, pool_bytes, stream);
+    if (e != hipSuccess) {
+        scratch.give(mem, stream);
+        return e;
+    }
+    // (grid and rows per draw: launch_extract_wave's rules)
+    size_t g = (total + 64 * XWG_WAVES - 1) / (64 * XWG_WAVES);
+    const size_t cap = (size_t)num_cus * RSB_WALK_MIN_WGS;
+    if (g > cap) g = cap;
+    if (g >= nshards) g -= g % nshards;
+    uint32_t row_chunk = ROW_CHUNK;
+    while (row_chunk > 1u && (size_t)row_chunk * g * XWG_WAVES * 2u > total) row_chunk >>= 1;
+    hipLaunchKernelGGL((extract_prefix_wave_kernel<false, true>), dim3((unsigned)g), dim3(64 * XWG_WAVES), 0, stream, d_shards, nshards,
+                       (const uint64_t *)d_rows, (size_t)0, (uint8_t *)d_out, stride, (uint32_t *)d_plen, pool, (unsigned long long *)nullptr,
+                       row_chunk, (const uint64_t *)d_seg, seg_stride);
+    if ((stride & 15u) == 0u && ((uintptr_t)d_out & 15u) == 0u)
+        hipLaunchKernelGGL(move_prefix16_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, stream, (uint8_t *)d_out, stride,
+                           (const uint32_t *)d_plen, total);
+    else
+        hipLaunchKernelGGL(move_prefix_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, stream, (uint8_t *)d_out, stride,
+                           (const uint32_t *)d_plen, total);
+    hipLaunchKernelGGL((extract_postfix_wave_kernel<false, true>), dim3((unsigned)g), dim3(64 * XWG_WAVES), 0, stream, d_shards, nshards,
+                       (const uint64_t *)d_rows, (size_t)0, (uint8_t *)d_out, stride, (const uint32_t *)d_plen, (uint32_t *)d_len,
+                       pool + (size_t)nshards * POOL_STRIDE, (unsigned long long *)nullptr, row_chunk, (const uint64_t *)d_seg, seg_stride);
     e = hipGetLastError();
     scratch.give(mem, stream);
     return e;

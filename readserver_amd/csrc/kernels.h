@@ -187,6 +187,27 @@ hipError_t launch_extract_wave(scratch_cache &scratch, const shard_view *d_shard
                                hipStream_t stream, unsigned long long *d_work = nullptr);
 // d_work (counting mode): WORK_WORDS counters, zeroed by the caller: words 0-7 the prefix walk, 8-15 the
 // postfix walk (extract_lines.hip, XW_*)
+// The same walks over RAGGED segments: shard i's rows are d_rows[seg(i) .. seg(i + 1)), seg(i) = d_seg[i * seg_stride] (u64, in
+// HBM: interval_rows.hip's cell scan, seg_stride = Q) -- `total` rows in all (< 2^31), d_out [total][stride], d_plen / d_len
+// [total], in the rows' order.  No padding: a set whose rows sit in one shard costs what they cost.
+hipError_t launch_extract_ragged(scratch_cache &scratch, const shard_view *d_shards, uint32_t nshards, const void *d_rows, size_t total,
+                                 const void *d_seg, size_t seg_stride, void *d_out, uint32_t stride, void *d_plen, void *d_len, int num_cus,
+                                 hipStream_t stream);
+// interval_rows.hip: {lower, upper} pairs [S][Q] -> the rows of the batch, with a limit on the rows of one query.
+//   launch_interval_totals: d_matches u64[Q] (every query's rows over the S shards), d_first u64[Q + 1] (exclusive scan of the
+//     totals of the queries at or under max_rows; 0 = no limit), *d_over (u64) = queries over it; d_kept: u64[Q + 1] scratch
+//   launch_interval_cells: d_cellpos u64[S * Q + 1] = where shard i's rows of query q start when the kept rows are laid
+//     out shard by shard; d_cellw: u64[S * Q + 1] scratch
+//   launch_interval_fill: a thread per output row t < cap: d_shard[t], d_rows[t] (optional) in the caller's order --
+//     nothing at all when first[Q] > cap; with d_cellpos also d_cell_rows[cell row] and d_dest[t] = that cell row (u32)
+// d_temp / temp_bytes: interval_rows_scan_bytes(number of elements scanned) bytes of scratch
+size_t interval_rows_scan_bytes(size_t n);
+hipError_t launch_interval_totals(const shard_view *d_views, uint32_t S, const void *d_pairs, size_t Q, uint64_t max_rows, void *d_matches,
+                                  void *d_kept, void *d_first, void *d_over, void *d_temp, size_t temp_bytes, hipStream_t stream);
+hipError_t launch_interval_cells(const shard_view *d_views, uint32_t S, const void *d_pairs, size_t Q, uint64_t max_rows, const void *d_matches,
+                                 void *d_cellw, void *d_cellpos, void *d_temp, size_t temp_bytes, hipStream_t stream);
+hipError_t launch_interval_fill(const shard_view *d_views, uint32_t S, const void *d_pairs, size_t Q, const void *d_first, size_t cap,
+                                void *d_shard, void *d_rows, const void *d_cellpos, void *d_cell_rows, void *d_dest, hipStream_t stream);
 // (SEL_SHIFT, sample_window, window_samples, window_psi_hint: line_format.h -- shared with the host-side layout test)
 // query / query_exactmatch (query.cpp:87-120) over extracted reads
 hipError_t launch_match_reads(const void *d_reads, const void *d_len, size_t n, uint32_t stride, const void *d_owner,

@@ -42,11 +42,24 @@ int service_count_batch(rsbwt_set_t *set, const std::vector<service_request> &rq
 // ReplyReads{forward_matches | revcomp_matches}} carrying the reads that partition holds for the query.
 struct reads_config {
     size_t min_read_length = 73, max_read_length = 100;  // service.cpp:56-57; service.cfg min_read_length / max_read_length (:1417-1420)
+    // service.cfg `max_match_reads` (the reference's front-end has the key, src/service/server.cpp:129,413): a (request,
+    // strand) whose query brings more rows than this, summed over the partitions, is answered with no matches at all;
+    // 0 = no limit, the path of every release before the key
+    uint64_t max_match_reads = 0;
     std::vector<std::string> suffix;                      // service.cfg `suffix` of each shard of the set ("" where absent): a tile is looked
                                                           // up only in the partitions whose suffix it ends with (is_suffix_of, :228-230)
 };
+// capped (optional): capped[i] = 1 when a strand of request i was over cfg.max_match_reads
 int service_reads_batch(rsbwt_set_t *set, const std::vector<service_request> &rq, bool per_partition, const reads_config &cfg,
-                        reply_arena *replies, std::vector<char> *handled);
+                        reply_arena *replies, std::vector<char> *handled, std::vector<char> *capped = nullptr);
+// What service_reads_batch reaches rsbwt_set_query_var_capped through (sets.hip fills it in when the engine is linked; the
+// host harnesses under tests/native link this file against stub engines that know rsbwt_set_query_var only): null with
+// a limit set = RSBWT_ENODEV.
+struct query_engine {
+    int (*query_var_capped)(rsbwt_set_t *, const char *, const uint64_t *, size_t, uint64_t, uint64_t *, uint32_t *, char *, uint32_t, uint32_t *,
+                            size_t, size_t *, uint64_t *);
+};
+extern query_engine query_engine_hooks;
 // the same requests answered with EMPTY read lists (a failed batch: the front-end has no timeout, server.cpp:469)
 void service_reads_empty(const std::vector<service_request> &rq, size_t rows, reply_arena *replies, std::vector<char> *handled);
 inline bool service_is_reads_request(const service_request &r) { return r.t == 2 && r.rt == 2; }  // ExactMatch + Reads

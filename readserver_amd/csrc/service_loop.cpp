@@ -425,6 +425,9 @@ struct rsbwt_service {
     bool serve_reads = true;
     reads_config reads_cfg;
     std::atomic<uint64_t> read_requests{0};
+    // Reads requests with a strand over reads_cfg.max_match_reads (rsbwt_service_set_max_match_reads)
+    std::atomic<uint64_t> capped_requests{0};
+    std::atomic<bool> capped_logged{false};
     // KmerMatch Count / Reads (KmerTask, service.cpp:1537-1544 -> find_kmer_reads :466-502): answered here when on
     bool serve_kmer = false;
     std::atomic<uint64_t> kmer_requests{0};
@@ -516,12 +519,15 @@ struct rsbwt_service {
         any_unserved = any_unserved && unserved_empty && !other;
         if (!any_reads && !any_kmer && !any_unserved) return;
         reply_arena rr, kr;
-        std::vector<char> handled_r(n, 0), handled_k(n, 0);
+        std::vector<char> handled_r(n, 0), handled_k(n, 0), capped_r;
         if (any_reads) {
-            rc = service_reads_batch(set, job.rq, per_partition, reads_cfg, &rr, &handled_r);
+            rc = service_reads_batch(set, job.rq, per_partition, reads_cfg, &rr, &handled_r, &capped_r);
             if (rc != RSBWT_OK) {
                 note_failure(rc, n, "read");
                 service_reads_empty(job.rq, rows, &rr, &handled_r);
+            } else {
+                for (size_t i = 0; i < capped_r.size(); ++i)
+                    if (capped_r[i]) note_capped(job.rq[i]);
             }
         }
         if (any_kmer) {
@@ -570,6 +576,13 @@ struct rsbwt_service {
         if (unserved_logged.compare_exchange_strong(expected, true))
             fprintf(stderr, "rsbwt service: answering requests this service does not serve (first: type %d, return type %d) with empty results\n",
                     r.t, r.rt);
+    }
+    void note_capped(const service_request &r) {
+        capped_requests++;
+        bool expected = false;
+        if (capped_logged.compare_exchange_strong(expected, true))
+            fprintf(stderr, "rsbwt service: a Reads request brings more than max_match_reads = %llu reads and is answered with none (first: a query of %zu symbols)\n",
+                    (unsigned long long)reads_cfg.max_match_reads, r.q.size());
     }
     void kmer_empty(const window_job &job, size_t rows, reply_arena *kr, std::vector<char> *handled_k) {
         const size_t n = job.rq.size();
@@ -984,6 +997,16 @@ int rsbwt_service_set_kmermatch(rsbwt_service_t *s, int enable) {
         return RSBWT_OK;
     });
 }
+
+int rsbwt_service_set_max_match_reads(rsbwt_service_t *s, uint64_t n) {
+    return guarded("rsbwt_service_set_max_match_reads", [&]() -> int {
+        if (!s) return fail(RSBWT_EINVAL, "null service");
+        if (n && !query_engine_hooks.query_var_capped) return fail(RSBWT_ENODEV, "max_match_reads needs the engine: it is not part of this build");
+        s->reads_cfg.max_match_reads = n;
+        return RSBWT_OK;
+    });
+}
+uint64_t rsbwt_service_capped_requests(const rsbwt_service_t *s) { return s ? s->capped_requests.load() : 0; }
 
 void rsbwt_service_set_unserved(rsbwt_service_t *s, int empty) {
     if (s) s->unserved_empty = empty != 0;

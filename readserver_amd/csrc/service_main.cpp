@@ -16,6 +16,8 @@
 //   exactmatch = "extract" | "search";            how "is this tile itself a read?" is answered (Reads, KmerMatch): by extracting
 //                                                 the reads of its interval, or by backward search from the terminator
 //                                                 rows (rsbwt_exactmatch_by_search); the replies are the same (default extract)
+//   max_match_reads = "100000";                   an ExactMatch-Reads query (each strand by itself) that brings more reads than
+//                                                 this over all shards is answered with none (default: absent or "0", no limit)
 //   unserved = "empty";                           requests of any other kind get 2 x shards Replies with no matches
 //                                                 (default: no reply, as before)
 // and then sends 2 x shards replies per request (front-end `workers` = 2 x shards) or 2 (`summed`).
@@ -56,6 +58,11 @@ int main(int argc, char **argv) {
     const char *exactmatch = get(cfg, "exactmatch", "extract");
     if (strcmp(exactmatch, "extract") != 0 && strcmp(exactmatch, "search") != 0) {
         fprintf(stderr, "service.cfg: exactmatch = \"%s\": \"extract\" or \"search\"\n", exactmatch);
+        return EXIT_FAILURE;
+    }
+    const char *max_match = get(cfg, "max_match_reads", "0");
+    if (!*max_match || strspn(max_match, "0123456789") != strlen(max_match) || strlen(max_match) > 19) {
+        fprintf(stderr, "service.cfg: max_match_reads = \"%s\": a non-negative decimal number\n", max_match);
         return EXIT_FAILURE;
     }
     const bool serve_kmer = strcmp(kmermatch, "on") == 0;
@@ -107,6 +114,10 @@ int main(int argc, char **argv) {
     // min_read_length / max_read_length: service.cpp:1417-1420 (defaults 73 / 100, :56-57)
     rsbwt_service_set_reads(svc, serve_reads ? 1 : 0, (uint32_t)atoi(get(cfg, "min_read_length", "0")), (uint32_t)atoi(get(cfg, "max_read_length", "0")));
     if (rsbwt_service_set_kmermatch(svc, serve_kmer ? 1 : 0) != RSBWT_OK) {
+        fprintf(stderr, "%s\n", rsbwt_last_error());
+        return EXIT_FAILURE;
+    }
+    if (rsbwt_service_set_max_match_reads(svc, strtoull(max_match, nullptr, 10)) != RSBWT_OK) {
         fprintf(stderr, "%s\n", rsbwt_last_error());
         return EXIT_FAILURE;
     }

@@ -410,9 +410,14 @@ static int for_each_parallel(size_t n, F &&fn) {
     return rc;
 }
 
+query_engine query_engine_hooks = {nullptr};
+
 int service_reads_batch(rsbwt_set_t *set, const std::vector<service_request> &rq, bool per_partition, const reads_config &cfg,
-                        reply_arena *replies, std::vector<char> *handled) {
+                        reply_arena *replies, std::vector<char> *handled, std::vector<char> *capped) {
     const size_t n = rq.size(), S = rsbwt_set_size(set);
+    if (capped) capped->assign(n, 0);
+    const uint64_t LIMIT = cfg.max_match_reads;
+    if (LIMIT && !query_engine_hooks.query_var_capped) return fail(RSBWT_ENODEV, "max_match_reads needs the engine: it is not part of this build");
     const size_t MINL = cfg.min_read_length, MAXL = cfg.max_read_length;
     handled->assign(n, 0);
     replies->bytes.clear();
@@ -430,6 +435,7 @@ int service_reads_batch(rsbwt_set_t *set, const std::vector<service_request> &rq
         std::string w;
         std::vector<std::vector<std::string>> tiles;  // [shard]: tiles that are reads of that partition, in find_reads' order
         std::vector<std::vector<std::string>> reads;  // [shard]: query(w) / the interval's rows
+        bool over = false;                            // its rows exceed cfg.max_match_reads: answered with no matches at all
     };
     std::vector<job_t> jobs;
     for (size_t i = 0; i < n; ++i) {
@@ -536,16 +542,22 @@ int service_reads_batch(rsbwt_set_t *set, const std::vector<service_request> &rq
         std::vector<char> reads;
         std::vector<uint32_t> rlen, rshard;
         size_t room = 16 * m + 256;  // reads the buffers hold: one call answers when they fit, else it says how many there are
+        // (with a limit a query brings LIMIT rows at most: the call itself bounds what the buffers must hold)
+        std::vector<uint64_t> matches(LIMIT ? m : 0);
         for (int attempt = 0;; ++attempt) {
             int rc = RSBWT_ERANGE;
             for (int sized = 0; sized < 2 && rc == RSBWT_ERANGE; ++sized) {
                 reads.assign(room * (size_t)stride, 0);
                 rlen.assign(room, 0);
                 rshard.assign(room, 0);
-                rc = rsbwt_set_query_var(set, flat.data(), qoff.data(), m, first.data(), rshard.data(), reads.data(), stride, rlen.data(), room, &nreads);
+                rc = LIMIT ? query_engine_hooks.query_var_capped(set, flat.data(), qoff.data(), m, LIMIT, first.data(), rshard.data(), reads.data(),
+                                                                 stride, rlen.data(), room, &nreads, matches.data())
+                           : rsbwt_set_query_var(set, flat.data(), qoff.data(), m, first.data(), rshard.data(), reads.data(), stride, rlen.data(), room, &nreads);
                 if (rc == RSBWT_ERANGE && nreads > room) room = nreads;
             }
             if (rc != RSBWT_OK) return rc;
+            for (size_t j = 0; j < matches.size(); ++j)
+                if (matches[j] > LIMIT) jobs[members[j]].over = true;
             if (nreads == 0) break;
             bool over = false;
             for (size_t r = 0; r < nreads && !over; ++r) over = rlen[r] == 0xFFFFFFFFu;
@@ -574,6 +586,13 @@ int service_reads_batch(rsbwt_set_t *set, const std::vector<service_request> &rq
         return RSBWT_OK;
     });
     if (rc_len != RSBWT_OK) return rc_len;
+    // a strand over the limit: no tile matches either -- the Reply of an empty result (rsbwt_proto_encode_empty_reply)
+    for (job_t &jb : jobs)
+        if (jb.over) {
+            for (auto &l : jb.tiles) l.clear();
+            for (auto &l : jb.reads) l.clear();
+            if (capped) (*capped)[jb.req] = 1;
+        }
     if (timing) t_query = now();
     // ---- Reply bytes: request by request, partition by partition (or all partitions' lists joined, shard 0's first),
     // forward then reverse complement

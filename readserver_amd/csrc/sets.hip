@@ -26,6 +26,7 @@
 #include "../../include/rsbwt.h"
 #include "capi_guard.h"
 #include "capi_internal.h"
+#include "service.h"
 
 using namespace rsb;
 
@@ -1209,6 +1210,224 @@ int rsbwt_set_query(rsbwt_set_t *s, const char *kmers, size_t Q, uint32_t k, siz
                     size_t *nreads) {
     return guarded("rsbwt_set_query", [&]() -> int {
         return rsbwt_set_query_body(s, kmers, Q, k, stride, first, read_shard, reads, read_stride, read_len, cap_reads, nreads);
+    });
+}
+
+// ---- rsbwt_set_query_var with a limit on the rows of one query; the intervals' rows made on the GPU (interval_rows.hip) ----
+namespace {
+// the calling thread's last capped query: rows expanded on the device, rows uploaded from the host, queries over the
+// limit, bytes copied to the host before the extraction was launched
+thread_local uint64_t capped_last_work[4] = {0, 0, 0, 0};
+
+enum { CAPPED_TAKE_HOST = 1 };  // (not an error: the device path leaves the call to the host path)
+
+// One device group holding every shard: the search leaves its pairs [S][Q] in HBM, the totals / scans / fill make first[],
+// matches[] and the rows there, the ragged walks (extract_lines.hip) take the rows where they are.  What crosses to the
+// host before the walks are launched: first[] and matches[] (the caller's answers; first[Q] sizes the launches) and one
+// counter -- never an interval or a row.
+int query_capped_device(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t max_rows, uint64_t *first,
+                        uint32_t *read_shard, char *reads, uint32_t read_stride, uint32_t *read_len, size_t cap_reads, size_t *nreads,
+                        uint64_t *matches) {
+    dev_group *g = s->groups[0];
+    const uint32_t S = (uint32_t)g->idx.size();
+    int rc = use_device(g->device);
+    if (rc) return rc;
+    call_ctx *c = g->pool.acquire();
+    if (!c) return fail(RSBWT_EHIP, "cannot create a HIP stream");
+    hipStream_t st = c->st[0];
+    scratch_cache::lease la, lb;
+    struct release_t {
+        dev_group *g;
+        call_ctx *c;
+        scratch_cache::lease *la, *lb;
+        ~release_t() {
+            (void)hipStreamSynchronize(c->st[0]);
+            g->scratch.give(*la, c->st[0]);
+            g->scratch.give(*lb, c->st[0]);
+            g->pool.release(c);
+        }
+    } release{g, c, &la, &lb};
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t cells = (size_t)S * Q;
+    const size_t a_pairs = al(cells * 16), a_q = al((Q + 1) * 8), a_cells = al((cells + 1) * 8), a_tmp = interval_rows_scan_bytes(cells + 1) + 256;
+    hipError_t e = g->scratch.take(a_pairs + 3 * a_q + 2 * a_cells + 256 + a_tmp, st, &la);
+    if (e != hipSuccess) return fail_hip(e, "scratch for a capped query");
+    uint8_t *d_pairs = (uint8_t *)la.p, *d_matches = d_pairs + a_pairs, *d_kept = d_matches + a_q, *d_first = d_kept + a_q,
+            *d_cellw = d_first + a_q, *d_cellpos = d_cellw + a_cells, *d_over = d_cellpos + a_cells, *d_tmp = d_over + 256;
+    // ---- the search, sliced as search_host_views_var slices it; every slice's pairs land in the batch's [S][Q] block
+    const size_t SLICE = 1u << 16;
+    std::vector<uint64_t> rel;
+    for (size_t q0 = 0; q0 < Q; q0 += SLICE) {
+        const size_t mq = std::min(SLICE, Q - q0);
+        uint64_t kmax = 0;
+        for (size_t i = 0; i < mq; ++i) {
+            if (off[q0 + i + 1] < off[q0 + i]) return fail(RSBWT_EINVAL, "query %zu: its end lies before its start", q0 + i);
+            const uint64_t n = off[q0 + i + 1] - off[q0 + i];
+            if (n <= 65535ull) kmax = std::max(kmax, n);
+        }
+        if (kmax == 0) {  // nothing to search: pairs of all ones are no interval of any shard (upper >= n)
+            HIP_OK(hipMemset2DAsync(d_pairs + q0 * 16, Q * 16, 0xFF, mq * 16, S, st));
+            continue;
+        }
+        const uint32_t k = (uint32_t)kmax, wpq = (k + 31u) / 32u;
+        const size_t tb = (size_t)(off[q0 + mq] - off[q0]);
+        const size_t a_text = al(tb + 16), a_off = al((mq + 1) * 8), a_pk = al(mq * wpq * 8), a_ok = al(mq), a_len = al(mq * 4),
+                     a_rec = al((size_t)S * mq * 16), a_res = mq == Q ? 0 : al((size_t)S * mq * 16);
+        if ((rc = c->stage(a_text + a_off + a_pk + a_ok + a_len + a_rec + a_res)) != RSBWT_OK) return rc;
+        uint8_t *d_text = (uint8_t *)c->d_stage, *d_off = d_text + a_text, *d_pk = d_off + a_off, *d_ok = d_pk + a_pk, *d_len = d_ok + a_ok,
+                *d_rec = d_len + a_len, *d_res = mq == Q ? d_pairs : d_rec + a_rec;
+        rel.resize(mq + 1);
+        for (size_t i = 0; i <= mq; ++i) rel[i] = off[q0 + i] - off[q0];
+        if (tb) HIP_OK(hipMemcpyAsync(d_text, text + off[q0], tb, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_off, rel.data(), (mq + 1) * 8, hipMemcpyHostToDevice, st));
+        e = launch_pack_var(d_text, d_off, mq, wpq, d_pk, d_ok, d_len, st);
+        if (e != hipSuccess) return fail_hip(e, "pack kernel launch");
+        e = launch_search_init_var(g->d_views, S, d_pk, d_ok, d_len, mq, wpq, d_rec, st);
+        if (e != hipSuccess) return fail_hip(e, "start-record kernel launch");
+        search_extra ex;
+        ex.narrow = group_is_narrow(s, g, k);
+        ex.d_init = d_rec;
+        ex.pairs = true;
+        if ((rc = search_launch(*g, g->d_views, S, g->num_cus, d_pk, d_ok, mq, k, d_res, nullptr, false, st, &ex)) != RSBWT_OK) return rc;
+        if (mq != Q) HIP_OK(hipMemcpy2DAsync(d_pairs + q0 * 16, Q * 16, d_res, mq * 16, mq * 16, S, hipMemcpyDeviceToDevice, st));
+        HIP_OK(hipStreamSynchronize(st));  // (rel and the staging buffer are used again by the next slice)
+    }
+    // ---- totals, the limit, first[]; the cells of the kept rows
+    const size_t tmp_bytes = a_tmp - 256;
+    e = launch_interval_totals(g->d_views, S, d_pairs, Q, max_rows, d_matches, d_kept, d_first, d_over, d_tmp, tmp_bytes, st);
+    if (e == hipSuccess) e = launch_interval_cells(g->d_views, S, d_pairs, Q, max_rows, d_matches, d_cellw, d_cellpos, d_tmp, tmp_bytes, st);
+    if (e != hipSuccess) return fail_hip(e, "interval-rows kernels");
+    uint64_t over = 0;
+    HIP_OK(hipMemcpyAsync(first, d_first, (Q + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (matches) HIP_OK(hipMemcpyAsync(matches, d_matches, Q * 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(&over, d_over, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    const uint64_t total = first[Q];
+    *nreads = (size_t)total;
+    capped_last_work[2] = over;
+    capped_last_work[3] = (Q + 1) * 8 + (matches ? Q * 8 : 0) + 8;
+    if (total > cap_reads) return fail(RSBWT_ERANGE, "%llu reads over the set, room for %zu", (unsigned long long)total, cap_reads);
+    if (total == 0) return RSBWT_OK;
+    if (!reads || !read_len) return fail(RSBWT_EINVAL, "null argument");
+    if (total >= (1ull << 31)) return CAPPED_TAKE_HOST;  // (the walk kernels number a launch's rows in 32 bits)
+    // ---- the rows, by cell for the walks and as (shard, cell row) in the caller's order; the ragged walks; the copy back
+    if ((rc = ensure_group_xviews(s, g, st)) != RSBWT_OK) return rc;
+    const size_t a_rows = al(total * 8), a_u32 = al(total * 4), a_out = al(total * (size_t)read_stride);
+    e = g->scratch.take(a_rows + 4 * a_u32 + a_out, st, &lb);
+    if (e != hipSuccess) return fail(RSBWT_ENOMEM, "%llu reads of %u bytes do not fit the device's free memory: %s", (unsigned long long)total,
+                                     read_stride, hipGetErrorString(e));
+    uint8_t *d_crow = (uint8_t *)lb.p, *d_out = d_crow + a_rows, *d_dest = d_out + a_out, *d_shard = d_dest + a_u32, *d_plen = d_shard + a_u32,
+            *d_rlen = d_plen + a_u32;
+    e = launch_interval_fill(g->d_views, S, d_pairs, Q, d_first, (size_t)total, d_shard, nullptr, d_cellpos, d_crow, d_dest, st);
+    if (e == hipSuccess)
+        e = launch_extract_ragged(g->scratch, g->d_xviews, S, d_crow, (size_t)total, d_cellpos, Q, d_out, read_stride, d_plen, d_rlen, g->num_cus, st);
+    if (e != hipSuccess) return fail_hip(e, "row expansion and extract kernel launches");
+    capped_last_work[0] = total;
+    std::vector<char> ho(total * (size_t)read_stride);
+    std::vector<uint32_t> hl(total), hd(total), hs(total);
+    HIP_OK(hipMemcpyAsync(ho.data(), d_out, total * (size_t)read_stride, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(hl.data(), d_rlen, total * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(hd.data(), d_dest, total * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(hs.data(), d_shard, total * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (size_t t = 0; t < total; ++t) {
+        const size_t cell = hd[t];
+        const uint32_t keep = hl[cell] == 0xFFFFFFFFu ? 0u : hl[cell];
+        if (keep) memcpy(reads + t * (size_t)read_stride, ho.data() + cell * (size_t)read_stride, keep);
+        read_len[t] = hl[cell];
+        if (read_shard) read_shard[t] = (uint32_t)g->idx[hs[t]];
+    }
+    return RSBWT_OK;
+}
+
+int query_capped_body(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t max_rows, uint64_t *first,
+                      uint32_t *read_shard, char *reads, uint32_t read_stride, uint32_t *read_len, size_t cap_reads, size_t *nreads,
+                      uint64_t *matches) {
+    if (!s || !nreads || (!first && Q)) return fail(RSBWT_EINVAL, "null argument");
+    *nreads = 0;
+    for (uint64_t &w : capped_last_work) w = 0;
+    if (Q == 0) return RSBWT_OK;
+    if (read_stride == 0) return fail(RSBWT_EINVAL, "read_stride must be positive");
+    if (!off || (!text && off[Q] != off[0])) return fail(RSBWT_EINVAL, "null argument");
+    for (rsbwt_t *h : s->shards)
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
+    const size_t S = s->shards.size();
+    static const bool turns_only = getenv("RSBWT_SET_EXTRACT_TURNS") != nullptr;        // A/B knobs (tools/README.md)
+    static const bool host_rows = getenv("RSBWT_SET_QUERY_HOST_ROWS") != nullptr;
+    if (s->groups.size() == 1 && S <= 1024 && !turns_only && !host_rows) {
+        const int rc = query_capped_device(s, text, off, Q, max_rows, first, read_shard, reads, read_stride, read_len, cap_reads, nreads, matches);
+        if (rc != CAPPED_TAKE_HOST) return rc;
+        for (uint64_t &w : capped_last_work) w = 0;
+    }
+    // several device groups (or a batch of 2^31 rows): the intervals come to the host, the limit is applied there, and the
+    // rows go the way rsbwt_set_query_var's go
+    std::vector<uint64_t> lo(S * Q), up(S * Q);
+    const int rc = rsbwt_set_find_intervals_var_body(s, text, off, Q, lo.data(), up.data(), false);
+    if (rc) return rc;
+    uint64_t over = 0;
+    for (size_t q = 0; q < Q; ++q) {
+        uint64_t m = 0;
+        for (size_t i = 0; i < S; ++i) {
+            const uint64_t l = lo[i * Q + q], u = up[i * Q + q];
+            if (l <= u && u < s->shards[i]->view.n) m += u - l + 1;
+        }
+        if (matches) matches[q] = m;
+        if (max_rows && m > max_rows) {
+            ++over;
+            for (size_t i = 0; i < S; ++i) { lo[i * Q + q] = 1; up[i * Q + q] = 0; }
+        }
+    }
+    capped_last_work[2] = over;
+    capped_last_work[3] = S * Q * 16;
+    const int rq = set_query_rows(s, Q, lo, up, first, read_shard, reads, read_stride, read_len, cap_reads, nreads);
+    if (rq == RSBWT_OK) capped_last_work[1] = *nreads;
+    return rq;
+}
+
+// the service code's way in (service.h: service_slice.cpp is also linked into host harnesses without the engine)
+struct register_query_hooks {
+    register_query_hooks() { rsb::query_engine_hooks.query_var_capped = rsbwt_set_query_var_capped; }
+} register_query_hooks_now;
+}  // namespace
+
+int rsbwt_set_query_var_capped(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t max_rows, uint64_t *first,
+                               uint32_t *read_shard, char *reads, uint32_t read_stride, uint32_t *read_len, size_t cap_reads,
+                               size_t *nreads, uint64_t *matches) {
+    return guarded("rsbwt_set_query_var_capped", [&]() -> int {
+        return query_capped_body(s, text, off, Q, max_rows, first, read_shard, reads, read_stride, read_len, cap_reads, nreads, matches);
+    });
+}
+
+void rsbwt_set_query_last_work(uint64_t *work4) {
+    if (work4) memcpy(work4, capped_last_work, sizeof capped_last_work);
+}
+
+// the expansion alone, on the caller's buffers and stream: one-device set, nothing synchronised
+int rsbwt_set_interval_rows_dev(rsbwt_set_t *s, const void *d_pairs, size_t Q, uint64_t max_rows, void *d_first, void *d_matches,
+                                void *d_shard, void *d_rows, size_t cap, void *stream) {
+    return guarded("rsbwt_set_interval_rows_dev", [&]() -> int {
+        if (!s) return fail(RSBWT_EINVAL, "null set");
+        if (s->groups.size() != 1) return fail(RSBWT_EINVAL, "the set spans %zu devices: device-resident calls need one", s->groups.size());
+        if (!d_first || (Q && (!d_pairs || !d_matches)) || (cap && (!d_shard || !d_rows))) return fail(RSBWT_EINVAL, "null argument");
+        if (cap >= (1ull << 38)) return fail(RSBWT_ERANGE, "room for %zu rows: at most 2^38 per call", cap);
+        dev_group *g = s->groups[0];
+        int rc = use_device(g->device);
+        if (rc) return rc;
+        hipStream_t st = (hipStream_t)stream;
+        if (Q == 0) {
+            HIP_OK(hipMemsetAsync(d_first, 0, 8, st));
+            return RSBWT_OK;
+        }
+        const size_t a_q = ((Q + 1) * 8 + 255) & ~(size_t)255, tmp_bytes = interval_rows_scan_bytes(Q + 1);
+        scratch_cache::lease mem;
+        hipError_t e = g->scratch.take(a_q + 256 + tmp_bytes + 256, st, &mem);
+        if (e != hipSuccess) return fail_hip(e, "scratch for the interval rows");
+        uint8_t *d_kept = (uint8_t *)mem.p, *d_over = d_kept + a_q, *d_tmp = d_over + 256;
+        const uint32_t S = (uint32_t)g->idx.size();
+        e = launch_interval_totals(g->d_views, S, d_pairs, Q, max_rows, d_matches, d_kept, d_first, d_over, d_tmp, tmp_bytes, st);
+        if (e == hipSuccess) e = launch_interval_fill(g->d_views, S, d_pairs, Q, d_first, cap, d_shard, d_rows, nullptr, nullptr, nullptr, st);
+        g->scratch.give(mem, st);
+        return e == hipSuccess ? RSBWT_OK : fail_hip(e, "interval-rows kernels");
     });
 }
 

@@ -145,8 +145,6 @@ struct slow_call_timer {
         if (_e != hipSuccess) return fail_hip(_e, #x);         \
     } while (0)
 
-inline uint32_t words_per_kmer(uint32_t k) { return k ? (k + 31u) / 32u : 1u; }
-
 struct ctx_guard {
     ctx_pool &pool;
     call_ctx *c;
@@ -1029,17 +1027,13 @@ int search_host_views(search_meter &m, ctx_pool &pool, const shard_view *d_views
     return RSBWT_OK;
 }
 
-// The same for queries of LENGTHS OF THEIR OWN: query q = text[off[q] .. off[q+1]) (search_lines.hip, search_init_var_kernel:
-// a start record says where its search goes on).  lower / upper [nshards][Q]; an empty query, one with a symbol outside
-// ACGT or one longer than 65,535 symbols ends as (1, 0) / count 0.
-int search_host_views_var(search_meter &m, ctx_pool &pool, const shard_view *d_views, uint32_t nshards, int num_cus,
-                          const char *text, const uint64_t *off, size_t Q, uint64_t *lower, uint64_t *upper, bool counts_only,
-                          bool narrow) {
-    ctx_guard g(pool);
-    if (!g.c) return fail(RSBWT_EHIP, "cannot create a HIP stream");
-    hipStream_t st = g.c->st[0];
+// The loop of every call over a host batch of queries of LENGTHS OF THEIR OWN (capi_internal.h).
+int for_each_var_slice(call_ctx &c, hipStream_t st, const char *text, const uint64_t *off, size_t Q,
+                       const std::function<size_t(size_t)> &extra_bytes, const std::function<int(size_t, size_t)> &empty,
+                       const std::function<int(const var_slice &)> &run) {
     const size_t SLICE = 1u << 16;
     std::vector<uint64_t> rel;
+    int rc;
     for (size_t q0 = 0; q0 < Q; q0 += SLICE) {
         const size_t mq = std::min(SLICE, Q - q0);
         uint64_t kmax = 0;
@@ -1049,41 +1043,71 @@ int search_host_views_var(search_meter &m, ctx_pool &pool, const shard_view *d_v
             if (n <= 65535ull) kmax = std::max(kmax, n);  // (a longer one is refused by the packing: it does not size the batch)
         }
         if (kmax == 0) {  // nothing to search in this slice
+            if ((rc = empty(q0, mq)) != RSBWT_OK) return rc;
+            continue;
+        }
+        var_slice sl;
+        sl.q0 = q0;
+        sl.mq = mq;
+        sl.k = (uint32_t)kmax;
+        sl.wpq = words_per_kmer(sl.k);
+        const size_t tb = (size_t)(off[q0 + mq] - off[q0]);
+        const size_t a_text = al256(tb + 16), a_off = al256((mq + 1) * 8), a_pk = al256(mq * sl.wpq * 8), a_ok = al256(mq), a_len = al256(mq * 4);
+        if ((rc = c.stage(a_text + a_off + a_pk + a_ok + a_len + extra_bytes(mq))) != RSBWT_OK) return rc;
+        uint8_t *d_text = (uint8_t *)c.d_stage, *d_off = d_text + a_text;
+        sl.d_pk = d_off + a_off;
+        sl.d_ok = sl.d_pk + a_pk;
+        sl.d_len = sl.d_ok + a_ok;
+        sl.d_extra = sl.d_len + a_len;
+        rel.resize(mq + 1);
+        for (size_t i = 0; i <= mq; ++i) rel[i] = off[q0 + i] - off[q0];
+        if (tb) HIP_OK(hipMemcpyAsync(d_text, text + off[q0], tb, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_off, rel.data(), (mq + 1) * 8, hipMemcpyHostToDevice, st));
+        const hipError_t e = launch_pack_var(d_text, d_off, mq, sl.wpq, sl.d_pk, sl.d_ok, sl.d_len, st);
+        if (e != hipSuccess) return fail_hip(e, "pack kernel launch");
+        if ((rc = run(sl)) != RSBWT_OK) return rc;
+        HIP_OK(hipStreamSynchronize(st));  // (rel and the staging buffer are used again by the next slice)
+    }
+    return RSBWT_OK;
+}
+
+// search_host_views for such queries (search_lines.hip, search_init_var_kernel: a start record says where a query's
+// search goes on).  lower / upper [nshards][Q]; an empty query, one with a symbol outside ACGT or one longer than
+// 65,535 symbols ends as (1, 0) / count 0.
+int search_host_views_var(search_meter &m, ctx_pool &pool, const shard_view *d_views, uint32_t nshards, int num_cus,
+                          const char *text, const uint64_t *off, size_t Q, uint64_t *lower, uint64_t *upper, bool counts_only,
+                          bool narrow) {
+    ctx_guard g(pool);
+    if (!g.c) return fail(RSBWT_EHIP, "cannot create a HIP stream");
+    hipStream_t st = g.c->st[0];
+    auto a_rec = [&](size_t mq) { return al256((size_t)nshards * mq * 16); };
+    auto a_res = [&](size_t mq) { return al256((size_t)nshards * mq * 8); };
+    return for_each_var_slice(
+        *g.c, st, text, off, Q, [&](size_t mq) { return a_rec(mq) + 2 * a_res(mq); },
+        [&](size_t q0, size_t mq) -> int {
             for (uint32_t s = 0; s < nshards; ++s)
                 for (size_t i = 0; i < mq; ++i) {
                     lower[s * Q + q0 + i] = counts_only ? 0 : 1;
                     if (!counts_only) upper[s * Q + q0 + i] = 0;
                 }
-            continue;
-        }
-        const uint32_t k = (uint32_t)kmax, wpq = words_per_kmer(k);
-        const size_t tb = (size_t)(off[q0 + mq] - off[q0]);
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t a_text = al(tb + 16), a_off = al((mq + 1) * 8), a_pk = al(mq * wpq * 8), a_ok = al(mq), a_len = al(mq * 4),
-                     a_rec = al((size_t)nshards * mq * 16), a_res = al((size_t)nshards * mq * 8);
-        int rc;
-        if ((rc = g.c->stage(a_text + a_off + a_pk + a_ok + a_len + a_rec + 2 * a_res)) != RSBWT_OK) return rc;
-        uint8_t *d_text = (uint8_t *)g.c->d_stage, *d_off = d_text + a_text, *d_pk = d_off + a_off, *d_ok = d_pk + a_pk, *d_len = d_ok + a_ok,
-                *d_rec = d_len + a_len, *d_lo = d_rec + a_rec, *d_up = d_lo + a_res;
-        rel.resize(mq + 1);
-        for (size_t i = 0; i <= mq; ++i) rel[i] = off[q0 + i] - off[q0];
-        if (tb) HIP_OK(hipMemcpyAsync(d_text, text + off[q0], tb, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(d_off, rel.data(), (mq + 1) * 8, hipMemcpyHostToDevice, st));
-        hipError_t e = launch_pack_var(d_text, d_off, mq, wpq, d_pk, d_ok, d_len, st);
-        if (e != hipSuccess) return fail_hip(e, "pack kernel launch");
-        e = launch_search_init_var(d_views, nshards, d_pk, d_ok, d_len, mq, wpq, d_rec, st);
-        if (e != hipSuccess) return fail_hip(e, "start-record kernel launch");
-        search_extra ex;
-        ex.narrow = narrow;
-        ex.d_init = d_rec;
-        if ((rc = search_launch(m, d_views, nshards, num_cus, d_pk, d_ok, mq, k, d_lo, d_up, counts_only, st, &ex)) != RSBWT_OK) return rc;
-        for (uint32_t s = 0; s < nshards; ++s) {
-            HIP_OK(hipMemcpyAsync(lower + s * Q + q0, d_lo + (size_t)s * mq * 8, mq * 8, hipMemcpyDeviceToHost, st));
-            if (!counts_only) HIP_OK(hipMemcpyAsync(upper + s * Q + q0, d_up + (size_t)s * mq * 8, mq * 8, hipMemcpyDeviceToHost, st));
-        }
-        HIP_OK(hipStreamSynchronize(st));  // (rel and the staging buffer are used again by the next slice)
-    }
-    return RSBWT_OK;
+            return RSBWT_OK;
+        },
+        [&](const var_slice &sl) -> int {
+            const size_t q0 = sl.q0, mq = sl.mq;
+            uint8_t *d_rec = sl.d_extra, *d_lo = d_rec + a_rec(mq), *d_up = d_lo + a_res(mq);
+            const hipError_t e = launch_search_init_var(d_views, nshards, sl.d_pk, sl.d_ok, sl.d_len, mq, sl.wpq, d_rec, st);
+            if (e != hipSuccess) return fail_hip(e, "start-record kernel launch");
+            search_extra ex;
+            ex.narrow = narrow;
+            ex.d_init = d_rec;
+            const int rc = search_launch(m, d_views, nshards, num_cus, sl.d_pk, sl.d_ok, mq, sl.k, d_lo, d_up, counts_only, st, &ex);
+            if (rc) return rc;
+            for (uint32_t s = 0; s < nshards; ++s) {
+                HIP_OK(hipMemcpyAsync(lower + s * Q + q0, d_lo + (size_t)s * mq * 8, mq * 8, hipMemcpyDeviceToHost, st));
+                if (!counts_only) HIP_OK(hipMemcpyAsync(upper + s * Q + q0, d_up + (size_t)s * mq * 8, mq * 8, hipMemcpyDeviceToHost, st));
+            }
+            return RSBWT_OK;
+        });
 }
 }  // namespace rsb
 
@@ -1234,55 +1258,36 @@ int read_copies_host_views(search_meter &m, ctx_pool &pool, const shard_view *d_
     return RSBWT_OK;
 }
 
-// The same for queries of lengths of their own, sliced as search_host_views_var slices them: an empty query, one with a
-// symbol outside ACGT or one longer than 65,535 symbols gives 0 / 0.
+// The same for queries of lengths of their own (for_each_var_slice): an empty query, one with a symbol outside ACGT or
+// one longer than 65,535 symbols gives 0 / 0.
 int read_copies_host_views_var(search_meter &m, ctx_pool &pool, const shard_view *d_views, uint32_t nshards, int num_cus,
                                const char *text, const uint64_t *off, size_t Q, uint64_t *copies, uint64_t *ending) {
     ctx_guard g(pool);
     if (!g.c) return fail(RSBWT_EHIP, "cannot create a HIP stream");
     hipStream_t st = g.c->st[0];
-    const size_t SLICE = 1u << 16;
-    std::vector<uint64_t> rel;
-    for (size_t q0 = 0; q0 < Q; q0 += SLICE) {
-        const size_t mq = std::min(SLICE, Q - q0);
-        uint64_t kmax = 0;
-        for (size_t i = 0; i < mq; ++i) {
-            if (off[q0 + i + 1] < off[q0 + i]) return fail(RSBWT_EINVAL, "query %zu: its end lies before its start", q0 + i);
-            const uint64_t n = off[q0 + i + 1] - off[q0 + i];
-            if (n <= 65535ull) kmax = std::max(kmax, n);
-        }
-        if (kmax == 0) {  // nothing to search in this slice
+    auto a_scr = [&](size_t mq) { return al256(read_copies_scratch_bytes(nshards, mq)); };
+    auto a_res = [&](size_t mq) { return al256((size_t)nshards * mq * 8); };
+    return for_each_var_slice(
+        *g.c, st, text, off, Q, [&](size_t mq) { return a_scr(mq) + 2 * a_res(mq); },
+        [&](size_t q0, size_t mq) -> int {
             for (uint32_t s = 0; s < nshards; ++s)
                 for (size_t i = 0; i < mq; ++i) {
                     copies[s * Q + q0 + i] = 0;
                     if (ending) ending[s * Q + q0 + i] = 0;
                 }
-            continue;
-        }
-        const uint32_t k = (uint32_t)kmax, wpq = words_per_kmer(k);
-        const size_t tb = (size_t)(off[q0 + mq] - off[q0]);
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t a_text = al(tb + 16), a_off = al((mq + 1) * 8), a_pk = al(mq * wpq * 8), a_ok = al(mq), a_len = al(mq * 4),
-                     a_scr = al(read_copies_scratch_bytes(nshards, mq)), a_res = al((size_t)nshards * mq * 8);
-        int rc;
-        if ((rc = g.c->stage(a_text + a_off + a_pk + a_ok + a_len + a_scr + 2 * a_res)) != RSBWT_OK) return rc;
-        uint8_t *d_text = (uint8_t *)g.c->d_stage, *d_off = d_text + a_text, *d_pk = d_off + a_off, *d_ok = d_pk + a_pk, *d_len = d_ok + a_ok,
-                *d_scr = d_len + a_len, *d_cp = d_scr + a_scr, *d_en = d_cp + a_res;
-        rel.resize(mq + 1);
-        for (size_t i = 0; i <= mq; ++i) rel[i] = off[q0 + i] - off[q0];
-        if (tb) HIP_OK(hipMemcpyAsync(d_text, text + off[q0], tb, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(d_off, rel.data(), (mq + 1) * 8, hipMemcpyHostToDevice, st));
-        hipError_t e = launch_pack_var(d_text, d_off, mq, wpq, d_pk, d_ok, d_len, st);
-        if (e != hipSuccess) return fail_hip(e, "pack kernel launch");
-        if ((rc = read_copies_launch(m, d_views, nshards, num_cus, d_pk, d_ok, d_len, mq, k, d_scr, d_cp, ending ? d_en : nullptr, st)) != RSBWT_OK)
-            return rc;
-        for (uint32_t s = 0; s < nshards; ++s) {
-            HIP_OK(hipMemcpyAsync(copies + s * Q + q0, d_cp + (size_t)s * mq * 8, mq * 8, hipMemcpyDeviceToHost, st));
-            if (ending) HIP_OK(hipMemcpyAsync(ending + s * Q + q0, d_en + (size_t)s * mq * 8, mq * 8, hipMemcpyDeviceToHost, st));
-        }
-        HIP_OK(hipStreamSynchronize(st));  // (rel and the staging buffer are used again by the next slice)
-    }
-    return RSBWT_OK;
+            return RSBWT_OK;
+        },
+        [&](const var_slice &sl) -> int {
+            const size_t q0 = sl.q0, mq = sl.mq;
+            uint8_t *d_scr = sl.d_extra, *d_cp = d_scr + a_scr(mq), *d_en = d_cp + a_res(mq);
+            const int rc = read_copies_launch(m, d_views, nshards, num_cus, sl.d_pk, sl.d_ok, sl.d_len, mq, sl.k, d_scr, d_cp, ending ? d_en : nullptr, st);
+            if (rc) return rc;
+            for (uint32_t s = 0; s < nshards; ++s) {
+                HIP_OK(hipMemcpyAsync(copies + s * Q + q0, d_cp + (size_t)s * mq * 8, mq * 8, hipMemcpyDeviceToHost, st));
+                if (ending) HIP_OK(hipMemcpyAsync(ending + s * Q + q0, d_en + (size_t)s * mq * 8, mq * 8, hipMemcpyDeviceToHost, st));
+            }
+            return RSBWT_OK;
+        });
 }
 
 }  // namespace rsb

@@ -9,6 +9,7 @@
 
 #include <atomic>
 #include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <vector>
 
@@ -65,6 +66,24 @@ int search_host_views(search_meter &m, ctx_pool &pool, const shard_view *d_views
 int search_host_views_var(search_meter &m, ctx_pool &pool, const shard_view *d_views, uint32_t nshards, int num_cus,
                           const char *text, const uint64_t *off, size_t Q, uint64_t *lower, uint64_t *upper, bool counts_only,
                           bool narrow = false);
+inline uint32_t words_per_kmer(uint32_t k) { return k ? (k + 31u) / 32u : 1u; }
+inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+// THE loop over a host batch of queries of lengths of their own (query q = text[off[q] .. off[q+1])), for every call
+// that takes one (capi.hip).  The batch goes up in slices of 65,536 queries on `st`; per slice the loop refuses an
+// off[] that runs backwards, sizes the slice by its longest query of at most 65,535 symbols (k), lays text, relative
+// offsets, packed words, valid bytes and lengths out in c's staging buffer, each part 256-aligned, uploads, packs
+// (launch_pack_var), hands the slice to run() and synchronises `st` before the staging buffer is used again.
+//   extra_bytes(mq)  what the call wants behind d_len for a slice of mq queries: d_extra
+//   empty(q0, mq)    the answers of a slice with nothing to search (k would be 0): nothing is uploaded or launched
+//   run(slice)       the call's launches and copies back, enqueued on `st`
+struct var_slice {
+    size_t q0, mq;    // queries q0 .. q0 + mq of the batch
+    uint32_t k, wpq;  // the longest query's symbols; packed words per query
+    uint8_t *d_pk, *d_ok, *d_len, *d_extra;
+};
+int for_each_var_slice(call_ctx &c, hipStream_t st, const char *text, const uint64_t *off, size_t Q,
+                       const std::function<size_t(size_t)> &extra_bytes, const std::function<int(size_t, size_t)> &empty,
+                       const std::function<int(const var_slice &)> &run);
 // search_extra::narrow for a launch on this shard: a T-mer's interval is ~ n / 4^T rows wide;
 // a quarter of a window or less = the steps after the table find both positions in one line
 inline bool view_is_narrow(const shard_view &v, uint32_t k) {

@@ -232,6 +232,34 @@ int for_each_group(rsbwt_set_t *s, F &&fn) {
     return RSBWT_OK;
 }
 
+// Inside for_each_group, for calls that answer [num_shards][Q] arrays in the set's shard order (b: an optional second
+// array): fn(g, a', b') does group gi's work into [S_g][Q] blocks.  When the group's shards sit next to each other in
+// the set (the usual map: shard s -> GPU s / 8) those blocks ARE the caller's rows; else they are temporaries whose
+// row j is copied to row idx[j].
+template <class F>
+int group_scatter(rsbwt_set_t *s, size_t gi, size_t Q, uint64_t *a, uint64_t *b, F &&fn) {
+    dev_group *g = s->groups[gi];
+    int rc = use_device(g->device);
+    if (rc) return rc;
+    const size_t Sg = g->idx.size(), at = g->idx.front() * Q;
+    if (g->idx.back() - g->idx.front() + 1 == Sg) return fn(g, a + at, b ? b + at : nullptr);
+    std::vector<uint64_t> ta(Sg * Q), tb(b ? Sg * Q : 0);
+    if ((rc = fn(g, ta.data(), b ? tb.data() : nullptr)) != RSBWT_OK) return rc;
+    for (size_t j = 0; j < Sg; ++j) {
+        memcpy(a + g->idx[j] * Q, ta.data() + j * Q, Q * 8);
+        if (b) memcpy(b + g->idx[j] * Q, tb.data() + j * Q, Q * 8);
+    }
+    return RSBWT_OK;
+}
+
+// What every device-resident call of a set starts with: they serve a set whose shards all sit on one device.
+int one_device_group(rsbwt_set_t *s, dev_group **g) {
+    if (!s) return fail(RSBWT_EINVAL, "null set");
+    if (s->groups.size() != 1) return fail(RSBWT_EINVAL, "the set spans %zu devices: device-resident calls need one", s->groups.size());
+    *g = s->groups[0];
+    return use_device((*g)->device);
+}
+
 }  // namespace
 
 extern "C" {
@@ -457,25 +485,10 @@ static int rsbwt_set_find_intervals_body(rsbwt_set_t *s, const char *kmers, size
     for (rsbwt_t *h : s->shards)
         if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
     return for_each_group(s, [&](size_t gi) -> int {
-        dev_group *g = s->groups[gi];
-        int rc = use_device(g->device);
-        if (rc) return rc;
-        // a group's shards are searched into a [S_g][Q] block; when they sit next to each other in
-        // the set (the usual map: shard s -> GPU s / 8) that block IS the output
-        const size_t Sg = g->idx.size();
-        const bool contiguous = g->idx.back() - g->idx.front() + 1 == Sg;
-        if (contiguous)
-            return search_host_views(*g, g->pool, g->d_views, (uint32_t)Sg, g->num_cus, kmers, Q, k, stride,
-                                     lower + g->idx.front() * Q, upper + g->idx.front() * Q, false, group_is_narrow(s, g, k));
-        std::vector<uint64_t> lo(Sg * Q), up(Sg * Q);
-        rc = search_host_views(*g, g->pool, g->d_views, (uint32_t)Sg, g->num_cus, kmers, Q, k, stride, lo.data(), up.data(), false,
-                               group_is_narrow(s, g, k));
-        if (rc) return rc;
-        for (size_t j = 0; j < Sg; ++j) {
-            memcpy(lower + g->idx[j] * Q, lo.data() + j * Q, Q * 8);
-            memcpy(upper + g->idx[j] * Q, up.data() + j * Q, Q * 8);
-        }
-        return RSBWT_OK;
+        return group_scatter(s, gi, Q, lower, upper, [&](dev_group *g, uint64_t *lo, uint64_t *up) -> int {
+            return search_host_views(*g, g->pool, g->d_views, (uint32_t)g->idx.size(), g->num_cus, kmers, Q, k, stride, lo, up, false,
+                                     group_is_narrow(s, g, k));
+        });
     });
 }
 int rsbwt_set_find_intervals(rsbwt_set_t *s, const char *kmers, size_t Q, uint32_t k, size_t stride,
@@ -497,24 +510,10 @@ static int rsbwt_set_find_intervals_var_body(rsbwt_set_t *s, const char *text, c
     for (size_t q = 0; q < Q; ++q)
         if (off[q + 1] >= off[q] && off[q + 1] - off[q] <= 65535ull) kmax = std::max(kmax, off[q + 1] - off[q]);
     return for_each_group(s, [&](size_t gi) -> int {
-        dev_group *g = s->groups[gi];
-        int rc = use_device(g->device);
-        if (rc) return rc;
-        const size_t Sg = g->idx.size();
-        const bool narrow = kmax != 0 && group_is_narrow(s, g, (uint32_t)kmax);
-        const bool contiguous = g->idx.back() - g->idx.front() + 1 == Sg;
-        if (contiguous)
-            return search_host_views_var(*g, g->pool, g->d_views, (uint32_t)Sg, g->num_cus, text, off, Q, lower + g->idx.front() * Q,
-                                         counts_only ? nullptr : upper + g->idx.front() * Q, counts_only, narrow);
-        std::vector<uint64_t> lo(Sg * Q), up(counts_only ? 0 : Sg * Q);
-        rc = search_host_views_var(*g, g->pool, g->d_views, (uint32_t)Sg, g->num_cus, text, off, Q, lo.data(), counts_only ? nullptr : up.data(),
-                                   counts_only, narrow);
-        if (rc) return rc;
-        for (size_t j = 0; j < Sg; ++j) {
-            memcpy(lower + g->idx[j] * Q, lo.data() + j * Q, Q * 8);
-            if (!counts_only) memcpy(upper + g->idx[j] * Q, up.data() + j * Q, Q * 8);
-        }
-        return RSBWT_OK;
+        return group_scatter(s, gi, Q, lower, counts_only ? nullptr : upper, [&](dev_group *g, uint64_t *lo, uint64_t *up) -> int {
+            return search_host_views_var(*g, g->pool, g->d_views, (uint32_t)g->idx.size(), g->num_cus, text, off, Q, lo, up, counts_only,
+                                         kmax != 0 && group_is_narrow(s, g, (uint32_t)kmax));
+        });
     });
 }
 int rsbwt_set_find_intervals_var(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *lower, uint64_t *upper) {
@@ -539,7 +538,7 @@ int rsbwt_set_count_var(rsbwt_set_t *s, const char *text, const uint64_t *off, s
 }
 
 // Whole-read matches of queries of lengths of their own (read_lookup.hip): copies / ending [num_shards][Q] in the set's
-// shard order, per device group one launch sequence over its shards, sliced as rsbwt_set_count_var is.
+// shard order, per device group one launch sequence over its shards, sliced as rsbwt_set_count_var is (for_each_var_slice).
 static int rsbwt_set_read_copies_var_body(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *copies,
                                           uint64_t *ending) {
     if (!s) return fail(RSBWT_EINVAL, "null set");
@@ -548,22 +547,9 @@ static int rsbwt_set_read_copies_var_body(rsbwt_set_t *s, const char *text, cons
     for (rsbwt_t *h : s->shards)
         if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
     return for_each_group(s, [&](size_t gi) -> int {
-        dev_group *g = s->groups[gi];
-        int rc = use_device(g->device);
-        if (rc) return rc;
-        const size_t Sg = g->idx.size();
-        const bool contiguous = g->idx.back() - g->idx.front() + 1 == Sg;
-        if (contiguous)
-            return read_copies_host_views_var(*g, g->pool, g->d_views, (uint32_t)Sg, g->num_cus, text, off, Q, copies + g->idx.front() * Q,
-                                              ending ? ending + g->idx.front() * Q : nullptr);
-        std::vector<uint64_t> cp(Sg * Q), en(ending ? Sg * Q : 0);
-        rc = read_copies_host_views_var(*g, g->pool, g->d_views, (uint32_t)Sg, g->num_cus, text, off, Q, cp.data(), ending ? en.data() : nullptr);
-        if (rc) return rc;
-        for (size_t j = 0; j < Sg; ++j) {
-            memcpy(copies + g->idx[j] * Q, cp.data() + j * Q, Q * 8);
-            if (ending) memcpy(ending + g->idx[j] * Q, en.data() + j * Q, Q * 8);
-        }
-        return RSBWT_OK;
+        return group_scatter(s, gi, Q, copies, ending, [&](dev_group *g, uint64_t *cp, uint64_t *en) -> int {
+            return read_copies_host_views_var(*g, g->pool, g->d_views, (uint32_t)g->idx.size(), g->num_cus, text, off, Q, cp, en);
+        });
     });
 }
 int rsbwt_set_read_copies_var(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *copies, uint64_t *ending) {
@@ -597,7 +583,7 @@ static int rsbwt_set_count_body(rsbwt_set_t *s, const char *kmers, size_t Q, uin
         if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
     const size_t G = s->groups.size();
     const bool use_rccl = G > 1 && ensure_comms(s);
-    const uint32_t wpq = k ? (k + 31u) / 32u : 1u;
+    const uint32_t wpq = words_per_kmer(k);
     const size_t SLICE = 1u << 20;
     std::vector<std::vector<uint64_t>> part(use_rccl ? 0 : G);
     for (size_t q0 = 0; q0 < Q; q0 += SLICE) {
@@ -682,10 +668,8 @@ int rsbwt_set_count(rsbwt_set_t *s, const char *kmers, size_t Q, uint32_t k, siz
 // d_lower/d_upper: [num_shards][Q].  Nothing is synchronised.
 int rsbwt_set_find_intervals_dev(rsbwt_set_t *s, const void *d_packed, const void *d_valid, size_t Q, uint32_t k,
                                  void *d_lower, void *d_upper, void *stream) {
-    if (!s) return fail(RSBWT_EINVAL, "null set");
-    if (s->groups.size() != 1) return fail(RSBWT_EINVAL, "the set spans %zu devices: device-resident calls need one", s->groups.size());
-    dev_group *g = s->groups[0];
-    int rc = use_device(g->device);
+    dev_group *g = nullptr;
+    int rc = one_device_group(s, &g);
     if (rc) return rc;
     search_extra ex;
     ex.narrow = group_is_narrow(s, g, k);
@@ -695,10 +679,8 @@ int rsbwt_set_find_intervals_dev(rsbwt_set_t *s, const void *d_packed, const voi
 
 int rsbwt_set_find_interval_pairs_dev(rsbwt_set_t *s, const void *d_packed, const void *d_valid, size_t Q, uint32_t k,
                                       void *d_pairs, void *stream) {
-    if (!s) return fail(RSBWT_EINVAL, "null set");
-    if (s->groups.size() != 1) return fail(RSBWT_EINVAL, "the set spans %zu devices: device-resident calls need one", s->groups.size());
-    dev_group *g = s->groups[0];
-    int rc = use_device(g->device);
+    dev_group *g = nullptr;
+    int rc = one_device_group(s, &g);
     if (rc) return rc;
     search_extra ex;
     ex.pairs = true;
@@ -715,26 +697,22 @@ size_t rsbwt_set_records_bytes(const rsbwt_set_t *s, size_t Q) { return s ? s->s
 
 int rsbwt_set_prepare_dev(rsbwt_set_t *s, const void *d_packed, const void *d_valid, size_t Q, uint32_t k, void *d_records,
                           void *stream) {
-    if (!s) return fail(RSBWT_EINVAL, "null set");
-    if (s->groups.size() != 1) return fail(RSBWT_EINVAL, "the set spans %zu devices: device-resident calls need one", s->groups.size());
+    dev_group *g = nullptr;
+    int rc = one_device_group(s, &g);
+    if (rc) return rc;
     if (Q == 0) return RSBWT_OK;
     if (!d_packed || !d_valid || !d_records) return fail(RSBWT_EINVAL, "null argument");
     if (k == 0 || k > 65535u) return fail(RSBWT_ERANGE, "k %u: 1..65535 symbols per k-mer", k);
-    dev_group *g = s->groups[0];
-    int rc = use_device(g->device);
-    if (rc) return rc;
     const hipError_t e = launch_search_init(g->d_views, (uint32_t)g->idx.size(), d_packed, d_valid, Q, k, d_records, (hipStream_t)stream);
     return e == hipSuccess ? RSBWT_OK : fail_hip(e, "start-record kernel launch");
 }
 
 int rsbwt_set_find_interval_pairs_prepared_dev(rsbwt_set_t *s, const void *d_packed, const void *d_valid, const void *d_records,
                                                size_t Q, uint32_t k, void *d_pairs, void *stream) {
-    if (!s) return fail(RSBWT_EINVAL, "null set");
-    if (s->groups.size() != 1) return fail(RSBWT_EINVAL, "the set spans %zu devices: device-resident calls need one", s->groups.size());
-    if (Q && !d_records) return fail(RSBWT_EINVAL, "null argument");
-    dev_group *g = s->groups[0];
-    int rc = use_device(g->device);
+    dev_group *g = nullptr;
+    int rc = one_device_group(s, &g);
     if (rc) return rc;
+    if (Q && !d_records) return fail(RSBWT_EINVAL, "null argument");
     search_extra ex;
     ex.pairs = true;
     ex.d_init = d_records;
@@ -745,10 +723,8 @@ int rsbwt_set_find_interval_pairs_prepared_dev(rsbwt_set_t *s, const void *d_pac
 
 int rsbwt_set_count_dev(rsbwt_set_t *s, const void *d_packed, const void *d_valid, size_t Q, uint32_t k,
                         void *d_counts, void *stream) {
-    if (!s) return fail(RSBWT_EINVAL, "null set");
-    if (s->groups.size() != 1) return fail(RSBWT_EINVAL, "the set spans %zu devices: device-resident calls need one", s->groups.size());
-    dev_group *g = s->groups[0];
-    int rc = use_device(g->device);
+    dev_group *g = nullptr;
+    int rc = one_device_group(s, &g);
     if (rc) return rc;
     search_extra ex;
     ex.narrow = group_is_narrow(s, g, k);
@@ -841,7 +817,7 @@ static int fused_1mm_launches(rsbwt_set_t *s, dev_group *g, const fused_1mm_layo
                               void *d_upper, void *d_bits, hipStream_t st) {
     const uint32_t S = (uint32_t)s->shards.size();
     const size_t V = 3 * (size_t)k + 1, mv = m * V;
-    const uint8_t *d_vok = d_var + ((mv * ((k + 31u) / 32u) * 8 + 15) & ~(size_t)15);
+    const uint8_t *d_vok = d_var + ((mv * words_per_kmer(k) * 8 + 15) & ~(size_t)15);
     search_extra resumed;
     if (L.tn) {
         search_extra traced;
@@ -872,24 +848,22 @@ size_t rsbwt_set_1mm_scratch_bytes(const rsbwt_set_t *s, size_t m, uint32_t k) {
 
 static int rsbwt_set_find_intervals_1mm_dev_body(rsbwt_set_t *s, const void *d_packed, const void *d_valid, size_t m, uint32_t k,
                                      void *d_lower, void *d_upper, void *d_scratch, void *stream) {
-    if (!s) return fail(RSBWT_EINVAL, "null set");
-    if (s->groups.size() != 1) return fail(RSBWT_EINVAL, "the set spans %zu devices: device-resident calls need one", s->groups.size());
+    dev_group *g = nullptr;
+    int rc = one_device_group(s, &g);
+    if (rc) return rc;
     if (m == 0) return RSBWT_OK;
     if (!d_lower || !d_upper) return fail(RSBWT_EINVAL, "null argument");
     const size_t row = m * (3 * (size_t)k + 1) * 8;
     fused_1mm_layout L;
     if (fused_1mm_applies(s, m, k, &L, true)) {
         if (!d_packed || !d_valid || !d_scratch) return fail(RSBWT_EINVAL, "null argument");
-        dev_group *g = s->groups[0];
-        int rc = use_device(g->device);
-        if (rc) return rc;
         uint8_t *d_var = (uint8_t *)d_scratch, *d_trace = d_var + ((variants_bytes(m, k) + 255) & ~(size_t)255), *d_own = d_trace + L.trace;
         if ((rc = variants_of_batch_dev(d_packed, d_valid, m, k, d_var, (hipStream_t)stream)) != RSBWT_OK) return rc;
         return fused_1mm_launches(s, g, L, d_packed, d_valid, m, k, d_var, d_trace, d_own, d_lower, d_upper, nullptr, (hipStream_t)stream);
     }
     for (size_t i = 0; i < s->shards.size(); ++i) {
-        const int rc = rsbwt_find_intervals_1mm_dev(s->shards[i], d_packed, d_valid, m, k, (uint8_t *)d_lower + i * row,
-                                                    (uint8_t *)d_upper + i * row, d_scratch, stream);
+        rc = rsbwt_find_intervals_1mm_dev(s->shards[i], d_packed, d_valid, m, k, (uint8_t *)d_lower + i * row,
+                                          (uint8_t *)d_upper + i * row, d_scratch, stream);
         if (rc) return rc;
     }
     return RSBWT_OK;
@@ -1254,44 +1228,30 @@ int query_capped_device(rsbwt_set_t *s, const char *text, const uint64_t *off, s
     if (e != hipSuccess) return fail_hip(e, "scratch for a capped query");
     uint8_t *d_pairs = (uint8_t *)la.p, *d_matches = d_pairs + a_pairs, *d_kept = d_matches + a_q, *d_first = d_kept + a_q,
             *d_cellw = d_first + a_q, *d_cellpos = d_cellw + a_cells, *d_over = d_cellpos + a_cells, *d_tmp = d_over + 256;
-    // ---- the search, sliced as search_host_views_var slices it; every slice's pairs land in the batch's [S][Q] block
-    const size_t SLICE = 1u << 16;
-    std::vector<uint64_t> rel;
-    for (size_t q0 = 0; q0 < Q; q0 += SLICE) {
-        const size_t mq = std::min(SLICE, Q - q0);
-        uint64_t kmax = 0;
-        for (size_t i = 0; i < mq; ++i) {
-            if (off[q0 + i + 1] < off[q0 + i]) return fail(RSBWT_EINVAL, "query %zu: its end lies before its start", q0 + i);
-            const uint64_t n = off[q0 + i + 1] - off[q0 + i];
-            if (n <= 65535ull) kmax = std::max(kmax, n);
-        }
-        if (kmax == 0) {  // nothing to search: pairs of all ones are no interval of any shard (upper >= n)
+    // ---- the search (for_each_var_slice); every slice's pairs land in the batch's [S][Q] block: the only slice writes
+    // them there, one of several leaves them behind its start records and they are copied over row by row
+    auto a_rec = [&](size_t mq) { return al((size_t)S * mq * 16); };
+    rc = for_each_var_slice(
+        *c, st, text, off, Q, [&](size_t mq) { return a_rec(mq) + (mq == Q ? 0 : al((size_t)S * mq * 16)); },
+        [&](size_t q0, size_t mq) -> int {  // nothing to search: pairs of all ones are no interval of any shard (upper >= n)
             HIP_OK(hipMemset2DAsync(d_pairs + q0 * 16, Q * 16, 0xFF, mq * 16, S, st));
-            continue;
-        }
-        const uint32_t k = (uint32_t)kmax, wpq = (k + 31u) / 32u;
-        const size_t tb = (size_t)(off[q0 + mq] - off[q0]);
-        const size_t a_text = al(tb + 16), a_off = al((mq + 1) * 8), a_pk = al(mq * wpq * 8), a_ok = al(mq), a_len = al(mq * 4),
-                     a_rec = al((size_t)S * mq * 16), a_res = mq == Q ? 0 : al((size_t)S * mq * 16);
-        if ((rc = c->stage(a_text + a_off + a_pk + a_ok + a_len + a_rec + a_res)) != RSBWT_OK) return rc;
-        uint8_t *d_text = (uint8_t *)c->d_stage, *d_off = d_text + a_text, *d_pk = d_off + a_off, *d_ok = d_pk + a_pk, *d_len = d_ok + a_ok,
-                *d_rec = d_len + a_len, *d_res = mq == Q ? d_pairs : d_rec + a_rec;
-        rel.resize(mq + 1);
-        for (size_t i = 0; i <= mq; ++i) rel[i] = off[q0 + i] - off[q0];
-        if (tb) HIP_OK(hipMemcpyAsync(d_text, text + off[q0], tb, hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(d_off, rel.data(), (mq + 1) * 8, hipMemcpyHostToDevice, st));
-        e = launch_pack_var(d_text, d_off, mq, wpq, d_pk, d_ok, d_len, st);
-        if (e != hipSuccess) return fail_hip(e, "pack kernel launch");
-        e = launch_search_init_var(g->d_views, S, d_pk, d_ok, d_len, mq, wpq, d_rec, st);
-        if (e != hipSuccess) return fail_hip(e, "start-record kernel launch");
-        search_extra ex;
-        ex.narrow = group_is_narrow(s, g, k);
-        ex.d_init = d_rec;
-        ex.pairs = true;
-        if ((rc = search_launch(*g, g->d_views, S, g->num_cus, d_pk, d_ok, mq, k, d_res, nullptr, false, st, &ex)) != RSBWT_OK) return rc;
-        if (mq != Q) HIP_OK(hipMemcpy2DAsync(d_pairs + q0 * 16, Q * 16, d_res, mq * 16, mq * 16, S, hipMemcpyDeviceToDevice, st));
-        HIP_OK(hipStreamSynchronize(st));  // (rel and the staging buffer are used again by the next slice)
-    }
+            return RSBWT_OK;
+        },
+        [&](const var_slice &sl) -> int {
+            const size_t q0 = sl.q0, mq = sl.mq;
+            uint8_t *d_rec = sl.d_extra, *d_res = mq == Q ? d_pairs : d_rec + a_rec(mq);
+            const hipError_t ei = launch_search_init_var(g->d_views, S, sl.d_pk, sl.d_ok, sl.d_len, mq, sl.wpq, d_rec, st);
+            if (ei != hipSuccess) return fail_hip(ei, "start-record kernel launch");
+            search_extra ex;
+            ex.narrow = group_is_narrow(s, g, sl.k);
+            ex.d_init = d_rec;
+            ex.pairs = true;
+            const int rs = search_launch(*g, g->d_views, S, g->num_cus, sl.d_pk, sl.d_ok, mq, sl.k, d_res, nullptr, false, st, &ex);
+            if (rs) return rs;
+            if (mq != Q) HIP_OK(hipMemcpy2DAsync(d_pairs + q0 * 16, Q * 16, d_res, mq * 16, mq * 16, S, hipMemcpyDeviceToDevice, st));
+            return RSBWT_OK;
+        });
+    if (rc) return rc;
     // ---- totals, the limit, first[]; the cells of the kept rows
     const size_t tmp_bytes = a_tmp - 256;
     e = launch_interval_totals(g->d_views, S, d_pairs, Q, max_rows, d_matches, d_kept, d_first, d_over, d_tmp, tmp_bytes, st);
@@ -1406,13 +1366,11 @@ void rsbwt_set_query_last_work(uint64_t *work4) {
 int rsbwt_set_interval_rows_dev(rsbwt_set_t *s, const void *d_pairs, size_t Q, uint64_t max_rows, void *d_first, void *d_matches,
                                 void *d_shard, void *d_rows, size_t cap, void *stream) {
     return guarded("rsbwt_set_interval_rows_dev", [&]() -> int {
-        if (!s) return fail(RSBWT_EINVAL, "null set");
-        if (s->groups.size() != 1) return fail(RSBWT_EINVAL, "the set spans %zu devices: device-resident calls need one", s->groups.size());
+        dev_group *g = nullptr;
+        int rc = one_device_group(s, &g);
+        if (rc) return rc;
         if (!d_first || (Q && (!d_pairs || !d_matches)) || (cap && (!d_shard || !d_rows))) return fail(RSBWT_EINVAL, "null argument");
         if (cap >= (1ull << 38)) return fail(RSBWT_ERANGE, "room for %zu rows: at most 2^38 per call", cap);
-        dev_group *g = s->groups[0];
-        int rc = use_device(g->device);
-        if (rc) return rc;
         hipStream_t st = (hipStream_t)stream;
         if (Q == 0) {
             HIP_OK(hipMemsetAsync(d_first, 0, 8, st));
@@ -1499,13 +1457,11 @@ static int set_hits_1mm_fused(rsbwt_set_t *s, dev_group *g, const fused_1mm_layo
 // d_hits: [num_shards][cap_per_shard] records of 32 B (rsbwt_hits_1mm_dev's), d_totals: u64[num_shards]
 int rsbwt_set_hits_1mm_dev(rsbwt_set_t *s, const void *d_packed, const void *d_valid, size_t m, uint32_t k, void *d_hits,
                            size_t cap_per_shard, void *d_totals, void *d_scratch, void *stream) {
-    if (!s) return fail(RSBWT_EINVAL, "null set");
-    if (s->groups.size() != 1) return fail(RSBWT_EINVAL, "the set spans %zu devices: device-resident calls need one", s->groups.size());
-    if (!d_totals || (!d_hits && cap_per_shard)) return fail(RSBWT_EINVAL, "null argument");
-    dev_group *g = s->groups[0];
-    const size_t S = s->shards.size();
-    int rc = use_device(g->device);
+    dev_group *g = nullptr;
+    int rc = one_device_group(s, &g);
     if (rc) return rc;
+    if (!d_totals || (!d_hits && cap_per_shard)) return fail(RSBWT_EINVAL, "null argument");
+    const size_t S = s->shards.size();
     if (m == 0) {
         HIP_OK(hipMemsetAsync(d_totals, 0, 8 * S, (hipStream_t)stream));
         return RSBWT_OK;
@@ -1560,24 +1516,22 @@ int rsbwt_set_hits_1mm_dev(rsbwt_set_t *s, const void *d_packed, const void *d_v
 // fraction of the rows per lane.
 int rsbwt_set_extract_dev(rsbwt_set_t *s, const void *d_rows, size_t n, void *d_out, uint32_t stride, void *d_len,
                           void *d_prefix_len, void *stream) {
-    if (!s) return fail(RSBWT_EINVAL, "null set");
-    if (s->groups.size() != 1) return fail(RSBWT_EINVAL, "the set spans %zu devices: device-resident calls need one", s->groups.size());
+    dev_group *g = nullptr;
+    int rc = one_device_group(s, &g);
+    if (rc) return rc;
     if (n == 0) return RSBWT_OK;
     if (!d_rows || !d_out || !d_len || !d_prefix_len) return fail(RSBWT_EINVAL, "null argument");
     if (stride == 0) return fail(RSBWT_EINVAL, "stride must be positive");
-    dev_group *g = s->groups[0];
     const size_t S = s->shards.size();
     static const bool turns_only = getenv("RSBWT_SET_EXTRACT_TURNS") != nullptr;  // A/B knob (tools/README.md): a launch sequence per shard
     if (turns_only || n > (1ull << 31)) {
         for (size_t i = 0; i < S; ++i) {
-            const int rc = rsbwt_extract_dev(s->shards[i], (const uint8_t *)d_rows + i * n * 8, n, (uint8_t *)d_out + i * n * (size_t)stride,
-                                             stride, (uint8_t *)d_len + i * n * 4, (uint8_t *)d_prefix_len + i * n * 4, stream);
+            rc = rsbwt_extract_dev(s->shards[i], (const uint8_t *)d_rows + i * n * 8, n, (uint8_t *)d_out + i * n * (size_t)stride,
+                                   stride, (uint8_t *)d_len + i * n * 4, (uint8_t *)d_prefix_len + i * n * 4, stream);
             if (rc) return rc;
         }
         return RSBWT_OK;
     }
-    int rc = use_device(g->device);
-    if (rc) return rc;
     if ((rc = ensure_group_xviews(s, g, (hipStream_t)stream)) != RSBWT_OK) return rc;
     unsigned long long *work = nullptr;
     if (g->counting) {  // rsbwt_set_set_counting: the walk kernels' counters over all shards, read with rsbwt_set_last_search_counters

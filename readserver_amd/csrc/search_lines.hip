@@ -261,6 +261,12 @@ search_init_1mm_kernel(const shard_view *__restrict__ shards, uint32_t nshards, 
 
 // work[] of a counting launch
 enum { WORK_STEPS = 0, WORK_OCC = 1, WORK_LINES = 2, WORK_KTAB = 3, WORK_PHASE0 = 4, WORK_PASSES = 10, WORK_HOPS = 11, WORK_SOLO = 12 };
+// Every word has a reader already (13-15: the 1-mismatch launches' and the '$' count's, which share the block with the
+// search before them), so the one-lane kernel's count of results that left unstaged is asked for: RSBWT_COUNT_UNSTAGED
+// (launch_solo; tools/staged_results_probe.py) adds it to word 15 of a counting launch.  With the knob set word 15 is
+// WRONG for its other readers -- rsbwt_read_copies' second lines (read_lookup.hip, tools/exactmatch_probe.py) get the
+// search's unstaged results added: a probe's knob, never set where those are read.
+enum { WORK_UNSTAGED = 15 };
 
 // LONGK: k > 32, i.e. a query spans several packed words.  A template parameter because with the
 // reload on the path -- however it is guarded at run time -- hipcc waits for vmcnt(0) at the top of
@@ -711,8 +717,9 @@ static void launch_solo(int grid, hipStream_t stream, const shard_view *shards, 
     // RSBWT_NO_STAGED_RESULTS: A/B knob (tools/README.md); also what leaves LDS to kernels running beside the search.
     static const bool no_staged = getenv("RSBWT_NO_STAGED_RESULTS") != nullptr;
     const bool staged = !CO && pairs != 2u && !no_staged;
-    const uint32_t pa = pairs | (staged ? SOLO_STAGED_RESULTS : 0u);
-    const size_t dyn = staged ? SOLO_RESULTS_LDS : 0u;
+    static const bool count_unstaged = getenv("RSBWT_COUNT_UNSTAGED") != nullptr;  // probe knob (tools/README.md)
+    const uint32_t pa = pairs | (staged ? SOLO_STAGED_RESULTS : 0u) | (CW && count_unstaged ? SOLO_COUNT_UNSTAGED : 0u);
+    const size_t dyn = staged ? SOLO_RESULTS_LDS : 0u;  // (WG_WAVES x RES_WAVE_LDS: search_solo.h)
     if (fused)  // (one shard, k <= 32, a k-mer table, no trace: the kernel makes its own start records)
         hipLaunchKernelGGL((search_solo_kernel<CW, CO, false, true>), dim3(grid), dim3(64 * WG_WAVES), dyn, stream, shards, nshards,
                            pk, init, valid, ctr, Q, k, wpq, lo, up, work, trace, trace_n, qchunk, pa);

@@ -16,11 +16,15 @@
 // workgroup): a lane's result is 16 bytes at its query's place, and lanes finish at passes of their own -- 8e7 scattered
 // 16-byte stores per headline launch, 6.6e7 EA write requests (profiles/r05_pmc_search_kernel.json).  A wave draws its
 // queries in order, so the 8 results of one 128-byte line of the result array all come from ONE wave, a few passes
-// apart: they are collected in LDS -- 15 line buffers per wave, a group of 8 consecutive queries (g = q >> 3) in buffer
-// g mod 15 if that was free when the group's first query was drawn -- and the lane that brings the last one in (an LDS
-// counter per buffer) has lanes 0..7 store the line whole.  A group whose buffer was still taken is not staged: its
-// lanes store as before.  The buffers' tags and counters are the wave's 16th line (2 KB per wave in all: with the line
-// slots exactly the 160 KB of a CU at four workgroups).
+// apart: they are collected in LDS -- RES_BUFS buffers per wave, a group of 8 consecutive queries (g = q >> 3) in buffer
+// g mod RES_BUFS if that was free when the group's first query was drawn -- and the lane that brings the last one in (an
+// LDS counter per buffer) has lanes 0..7 store the line whole.  A group whose buffer was still taken is not staged: its
+// lanes store as before.  2 KB per wave in all: with the line slots exactly the 160 KB of a CU at four workgroups.
+// A staged result is 8 bytes, {lower:40, width:24}: every interval the search produces has upper = lower + width - 1
+// (mod 2^64) -- a live one, an empty one after a step (width 0), the invalid (1, 0), the wrapped (0, 2^64 - 1) -- so
+// the flush rebuilds {lower, upper} exactly; 28 buffers of 64 bytes and their {tag, results still out} fit where 15
+// lines of 16-byte results did.  A result that does not fit (width >= 2^24 - 1, lower >= 2^40) is stored by its own lane
+// as an unstaged one is, and its slot says so (width RES_ESCAPED): the flush leaves that place alone.
 //
 // FUSED (a single shard behind a k-mer table, k <= 32, no trace): the kernel computes the start records itself -- no
 // start-record launch before it, no 16 bytes written and read back per search.  The record of a search is its k-mer
@@ -53,8 +57,27 @@ namespace rsb {
 
 constexpr uint64_t WL_DEAD = 1ull << 63;  // worklist record: an empty slot (bit 63 of its first word)
 constexpr uint32_t SOLO_STAGED_RESULTS = 4u;  // `pairs` bit 2: the launch brought SOLO_RESULTS_LDS bytes of dynamic LDS for staged results
-constexpr uint32_t SOLO_RESULTS_LDS = WG_WAVES * 2048u;
-constexpr uint32_t RES_BUFS = 15u;  // line buffers per wave (8 results each); the 16th line holds {tag, results still out} per buffer
+constexpr uint32_t SOLO_COUNT_UNSTAGED = 8u;  // `pairs` bit 3 (counting launches): work[WORK_UNSTAGED] += results stored by their own lane
+constexpr uint32_t RES_WAVE_LDS = 2048u;      // a wave's share of the staged results' LDS
+constexpr uint32_t SOLO_RESULTS_LDS = WG_WAVES * RES_WAVE_LDS;
+constexpr uint32_t RES_SLOT_BYTES = 8u;       // a staged result: {lower:40, width:24}
+constexpr uint32_t RES_STATE_BYTES = 8u;      // a buffer's {tag, results still out}
+constexpr uint32_t RES_BUFS = RES_WAVE_LDS / (8u * RES_SLOT_BYTES + RES_STATE_BYTES);  // buffers per wave (8 results each)
+static_assert(RES_BUFS * (8u * RES_SLOT_BYTES + RES_STATE_BYTES) <= RES_WAVE_LDS, "a wave's buffers and their state fit its 2 KB");
+static_assert(RES_WAVE_LDS == 2048u && RES_BUFS == 28u, "2 KB per wave: with the line slots a CU's 160 KB at four workgroups");
+static_assert(RES_BUFS >= 9u && RES_BUFS <= 64u, "a lane per buffer claims; at most 9 groups begin among a pass's 64 draws");
+constexpr uint32_t RES_WIDTH_BITS = 24u;
+constexpr uint32_t RES_ESCAPED = (1u << RES_WIDTH_BITS) - 1u;  // the slot's width when its result left by the lane's own store
+
+// The staged results pass from lane to lane through plain LDS accesses (the claiming lanes' tags and counts to the
+// lanes whose searches end; their slots to lanes 0..7 at the flush).  A wavefront-scope release / acquire fence on LDS
+// is what orders those accesses for the compiler -- it emits no instruction: a wave's LDS operations complete in
+// order -- and the wave barrier between them keeps the machine scheduler from moving anything across the hand-off.
+__device__ __forceinline__ void solo_lds_handoff() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+}
 
 #ifndef RSB_WALK1MM_WGS_PER_CU  // tuning knob (tools/build_variant.sh): the walk keeps three bases' counts across passes
 #define RSB_WALK1MM_WGS_PER_CU 3
@@ -70,7 +93,7 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                    ulonglong2 *__restrict__ trace, uint32_t trace_n, uint32_t qchunk, uint32_t pairs_arg,
                    const unsigned long long *__restrict__ wl_counts = nullptr, size_t wl_cap = 0, size_t wl_implicit = 0) {
     __shared__ uint4 s_stage[WG_WAVES][64 * SLOT_U4];
-    extern __shared__ uint4 s_results[];  // staged results: [WG_WAVES][2][64] x 16 B when `pairs_arg` bit 2 is set (else none)
+    extern __shared__ uint4 s_results[];  // staged results: [WG_WAVES] x RES_WAVE_LDS bytes when `pairs_arg` bit 2 is set (else none)
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = threadIdx.x >> 6;
     uint4 *stage = s_stage[wave];
@@ -80,13 +103,15 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
     constexpr bool CAN_STAGE = !COUNTS_ONLY && !WL && !WALK;
     // (group numbers are kept in 32 bits)
     const bool stage_out = CAN_STAGE && (pairs_arg & SOLO_STAGED_RESULTS) != 0u && pairs != 2u && Q < (1ull << 34);
-    uint4 *results = s_results + wave * 128u;
+    uint2 *results = reinterpret_cast<uint2 *>(s_results + wave * (RES_WAVE_LDS / 16u));  // [RES_BUFS][8] x {lower:40, width:24}
     uint32_t *res_state = reinterpret_cast<uint32_t *>(results + RES_BUFS * 8u);  // [RES_BUFS] x {tag, out}
+    const bool count_unstaged = COUNT_WORK && (pairs_arg & SOLO_COUNT_UNSTAGED) != 0u;
     const lds_u32 *mine0 = reinterpret_cast<const lds_u32 *>(stage + (lane & 7u) * 64u + (lane >> 3) * SLOT_U4);
 #define SOLO_MINE(d) (mine0 + (((((uint32_t)(d)) >> 2) ^ swz) << 2) + (((uint32_t)(d)) & 3u))
 
     unsigned long long w_steps = 0, w_occ = 0, w_lines = 0, w_hops = 0, w_ktab = 0, passes = 0;
     unsigned long long w_surv = 0, w_unstepped = 0;  // WALK (wave-uniform: popcounts of ballots)
+    unsigned long long w_unstaged = 0;  // plain results stored by their own lane
 
     uint32_t sid = blockIdx.x % nshards;
     for (uint32_t visited = 0; visited < nshards; ++visited, sid = (sid + 1u == nshards) ? 0u : sid + 1u) {
@@ -281,13 +306,13 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                 pool_next = taken < pool_end ? taken : pool_end;
                 if (CAN_STAGE && stage_out && pool_next > r0) {
                     // the groups of 8 queries that BEGIN among this pass's draws (at most 9): each gets its buffer,
-                    // g mod 15, if that is free (chunks are multiples of 64 and this wave's alone: a group is drawn here whole)
+                    // g mod RES_BUFS, if that is free (chunks are multiples of 64 and this wave's alone: a group is drawn here whole)
                     const uint64_t first = (r0 + 7ull) & ~7ull;
                     if (first < pool_next) {
                         const uint32_t ga = (uint32_t)(first >> 3), gb = (uint32_t)((pool_next - 1ull) >> 3) + 1u;
-                        const uint32_t ga15 = ga % RES_BUFS;
+                        const uint32_t gam = ga % RES_BUFS;
                         if (lane < RES_BUFS) {
-                            const uint32_t d = lane >= ga15 ? lane - ga15 : lane + RES_BUFS - ga15;
+                            const uint32_t d = lane >= gam ? lane - gam : lane + RES_BUFS - gam;
                             const uint32_t g = ga + d;
                             if (g < gb && res_state[2u * lane + 1u] == 0u) {
                                 const uint64_t q0 = (uint64_t)g << 3;
@@ -296,6 +321,7 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                             }
                         }
                     }
+                    solo_lds_handoff();  // the claims are released to the lanes whose searches end
                 }
             }
             // (FUSED: a reserve whose table entry is still to come keeps the pass going -- it is taken up two passes
@@ -629,6 +655,7 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                 nimp = imp;
                 if (WL && !imp) nq = (size_t)wl_index;  // from here on the search is known by its result index
             }
+            if (CAN_STAGE && stage_out) solo_lds_handoff();  // the claims are acquired before a tag is checked
             if (alive && done) {
                 if (trace_s) {  // (WL: `trace` carries the table entries read ahead, not a trace)
                     // the positions it never reached: a search resumed there ends where this one did
@@ -649,14 +676,22 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                     }
                 } else {
                     const uint32_t g32 = (uint32_t)(q >> 3), rb = g32 % RES_BUFS;
+                    bool own_store = true;
                     if (CAN_STAGE && stage_out && res_state[2u * rb] == g32) {
-                        results[rb * 8u + ((uint32_t)q & 7u)] = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+                        const uint64_t width = hi - lo + 1ull;  // (mod 2^64: 0 for every empty interval)
+                        own_store = width >= (uint64_t)RES_ESCAPED || (lo >> COUNT_BITS) != 0ull;
+                        results[rb * 8u + ((uint32_t)q & 7u)] =
+                            own_store ? make_uint2(0u, RES_ESCAPED << 8) : make_uint2((uint32_t)lo, (uint32_t)(lo >> 32) | ((uint32_t)width << 8));
                         last_in = atomicSub(&res_state[2u * rb + 1u], 1u) == 1u;  // (LDS: ds_add_rtn_u32)
-                    } else if (pairs) {
-                        reinterpret_cast<ulonglong2 *>(out_lo)[q] = make_ulonglong2(lo, hi);
-                    } else {
-                        out_lo[q] = lo;
-                        out_up[q] = hi;
+                    }
+                    if (own_store) {
+                        if (pairs) {
+                            reinterpret_cast<ulonglong2 *>(out_lo)[q] = make_ulonglong2(lo, hi);
+                        } else {
+                            out_lo[q] = lo;
+                            out_up[q] = hi;
+                        }
+                        if (count_unstaged) w_unstaged += 1;
                     }
                 }
                 has_q = false;
@@ -664,6 +699,7 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
             if (CAN_STAGE && stage_out) {
                 // the buffers whose last result has just come in: lanes 0..7 store the line whole (pairs), or its 64
                 // bytes of lower and of upper
+                solo_lds_handoff();  // the slots written above are released to the lanes that read them here
                 uint64_t fm = __builtin_amdgcn_ballot_w64(last_in);
                 while (fm != 0ull) {
                     const int src = __builtin_ctzll(fm);
@@ -672,9 +708,12 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                     const uint32_t g = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(q >> 3), src), bsel = g % RES_BUFS;
                     const size_t qq = ((size_t)g << 3) + lane;
                     if (lane < 8u && qq < Qs) {
-                        const uint4 v = results[bsel * 8u + lane];
-                        const uint64_t vlo = ((uint64_t)v.y << 32) | v.x, vhi = ((uint64_t)v.w << 32) | v.z;
-                        if (pairs) {
+                        const uint2 v = results[bsel * 8u + lane];
+                        const uint32_t width = v.y >> 8;
+                        const uint64_t vlo = ((uint64_t)(v.y & 0xFFu) << 32) | v.x, vhi = vlo + width - 1ull;
+                        if (width == RES_ESCAPED) {
+                            // stored by its own lane already
+                        } else if (pairs) {
                             reinterpret_cast<ulonglong2 *>(out_lo)[qq] = make_ulonglong2(vlo, vhi);
                         } else {
                             out_lo[qq] = vlo;
@@ -694,6 +733,7 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
         if (w_lines) atomicAdd(&work[WORK_LINES], w_lines);
         if (w_ktab) atomicAdd(&work[WORK_KTAB], w_ktab);
         if (w_hops) atomicAdd(&work[WORK_HOPS], w_hops);
+        if (w_unstaged) atomicAdd(&work[WORK_UNSTAGED], w_unstaged);
         if (WALK && lane == 0u) {
             atomicAdd(&work[13], w_surv);       // variants alive after the step of their position (mm1_worklist.hip's words)
             atomicAdd(&work[14], w_unstepped);  // variants passed on unstepped

@@ -204,7 +204,13 @@ int rsbwt_hits_1mm(rsbwt_t *h, const char *kmers, size_t Q, uint32_t k, size_t s
  * (src/bwt/query.cpp:43-85; joined as query() does, :94-96) for n SA rows.  Row i's read is written
  * to out + i*stride (no NUL), its length to len[i] and the length of its prefix part to
  * prefix_len[i] (either may be NULL).  A read that does not fit `stride` bytes, or a row >= BWLen,
- * gets len = UINT32_MAX (the reference would loop forever / read out of bounds). */
+ * gets len = UINT32_MAX (the reference would loop forever / read out of bounds).
+ * "Fits" is |prefix| + |postfix| <= stride, for any stride > 0: a read of exactly `stride` symbols comes back whole, at
+ * every split point, one of stride + 1 never does.  Unspecified, and not to be relied on: the bytes of row i's own
+ * `stride` bytes past len[i] (all of them for a read that does not fit), and prefix_len[i] of a read that does not fit.
+ * Nothing outside out[0 .. n*stride) is written.  The stride and the alignment of the row block choose how the bytes
+ * are stored (16 at a time for stride % 16 == 0 on a 16-byte aligned block, 4 at a time for stride % 4 == 0 on a 4-byte
+ * aligned one, else byte by byte), never what is stored; the same holds for every form below that takes a stride. */
 int rsbwt_extract(rsbwt_t *h, const uint64_t *rows, size_t n, char *out, uint32_t stride,
                   uint32_t *len, uint32_t *prefix_len);
 

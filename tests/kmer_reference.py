@@ -49,14 +49,21 @@ def _expected(oix, w, k, skip, minl=73, maxl=100):
     return got
 
 
-def _bwt_runs(reads):
-    """the run bytes of the multi-string BWT of `reads` (RLUnit: symbol rank << 5 | length), duplicates kept: suffixes
-    ordered by their string, '$' lowest, equal ones by read index"""
-    rank = {"$": 0, "A": 1, "C": 2, "G": 3, "T": 4}
+def suffix_rows(reads):
+    """what every row of the multi-string BWT of `reads` is: row -> (read index i, offset j), the row of the suffix
+    reads[i][j:] + '$' -- suffixes ordered by their string, '$' lowest, equal ones by read index.  The read of the row is
+    reads[i], the part of it left of the row (extractPrefix) has j symbols; j == len(reads[i]) on the terminator rows."""
     tr = str.maketrans("ACGT", "BCDE")  # (keeps '$' below every base)
     suf = sorted((r[j:].translate(tr) + "$", i, j) for i, r in enumerate(reads) for j in range(len(r) + 1))
+    return [(i, j) for _, i, j in suf]
+
+
+def _bwt_runs(reads):
+    """the run bytes of the multi-string BWT of `reads` (RLUnit: symbol rank << 5 | length), duplicates kept: the symbol
+    left of every row of suffix_rows"""
+    rank = {"$": 0, "A": 1, "C": 2, "G": 3, "T": 4}
     runs = []
-    for _, i, j in suf:
+    for i, j in suffix_rows(reads):
         c = rank[reads[i][j - 1]] if j else 0
         if runs and runs[-1] >> 5 == c and runs[-1] & 31 < 31:
             runs[-1] += 1

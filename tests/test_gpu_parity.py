@@ -191,14 +191,21 @@ def test_gpu_extract_vs_oracle_and_limits(rsb, oracle):
     rng = np.random.default_rng(5)
     with rsb.GpuBWT(runs=runs) as g:
         n = g.getBWLen()
-        rows = np.concatenate([rng.integers(0, n, 3000), [0, 1, n - 1, n, n + 5]]).astype(np.uint64)
         stride = 192
+        # the rows whose suffix is '$' alone have an empty postfix; those among them whose prefix is exactly `stride` long
+        # (found with the oracle, whose batch form cuts a walk at the stride) are the one kind of row that fits with the
+        # prefix filling the whole buffer: three of them are always among the rows
+        ends = np.arange(oix.pc("A"), dtype=np.uint64)
+        _, eln, epl = oix.extract_batch(ends, stride=stride, nthreads=4)
+        full = ends[(eln == stride) & (epl == stride)]
+        assert full.size >= 3
+        rows = np.concatenate([rng.integers(0, n, 3000), [0, 1, n - 1, n, n + 5], full[:3]]).astype(np.uint64)
         out = np.zeros((rows.size, stride), np.uint8)
         ln = np.empty(rows.size, np.uint32)
         pl = np.empty(rows.size, np.uint32)
         assert L.rsbwt_extract(g.handle, rows.ctypes.data, rows.size, out.ctypes.data, stride,
                                ln.ctypes.data, pl.ctypes.data) == 0
-        ok = 0
+        ok = nofit = exact = prefix_full = prefix_full_more = 0
         for i, r in enumerate(rows):
             if r >= n:
                 assert ln[i] == 0xFFFFFFFF
@@ -208,16 +215,23 @@ def test_gpu_extract_vs_oracle_and_limits(rsb, oracle):
             pre = buf.raw[:a] if a != C.c_size_t(-1).value else None
             b = oix.L.rso_extract_postfix(oix.h, int(r), buf, 4096)
             post = buf.raw[:b] if b != C.c_size_t(-1).value else None
-            if pre is None or post is None or len(pre) + len(post) > stride or len(pre) > stride:
-                if pre is not None and post is not None and len(pre) + len(post) <= stride:
-                    pass
-                else:
-                    assert ln[i] == 0xFFFFFFFF or ln[i] == len(pre or b"") + len(post or b"")
-                    continue
+            # the fit rule of include/rsbwt.h, exactly: a length comes back iff both walks end and |pre| + |post| <= stride
+            fits = pre is not None and post is not None and len(pre) + len(post) <= stride
+            assert (ln[i] != 0xFFFFFFFF) == fits, (i, r, ln[i], pre and len(pre), post and len(post))
+            if pre is not None and post is not None:
+                exact += len(pre) + len(post) == stride
+                prefix_full += len(pre) == stride and len(post) == 0
+                prefix_full_more += len(pre) == stride and len(post) > 0
+            if not fits:
+                nofit += 1
+                continue
             assert ln[i] == len(pre) + len(post) and pl[i] == len(pre), (i, r)
             assert out[i, :ln[i]].tobytes() == pre + post
             ok += 1
-        assert ok > 1000
+        assert ok > 1000 and nofit > 0
+        # the boundary is met from both sides: reads of exactly `stride` symbols (split anywhere, and with the prefix
+        # alone filling the stride), and a prefix of `stride` symbols with a postfix still to come
+        assert exact > 3 and prefix_full >= 3 and prefix_full_more > 0, (exact, prefix_full, prefix_full_more)
 
 
 def test_gpu_single_query_mirrors(rsb, gix, golden):

@@ -482,6 +482,36 @@ int rsbwt_set_interval_rows_dev(rsbwt_set_t *s, const void *d_pairs, size_t Q, u
 /* calling thread's last rsbwt_set_query_var_capped: {rows expanded on the device, rows uploaded from the host,
  * queries over the limit, bytes copied to the host before the extraction was launched} */
 void rsbwt_set_query_last_work(uint64_t *work4);
+/* Locate: WHERE a row lies.  For SA row r the LF walk of extractPrefix (src/bwt/query.cpp:49-57: while BWT[r] != '$',
+ * r = C[b] + Occ(b, r) - 1) gives
+ *   read_row  the row the walk ends on: the row of the read's full suffix, whose BWT symbol is '$'
+ *   offset    the LF steps taken = the length extractPrefix returns = where the row's suffix starts in its read
+ *   ordinal   Occ('$', read_row) - 1, in [0, num_strings): a dense number of the read inside its shard
+ * A row >= bwlen, or one whose walk needs more than max_steps steps (0 = 2^20), is not located: read_row = ordinal =
+ * UINT64_MAX, offset = UINT32_MAX; the call still succeeds.  Any output may be NULL, not all of them.  No read is
+ * extracted: the calls need neither RSBWT_OPEN_READS nor select samples or psi hints, and build none.  The _dev forms
+ * take device pointers and a stream and synchronise nothing; rsbwt_set_locate takes rows as rsbwt_set_extract does (one
+ * launch per device walks all of that device's shards); rsbwt_set_locate_dev serves a set on ONE device and takes
+ * d_shard u32[n] / d_rows u64[n] as rsbwt_set_interval_rows_dev writes them. */
+int rsbwt_locate(rsbwt_t *h, const uint64_t *rows, size_t n, uint32_t max_steps, uint64_t *read_row, uint64_t *ordinal,
+                 uint32_t *offset);
+int rsbwt_locate_dev(rsbwt_t *h, const void *d_rows, size_t n, uint32_t max_steps, void *d_read_row, void *d_ordinal,
+                     void *d_offset, void *stream);
+int rsbwt_set_locate(rsbwt_set_t *s, const uint32_t *shard_of, const uint64_t *rows, size_t n, uint32_t max_steps,
+                     uint64_t *read_row, uint64_t *ordinal, uint32_t *offset);
+int rsbwt_set_locate_dev(rsbwt_set_t *s, const void *d_shard, const void *d_rows, size_t n, uint32_t max_steps,
+                         void *d_read_row, void *d_ordinal, void *d_offset, void *stream);
+/* The matches of queries of lengths of their own as positions instead of strings: rsbwt_set_query_var_capped's first[] /
+ * read_shard[] / matches[] / limit rules and row order (query by query, shard ascending, SA row ascending); rows[t] is
+ * the SA row of match t in shard read_shard[t], read_row / ordinal / offset[t] its location.  Every array of `cap`
+ * entries may be NULL.  cap = 0 sizes the buffers (RSBWT_ERANGE, *nrows set).  On a one-device set search, expansion
+ * and walks stay on the device; a set over several devices expands on the host.  Same answers either way. */
+int rsbwt_set_locate_var_capped(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t max_rows,
+                                uint32_t max_steps, uint64_t *first, uint32_t *read_shard, uint64_t *rows,
+                                uint64_t *read_row, uint64_t *ordinal, uint32_t *offset, size_t cap, size_t *nrows,
+                                uint64_t *matches);
+/* calling thread's last host-buffer locate call: {rows that ended on '$', LF steps} */
+void rsbwt_locate_last_work(uint64_t *work2);
 /* KmerMatch (src/service/service.cpp:466-502, find_kmer_reads; KmerTask::run :871-960) over every shard: query q =
  * text[off[q] .. off[q+1]) is tiled as get_tiles(q, k, skip) does (:232-246), every all-ACGT tile goes through
  * find_reads with no suffix filter (:714-797, min / max_read_length: 0 = 73 / 100), and the reads are folded into a

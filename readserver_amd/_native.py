@@ -176,6 +176,13 @@ SIGNATURES = {
                                              C.POINTER(C.c_size_t), _vp]),
     "rsbwt_set_interval_rows_dev": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "rsbwt_set_query_last_work": (None, [_u64p]),
+    "rsbwt_locate": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp, _vp]),
+    "rsbwt_locate_dev": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "rsbwt_set_locate": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp, _vp]),
+    "rsbwt_set_locate_dev": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "rsbwt_set_locate_var_capped": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
+                                              C.POINTER(C.c_size_t), _vp]),
+    "rsbwt_locate_last_work": (None, [_u64p]),
     "rsbwt_service_set_max_match_reads": (C.c_int, [_vp, C.c_uint64]),
     "rsbwt_service_capped_requests": (C.c_uint64, [_vp]),
     "rsbwt_set_kmer_reads": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32,

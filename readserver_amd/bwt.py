@@ -177,6 +177,15 @@ class GpuBWT:
     def hbm_bytes(self):
         return lib().rsbwt_hbm_bytes(self._h)
 
+    def locate(self, rows, max_steps=0):
+        """(read_row, ordinal, offset) of SA rows (rsbwt_locate): the row of the read's full suffix, the read's number
+        among the shard's reads (Occ('$', read_row) - 1) and where the row's suffix starts in the read.  A row past the
+        index, or one whose walk needs more than max_steps LF steps (0 = 2^20), gets 2^64-1 / 2^64-1 / 2^32-1."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).ravel()
+        rr, od, of = np.empty(r.size, np.uint64), np.empty(r.size, np.uint64), np.empty(r.size, np.uint32)
+        check(lib().rsbwt_locate(self.handle, _ptr(r), r.size, max_steps, _ptr(rr), _ptr(od), _ptr(of)))
+        return rr, od, of
+
     @property
     def exactmatch_by_search(self):
         """True: query_exactmatch on this shard answers by backward search from the terminator rows
@@ -556,6 +565,46 @@ class ShardSet:
         if (ln == 0xFFFFFFFF).any():
             raise RsbwtError(-1, "a read does not fit the stride / a row is out of range")
         return [out[i, :ln[i]].tobytes().decode() for i in range(r.size)], pl
+
+    def locate(self, shard_of, rows, max_steps=0):
+        """(read_row, ordinal, offset) of (shard, row) pairs (rsbwt_set_locate; GpuBWT.locate's answers per shard)"""
+        sh = np.ascontiguousarray(shard_of, dtype=np.uint32).ravel()
+        r = np.ascontiguousarray(rows, dtype=np.uint64).ravel()
+        if sh.size != r.size:
+            raise ValueError("shard_of and rows differ in length")
+        rr, od, of = np.empty(r.size, np.uint64), np.empty(r.size, np.uint64), np.empty(r.size, np.uint32)
+        check(lib().rsbwt_set_locate(self._s, _ptr(sh), _ptr(r), r.size, max_steps, _ptr(rr), _ptr(od), _ptr(of)))
+        return rr, od, of
+
+    def locate_queries(self, queries, max_rows=0, max_steps=0):
+        """The matches of every query as positions (rsbwt_set_locate_var_capped): a dict of first (Q + 1), matches (Q),
+        and per match shard, row, read_row, ordinal, offset -- query q's matches at first[q]:first[q+1], shard ascending,
+        SA row ascending; none for a query whose rows over all shards exceed max_rows (0 = no limit)."""
+        text, off = self._var_text(queries)
+        Q = len(queries)
+        first = np.zeros(Q + 1, np.uint64)
+        matches = np.zeros(max(Q, 1), np.uint64)
+        n = C.c_size_t()
+        rc = lib().rsbwt_set_locate_var_capped(self._s, _ptr(text), _ptr(off), Q, max_rows, max_steps, _ptr(first), None, None, None, None,
+                                               None, 0, C.byref(n), _ptr(matches))
+        if rc not in (0, -7):
+            check(rc)
+        total = n.value
+        m = max(total, 1)
+        sh, of = np.zeros(m, np.uint32), np.zeros(m, np.uint32)
+        rows, rr, od = np.zeros(m, np.uint64), np.zeros(m, np.uint64), np.zeros(m, np.uint64)
+        if total:
+            check(lib().rsbwt_set_locate_var_capped(self._s, _ptr(text), _ptr(off), Q, max_rows, max_steps, _ptr(first), _ptr(sh), _ptr(rows),
+                                                    _ptr(rr), _ptr(od), _ptr(of), total, C.byref(n), _ptr(matches)))
+        return dict(first=first, matches=matches[:Q].copy(), shard=sh[:total], row=rows[:total], read_row=rr[:total], ordinal=od[:total],
+                    offset=of[:total])
+
+    @staticmethod
+    def locate_last_work():
+        """{located, lf_steps} of this thread's last locate call: rows that ended on '$', LF steps of all walks"""
+        w = np.zeros(2, np.uint64)
+        lib().rsbwt_locate_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return dict(located=int(w[0]), lf_steps=int(w[1]))
 
     def query(self, kmers, read_stride=256):
         """query() in every shard (query.cpp:87-100): per k-mer a list of (shard, read), shard 0's reads first."""

@@ -111,6 +111,13 @@ int read_copies_host_views(search_meter &m, ctx_pool &pool, const shard_view *d_
                            const char *kmers, size_t Q, uint32_t k, size_t stride, uint64_t *copies, uint64_t *ending);
 int read_copies_host_views_var(search_meter &m, ctx_pool &pool, const shard_view *d_views, uint32_t nshards, int num_cus,
                                const char *text, const uint64_t *off, size_t Q, uint64_t *copies, uint64_t *ending);
+// locate.hip: rows in host memory located through c's staging buffer (shard_of null: the one shard of d_views), the
+// answers into the caller's arrays (each optional), work2[0..1] += {rows ended on '$', LF steps}; and what
+// rsbwt_locate_last_work reports for the calling thread
+int locate_host_views(scratch_cache &scratch, call_ctx &c, const shard_view *d_views, uint32_t nshards, int num_cus, const uint32_t *shard_of,
+                      const uint64_t *rows, size_t n, uint32_t max_steps, uint64_t *read_row, uint64_t *ordinal, uint32_t *offset,
+                      uint64_t *work2);
+void locate_set_last_work(uint64_t walked, uint64_t steps);
 // 1-mismatch hit list of one shard from variants expanded once for the whole batch (sets.hip: every shard of a set
 // searches the same variants)
 size_t variants_bytes(size_t m, uint32_t k);

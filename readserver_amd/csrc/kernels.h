@@ -193,6 +193,13 @@ hipError_t launch_extract_wave(scratch_cache &scratch, const shard_view *d_shard
 hipError_t launch_extract_ragged(scratch_cache &scratch, const shard_view *d_shards, uint32_t nshards, const void *d_rows, size_t total,
                                  const void *d_seg, size_t seg_stride, void *d_out, uint32_t stride, void *d_plen, void *d_len, int num_cus,
                                  hipStream_t stream);
+// locate.hip: the LF walk of n (shard, row) entries to the row of their read's full suffix: d_shard_of u32[n] (nullptr:
+// one shard, every entry a row of it), d_rows u64[n] in any order; d_read_row / d_ordinal u64[n], d_offset u32[n], each
+// optional; max_steps 0 = 2^20.  d_work2 (optional, zeroed by the caller): [0] += rows that ended on '$', [1] += LF steps.
+// One launch walks all the shards, a wave one shard at a time.
+hipError_t launch_locate(scratch_cache &scratch, const shard_view *d_shards, uint32_t nshards, const void *d_shard_of, const void *d_rows,
+                         size_t n, uint32_t max_steps, void *d_read_row, void *d_ordinal, void *d_offset, unsigned long long *d_work2,
+                         int num_cus, hipStream_t stream);
 // interval_rows.hip: {lower, upper} pairs [S][Q] -> the rows of the batch, with a limit on the rows of one query.
 //   launch_interval_totals: d_matches u64[Q] (every query's rows over the S shards), d_first u64[Q + 1] (exclusive scan of the
 //     totals of the queries at or under max_rows; 0 = no limit), *d_over (u64) = queries over it; d_kept: u64[Q + 1] scratch

@@ -1389,6 +1389,255 @@ int rsbwt_set_interval_rows_dev(rsbwt_set_t *s, const void *d_pairs, size_t Q, u
     });
 }
 
+// ---- locate (locate.hip): rows of several shards, and the matches of queries as positions instead of strings ----
+// entry i = SA row rows[i] of shard shard_of[i]; one launch per device group walks all of that group's shards
+static int set_locate_body(rsbwt_set_t *s, const uint32_t *shard_of, const uint64_t *rows, size_t n, uint32_t max_steps, uint64_t *read_row,
+                           uint64_t *ordinal, uint32_t *offset, uint64_t *work2) {
+    const size_t S = s->shards.size();
+    for (size_t i = 0; i < n; ++i)
+        if (shard_of[i] >= S) return fail(RSBWT_EINVAL, "row %zu names shard %u of %zu", i, shard_of[i], S);
+    std::atomic<uint64_t> walked{0}, steps{0};
+    const int rc = for_each_group(s, [&](size_t gi) -> int {
+        dev_group *g = s->groups[gi];
+        const bool whole = s->groups.size() == 1;  // (the group's shard numbers are the set's)
+        std::vector<size_t> pos;
+        std::vector<uint32_t> lsh;
+        std::vector<uint64_t> lrows;
+        if (!whole) {
+            std::vector<uint32_t> local(S, ~0u);
+            for (size_t j = 0; j < g->idx.size(); ++j) local[g->idx[j]] = (uint32_t)j;
+            for (size_t i = 0; i < n; ++i)
+                if (local[shard_of[i]] != ~0u) {
+                    pos.push_back(i);
+                    lsh.push_back(local[shard_of[i]]);
+                    lrows.push_back(rows[i]);
+                }
+            if (pos.empty()) return RSBWT_OK;
+        }
+        int rg = use_device(g->device);
+        if (rg) return rg;
+        call_ctx *c = g->pool.acquire();
+        if (!c) return fail(RSBWT_EHIP, "cannot create a HIP stream");
+        struct release_t {
+            dev_group *g;
+            call_ctx *c;
+            ~release_t() { g->pool.release(c); }
+        } release{g, c};
+        uint64_t wk[2] = {0, 0};
+        if (whole) {
+            rg = locate_host_views(g->scratch, *c, g->d_views, (uint32_t)g->idx.size(), g->num_cus, shard_of, rows, n, max_steps, read_row, ordinal,
+                                   offset, wk);
+        } else {
+            const size_t m = pos.size();
+            std::vector<uint64_t> rr(read_row ? m : 0), od(ordinal ? m : 0);
+            std::vector<uint32_t> of(offset ? m : 0);
+            rg = locate_host_views(g->scratch, *c, g->d_views, (uint32_t)g->idx.size(), g->num_cus, lsh.data(), lrows.data(), m, max_steps,
+                                   read_row ? rr.data() : nullptr, ordinal ? od.data() : nullptr, offset ? of.data() : nullptr, wk);
+            if (rg == RSBWT_OK)
+                for (size_t t = 0; t < m; ++t) {
+                    if (read_row) read_row[pos[t]] = rr[t];
+                    if (ordinal) ordinal[pos[t]] = od[t];
+                    if (offset) offset[pos[t]] = of[t];
+                }
+        }
+        walked += wk[0];
+        steps += wk[1];
+        return rg;
+    });
+    if (work2) {
+        work2[0] += walked.load();
+        work2[1] += steps.load();
+    }
+    return rc;
+}
+
+int rsbwt_set_locate(rsbwt_set_t *s, const uint32_t *shard_of, const uint64_t *rows, size_t n, uint32_t max_steps, uint64_t *read_row,
+                     uint64_t *ordinal, uint32_t *offset) {
+    return guarded("rsbwt_set_locate", [&]() -> int {
+        locate_set_last_work(0, 0);
+        if (!s) return fail(RSBWT_EINVAL, "null set");
+        if (!read_row && !ordinal && !offset) return fail(RSBWT_EINVAL, "null argument: no output array");
+        if (n == 0) return RSBWT_OK;
+        if (!shard_of || !rows) return fail(RSBWT_EINVAL, "null argument");
+        uint64_t wk[2] = {0, 0};
+        const int rc = set_locate_body(s, shard_of, rows, n, max_steps, read_row, ordinal, offset, wk);
+        locate_set_last_work(wk[0], wk[1]);
+        return rc;
+    });
+}
+
+// one-device set, the caller's buffers and stream, nothing synchronised
+int rsbwt_set_locate_dev(rsbwt_set_t *s, const void *d_shard, const void *d_rows, size_t n, uint32_t max_steps, void *d_read_row,
+                         void *d_ordinal, void *d_offset, void *stream) {
+    return guarded("rsbwt_set_locate_dev", [&]() -> int {
+        dev_group *g = nullptr;
+        int rc = one_device_group(s, &g);
+        if (rc) return rc;
+        if (!d_read_row && !d_ordinal && !d_offset) return fail(RSBWT_EINVAL, "null argument: no output array");
+        if (n == 0) return RSBWT_OK;
+        if (!d_shard || !d_rows) return fail(RSBWT_EINVAL, "null argument");
+        const hipError_t e = launch_locate(g->scratch, g->d_views, (uint32_t)g->idx.size(), d_shard, d_rows, n, max_steps, d_read_row, d_ordinal,
+                                           d_offset, nullptr, g->num_cus, (hipStream_t)stream);
+        return e == hipSuccess ? RSBWT_OK : fail_hip(e, "locate kernel launch");
+    });
+}
+
+namespace {
+// One device group holding every shard: search, totals / limit / first[], the rows as (shard, row) and their walks all
+// stay in HBM; first[] and matches[] cross to the host before the rows are made (first[Q] sizes them), the answers after.
+int locate_capped_device(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t max_rows, uint32_t max_steps,
+                         uint64_t *first, uint32_t *read_shard, uint64_t *rows, uint64_t *read_row, uint64_t *ordinal, uint32_t *offset,
+                         size_t cap, size_t *nrows, uint64_t *matches, uint64_t *work2) {
+    dev_group *g = s->groups[0];
+    const uint32_t S = (uint32_t)g->idx.size();
+    int rc = use_device(g->device);
+    if (rc) return rc;
+    call_ctx *c = g->pool.acquire();
+    if (!c) return fail(RSBWT_EHIP, "cannot create a HIP stream");
+    hipStream_t st = c->st[0];
+    scratch_cache::lease la, lb;
+    struct release_t {
+        dev_group *g;
+        call_ctx *c;
+        scratch_cache::lease *la, *lb;
+        ~release_t() {
+            (void)hipStreamSynchronize(c->st[0]);
+            g->scratch.give(*la, c->st[0]);
+            g->scratch.give(*lb, c->st[0]);
+            g->pool.release(c);
+        }
+    } release{g, c, &la, &lb};
+    const size_t cells = (size_t)S * Q;
+    const size_t a_pairs = al256(cells * 16), a_q = al256((Q + 1) * 8), a_tmp = interval_rows_scan_bytes(Q + 1) + 256;
+    hipError_t e = g->scratch.take(a_pairs + 3 * a_q + 256 + a_tmp, st, &la);
+    if (e != hipSuccess) return fail_hip(e, "scratch for a capped locate");
+    uint8_t *d_pairs = (uint8_t *)la.p, *d_matches = d_pairs + a_pairs, *d_kept = d_matches + a_q, *d_first = d_kept + a_q,
+            *d_over = d_first + a_q, *d_tmp = d_over + 256;
+    // ---- the search (query_capped_device's: every slice's pairs land in the batch's [S][Q] block)
+    auto a_rec = [&](size_t mq) { return al256((size_t)S * mq * 16); };
+    rc = for_each_var_slice(
+        *c, st, text, off, Q, [&](size_t mq) { return a_rec(mq) + (mq == Q ? 0 : al256((size_t)S * mq * 16)); },
+        [&](size_t q0, size_t mq) -> int {
+            HIP_OK(hipMemset2DAsync(d_pairs + q0 * 16, Q * 16, 0xFF, mq * 16, S, st));
+            return RSBWT_OK;
+        },
+        [&](const var_slice &sl) -> int {
+            const size_t q0 = sl.q0, mq = sl.mq;
+            uint8_t *d_rec = sl.d_extra, *d_res = mq == Q ? d_pairs : d_rec + a_rec(mq);
+            const hipError_t ei = launch_search_init_var(g->d_views, S, sl.d_pk, sl.d_ok, sl.d_len, mq, sl.wpq, d_rec, st);
+            if (ei != hipSuccess) return fail_hip(ei, "start-record kernel launch");
+            search_extra ex;
+            ex.narrow = group_is_narrow(s, g, sl.k);
+            ex.d_init = d_rec;
+            ex.pairs = true;
+            const int rs = search_launch(*g, g->d_views, S, g->num_cus, sl.d_pk, sl.d_ok, mq, sl.k, d_res, nullptr, false, st, &ex);
+            if (rs) return rs;
+            if (mq != Q) HIP_OK(hipMemcpy2DAsync(d_pairs + q0 * 16, Q * 16, d_res, mq * 16, mq * 16, S, hipMemcpyDeviceToDevice, st));
+            return RSBWT_OK;
+        });
+    if (rc) return rc;
+    e = launch_interval_totals(g->d_views, S, d_pairs, Q, max_rows, d_matches, d_kept, d_first, d_over, d_tmp, a_tmp - 256, st);
+    if (e != hipSuccess) return fail_hip(e, "interval-rows kernels");
+    HIP_OK(hipMemcpyAsync(first, d_first, (Q + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (matches) HIP_OK(hipMemcpyAsync(matches, d_matches, Q * 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    const uint64_t total = first[Q];
+    *nrows = (size_t)total;
+    if (total > cap) return fail(RSBWT_ERANGE, "%llu rows over the set, room for %zu", (unsigned long long)total, cap);
+    if (total == 0) return RSBWT_OK;
+    const size_t a8 = al256(total * 8), a4 = al256(total * 4);
+    e = g->scratch.take(3 * a8 + 2 * a4 + 256, st, &lb);
+    if (e != hipSuccess) return fail(RSBWT_ENOMEM, "%llu rows do not fit the device's free memory: %s", (unsigned long long)total, hipGetErrorString(e));
+    uint8_t *d_rows = (uint8_t *)lb.p, *d_rr = d_rows + a8, *d_od = d_rr + a8, *d_of = d_od + a8, *d_sh = d_of + a4, *d_wk = d_sh + a4;
+    e = launch_interval_fill(g->d_views, S, d_pairs, Q, d_first, (size_t)total, d_sh, d_rows, nullptr, nullptr, nullptr, st);
+    if (e != hipSuccess) return fail_hip(e, "row expansion");
+    const bool walk = read_row || ordinal || offset;
+    unsigned long long wk[2] = {0, 0};
+    if (walk) {
+        HIP_OK(hipMemsetAsync(d_wk, 0, 16, st));
+        e = launch_locate(g->scratch, g->d_views, S, d_sh, d_rows, (size_t)total, max_steps, read_row ? d_rr : nullptr, ordinal ? d_od : nullptr,
+                          offset ? d_of : nullptr, (unsigned long long *)d_wk, g->num_cus, st);
+        if (e != hipSuccess) return fail_hip(e, "locate kernel launch");
+        HIP_OK(hipMemcpyAsync(wk, d_wk, 16, hipMemcpyDeviceToHost, st));
+    }
+    if (read_shard) HIP_OK(hipMemcpyAsync(read_shard, d_sh, total * 4, hipMemcpyDeviceToHost, st));
+    if (rows) HIP_OK(hipMemcpyAsync(rows, d_rows, total * 8, hipMemcpyDeviceToHost, st));
+    if (read_row) HIP_OK(hipMemcpyAsync(read_row, d_rr, total * 8, hipMemcpyDeviceToHost, st));
+    if (ordinal) HIP_OK(hipMemcpyAsync(ordinal, d_od, total * 8, hipMemcpyDeviceToHost, st));
+    if (offset) HIP_OK(hipMemcpyAsync(offset, d_of, total * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (read_shard)
+        for (size_t t = 0; t < total; ++t) read_shard[t] = (uint32_t)g->idx[read_shard[t]];
+    work2[0] += wk[0];
+    work2[1] += wk[1];
+    return RSBWT_OK;
+}
+}  // namespace
+
+int rsbwt_set_locate_var_capped(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t max_rows, uint32_t max_steps,
+                                uint64_t *first, uint32_t *read_shard, uint64_t *rows, uint64_t *read_row, uint64_t *ordinal,
+                                uint32_t *offset, size_t cap, size_t *nrows, uint64_t *matches) {
+    return guarded("rsbwt_set_locate_var_capped", [&]() -> int {
+        locate_set_last_work(0, 0);
+        if (!s || !nrows || (!first && Q)) return fail(RSBWT_EINVAL, "null argument");
+        *nrows = 0;
+        if (Q == 0) return RSBWT_OK;
+        if (!off || (!text && off[Q] != off[0])) return fail(RSBWT_EINVAL, "null argument");
+        for (rsbwt_t *h : s->shards)
+            if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
+        const size_t S = s->shards.size();
+        uint64_t wk[2] = {0, 0};
+        if (s->groups.size() == 1 && S <= 1024) {
+            const int rc = locate_capped_device(s, text, off, Q, max_rows, max_steps, first, read_shard, rows, read_row, ordinal, offset, cap,
+                                                nrows, matches, wk);
+            locate_set_last_work(wk[0], wk[1]);
+            return rc;
+        }
+        // several device groups: the intervals come to the host, the limit and the expansion run there
+        // (query_capped_body's rules), and the rows go the way rsbwt_set_locate's go
+        std::vector<uint64_t> lo(S * Q), up(S * Q);
+        int rc = rsbwt_set_find_intervals_var_body(s, text, off, Q, lo.data(), up.data(), false);
+        if (rc) return rc;
+        auto width = [&](size_t i, size_t q) -> uint64_t {
+            const uint64_t l = lo[i * Q + q], u = up[i * Q + q];
+            return (l <= u && u < s->shards[i]->view.n) ? u - l + 1 : 0;
+        };
+        size_t total = 0;
+        for (size_t q = 0; q < Q; ++q) {
+            uint64_t m = 0;
+            for (size_t i = 0; i < S; ++i) m += width(i, q);
+            if (matches) matches[q] = m;
+            first[q] = total;
+            if (max_rows && m > max_rows) {
+                for (size_t i = 0; i < S; ++i) { lo[i * Q + q] = 1; up[i * Q + q] = 0; }
+            } else {
+                total += (size_t)m;
+            }
+        }
+        first[Q] = total;
+        *nrows = total;
+        if (total > cap) return fail(RSBWT_ERANGE, "%zu rows over the set, room for %zu", total, cap);
+        if (total == 0) return RSBWT_OK;
+        std::vector<uint32_t> sh(total);
+        std::vector<uint64_t> rw(total);
+        size_t at = 0;
+        for (size_t q = 0; q < Q; ++q)
+            for (size_t i = 0; i < S; ++i) {
+                const uint64_t w = width(i, q), l = lo[i * Q + q];
+                for (uint64_t r = 0; r < w; ++r, ++at) {
+                    sh[at] = (uint32_t)i;
+                    rw[at] = l + r;
+                }
+            }
+        if (read_shard) memcpy(read_shard, sh.data(), total * sizeof(uint32_t));
+        if (rows) memcpy(rows, rw.data(), total * sizeof(uint64_t));
+        if (!read_row && !ordinal && !offset) return RSBWT_OK;
+        rc = set_locate_body(s, sh.data(), rw.data(), total, max_steps, read_row, ordinal, offset, wk);
+        locate_set_last_work(wk[0], wk[1]);
+        return rc;
+    });
+}
+
 static size_t hits_1mm_scratch_one(const rsbwt_set_t *s, size_t m, uint32_t k) {
     size_t need = 0;
     for (rsbwt_t *h : s->shards) need = std::max(need, rsbwt_hits_1mm_scratch_bytes(h, m, k));

@@ -29,7 +29,7 @@ namespace rsb {
 
 namespace {
 
-// rows of shard i for a query: its interval, if it is one of rows of that shard (sets.hip, set_query_rows' rule): the empty
+// rows of shard i for a query: its interval, if it is one of rows of that shard (sets.hip, intervals_to_rows_host's rule): the empty
 // (1, 0), the reference's (0, 2^64 - 1) corner and upper >= n all give 0
 __device__ __forceinline__ uint64_t pair_width(const ulonglong2 p, uint64_t n) {
     return (p.x <= p.y && p.y < n) ? p.y - p.x + 1ull : 0ull;

@@ -260,6 +260,62 @@ int one_device_group(rsbwt_set_t *s, dev_group **g) {
     return use_device((*g)->device);
 }
 
+// A call context on g's device for the duration of one host-buffer call; rc says whether there is one.  The capped
+// calls also lease their scratch through it (la, lb): their launches may still run when such a call leaves early, so
+// the destructor waits for the stream before the leases go back.  A call without leases waits for nothing here.
+struct group_call {
+    dev_group *const g;
+    const bool leases;
+    int rc;
+    call_ctx *c = nullptr;
+    hipStream_t st = nullptr;
+    scratch_cache::lease la, lb;
+    explicit group_call(dev_group *grp, bool with_leases = false) : g(grp), leases(with_leases), rc(use_device(grp->device)) {
+        if (rc == RSBWT_OK && !(c = g->pool.acquire())) rc = fail(RSBWT_EHIP, "cannot create a HIP stream");
+        if (c) st = c->st[0];
+    }
+    group_call(const group_call &) = delete;
+    ~group_call() {
+        if (!c) return;
+        if (leases) {
+            (void)hipStreamSynchronize(st);
+            g->scratch.give(la, st);
+            g->scratch.give(lb, st);
+        }
+        g->pool.release(c);
+    }
+};
+
+// Group g's share of the caller's (shard_of, rows): the shards as the group numbers them, their rows, and where each
+// entry stands in the caller's arrays (ascending)
+struct group_share {
+    std::vector<uint32_t> shard;
+    std::vector<uint64_t> rows;
+    std::vector<size_t> pos;
+};
+group_share share_of_group(const rsbwt_set_t *s, const dev_group *g, const uint32_t *shard_of, const uint64_t *rows, size_t n) {
+    std::vector<uint32_t> local(s->shards.size(), ~0u);
+    for (size_t j = 0; j < g->idx.size(); ++j) local[g->idx[j]] = (uint32_t)j;
+    group_share sh;
+    for (size_t i = 0; i < n; ++i)
+        if (local[shard_of[i]] != ~0u) {
+            sh.shard.push_back(local[shard_of[i]]);
+            sh.rows.push_back(rows[i]);
+            sh.pos.push_back(i);
+        }
+    return sh;
+}
+
+// The copy back of one extracted read: the kept bytes of cell src of a launch's answers (ho [.][stride], hl, hp) to slot
+// dst of the caller's arrays.  A read that did not fit its stride (length 0xFFFFFFFF) brings no bytes and keeps its mark.
+void scatter_read(const char *ho, const uint32_t *hl, const uint32_t *hp, size_t src, char *out, uint32_t stride, uint32_t *len,
+                  uint32_t *prefix_len, size_t dst) {
+    const uint32_t keep = hl[src] == 0xFFFFFFFFu ? 0u : hl[src];
+    if (keep) memcpy(out + dst * (size_t)stride, ho + src * (size_t)stride, keep);
+    if (len) len[dst] = hl[src];
+    if (prefix_len) prefix_len[dst] = hp[src];
+}
+
 }  // namespace
 
 extern "C" {
@@ -1020,46 +1076,36 @@ static int rsbwt_set_extract_body(rsbwt_set_t *s, const uint32_t *shard_of, cons
     if (n == 0) return RSBWT_OK;
     if (!shard_of || !rows || !out) return fail(RSBWT_EINVAL, "null argument");
     const size_t S = s->shards.size();
-    std::vector<std::vector<size_t>> where(S);
-    for (size_t i = 0; i < n; ++i) {
+    for (size_t i = 0; i < n; ++i)
         if (shard_of[i] >= S) return fail(RSBWT_EINVAL, "row %zu names shard %u of %zu", i, shard_of[i], S);
-        where[shard_of[i]].push_back(i);
-    }
     static const bool turns_only = getenv("RSBWT_SET_EXTRACT_TURNS") != nullptr;  // A/B knob (tools/README.md): a launch sequence per shard
     return for_each_group(s, [&](size_t gi) -> int {
         dev_group *g = s->groups[gi];
+        const group_share sh = share_of_group(s, g, shard_of, rows, n);
+        const size_t Sg = g->idx.size(), ng = sh.pos.size();
+        if (ng == 0) return RSBWT_OK;
+        std::vector<std::vector<size_t>> where(Sg);  // per shard of the group: its entries of the share, in the caller's order
+        for (size_t t = 0; t < ng; ++t) where[sh.shard[t]].push_back(t);
+        size_t nmax = 0;
+        for (const std::vector<size_t> &w : where) nmax = std::max(nmax, w.size());
         // The rows of all the group's shards in ONE launch sequence (the fused extraction bench.py --mode extract times):
         // [S_g][nmax] rows, a shard with fewer padded with rows past any index (they end at once).  What a window of the
         // service loop asks for -- a few hundred rows spread over the partitions -- then costs one walk's latency, not
         // one per partition (round 5; until then a launch sequence and a copy back per shard).
-        const size_t Sg = g->idx.size();
-        size_t nmax = 0, ng = 0;
-        for (size_t si : g->idx) {
-            nmax = std::max(nmax, where[si].size());
-            ng += where[si].size();
-        }
-        if (ng == 0) return RSBWT_OK;
         if (!turns_only && Sg > 1 && nmax < (1ull << 31) && Sg * nmax <= 4 * ng + 4096) {
-            int rc = use_device(g->device);
-            if (rc) return rc;
-            call_ctx *c = g->pool.acquire();
-            if (!c) return fail(RSBWT_EHIP, "cannot create a HIP stream");
-            struct release_t {
-                dev_group *g;
-                call_ctx *c;
-                ~release_t() { g->pool.release(c); }
-            } release{g, c};
-            hipStream_t st = c->st[0];
-            if ((rc = ensure_group_xviews(s, g, st)) != RSBWT_OK) return rc;
+            group_call gc(g);
+            if (gc.rc) return gc.rc;
+            call_ctx *c = gc.c;
+            hipStream_t st = gc.st;
+            int rc = ensure_group_xviews(s, g, st);
+            if (rc != RSBWT_OK) return rc;
             const size_t cells = Sg * nmax;
-            const size_t a_rows = (cells * 8 + 255) & ~(size_t)255, a_out = (cells * (size_t)stride + 255) & ~(size_t)255, a_u32 = (cells * 4 + 255) & ~(size_t)255;
+            const size_t a_rows = al256(cells * 8), a_out = al256(cells * (size_t)stride), a_u32 = al256(cells * 4);
             if ((rc = c->stage(a_rows + a_out + 2 * a_u32)) != RSBWT_OK) return rc;
             uint8_t *d_rows = (uint8_t *)c->d_stage, *d_out = d_rows + a_rows, *d_len = d_out + a_out, *d_pl = d_len + a_u32;
             std::vector<uint64_t> hr(cells, ~0ull);
-            for (size_t j = 0; j < Sg; ++j) {
-                const std::vector<size_t> &w = where[g->idx[j]];
-                for (size_t t = 0; t < w.size(); ++t) hr[j * nmax + t] = rows[w[t]];
-            }
+            for (size_t j = 0; j < Sg; ++j)
+                for (size_t t = 0; t < where[j].size(); ++t) hr[j * nmax + t] = sh.rows[where[j][t]];
             HIP_OK(hipMemcpyAsync(d_rows, hr.data(), cells * 8, hipMemcpyHostToDevice, st));
             const hipError_t e = launch_extract_wave(g->scratch, g->d_xviews, (uint32_t)Sg, d_rows, nmax, d_out, stride, d_pl, d_len, g->num_cus, st, nullptr);
             if (e != hipSuccess) return fail_hip(e, "extract kernel launch");
@@ -1069,34 +1115,22 @@ static int rsbwt_set_extract_body(rsbwt_set_t *s, const uint32_t *shard_of, cons
             HIP_OK(hipMemcpyAsync(hl.data(), d_len, cells * 4, hipMemcpyDeviceToHost, st));
             HIP_OK(hipMemcpyAsync(hp.data(), d_pl, cells * 4, hipMemcpyDeviceToHost, st));
             HIP_OK(hipStreamSynchronize(st));
-            for (size_t j = 0; j < Sg; ++j) {
-                const std::vector<size_t> &w = where[g->idx[j]];
-                for (size_t t = 0; t < w.size(); ++t) {
-                    const size_t cell = j * nmax + t;
-                    const uint32_t keep = hl[cell] == 0xFFFFFFFFu ? 0u : hl[cell];
-                    if (keep) memcpy(out + w[t] * (size_t)stride, ho.data() + cell * (size_t)stride, keep);
-                    if (len) len[w[t]] = hl[cell];
-                    if (prefix_len) prefix_len[w[t]] = hp[cell];
-                }
-            }
+            for (size_t j = 0; j < Sg; ++j)
+                for (size_t t = 0; t < where[j].size(); ++t)
+                    scatter_read(ho.data(), hl.data(), hp.data(), j * nmax + t, out, stride, len, prefix_len, sh.pos[where[j][t]]);
             return RSBWT_OK;
         }
-        for (size_t si : g->idx) {
-            const std::vector<size_t> &w = where[si];
+        for (size_t j = 0; j < Sg; ++j) {
+            const std::vector<size_t> &w = where[j];
             if (w.empty()) continue;
             const size_t m = w.size();
             std::vector<uint64_t> r(m);
             std::vector<char> o(m * (size_t)stride);
             std::vector<uint32_t> ln(m), pl(m);
-            for (size_t j = 0; j < m; ++j) r[j] = rows[w[j]];
-            const int rc = rsbwt_extract(s->shards[si], r.data(), m, o.data(), stride, ln.data(), pl.data());
+            for (size_t t = 0; t < m; ++t) r[t] = sh.rows[w[t]];
+            const int rc = rsbwt_extract(s->shards[g->idx[j]], r.data(), m, o.data(), stride, ln.data(), pl.data());
             if (rc) return rc;
-            for (size_t j = 0; j < m; ++j) {
-                const uint32_t keep = ln[j] == 0xFFFFFFFFu ? 0u : ln[j];
-                if (keep) memcpy(out + w[j] * (size_t)stride, o.data() + j * (size_t)stride, keep);
-                if (len) len[w[j]] = ln[j];
-                if (prefix_len) prefix_len[w[j]] = pl[j];
-            }
+            for (size_t t = 0; t < m; ++t) scatter_read(o.data(), ln.data(), pl.data(), t, out, stride, len, prefix_len, sh.pos[w[t]]);
         }
         return RSBWT_OK;
     });
@@ -1106,38 +1140,61 @@ int rsbwt_set_extract(rsbwt_set_t *s, const uint32_t *shard_of, const uint64_t *
     return guarded("rsbwt_set_extract", [&]() -> int { return rsbwt_set_extract_body(s, shard_of, rows, n, out, stride, len, prefix_len); });
 }
 
-// what rsbwt_set_query makes of the batch's intervals lo / up [S][Q]: first[], and the rows' reads in the caller's order
-static int set_query_rows(rsbwt_set_t *s, size_t Q, const std::vector<uint64_t> &lo, const std::vector<uint64_t> &up, uint64_t *first,
-                          uint32_t *read_shard, char *reads, uint32_t read_stride, uint32_t *read_len, size_t cap_reads, size_t *nreads) {
+// THE host-side rule that turns a batch's intervals lo / up [S][Q] into rows, for every call whose set spans several
+// device groups: shard i brings query q its interval if it is one of rows of that shard (rsbwt_query's rule: capi.hip,
+// interval_rows) -- matches[q] (optional) counts them over the shards; a query with more than max_rows of them
+// (0 = no limit) brings none; first[] is the running total of the rows kept.  With room for them (total <= cap) the rows
+// themselves follow as (shard_of, rows) in the caller's order: query by query, shard ascending, SA row ascending.
+struct expanded_rows {
+    size_t total = 0;
+    uint64_t over = 0;  // queries over the limit
+    std::vector<uint32_t> shard_of;
+    std::vector<uint64_t> rows;
+};
+static expanded_rows intervals_to_rows_host(const rsbwt_set_t *s, size_t Q, const std::vector<uint64_t> &lo, const std::vector<uint64_t> &up,
+                                            uint64_t max_rows, size_t cap, uint64_t *first, uint64_t *matches) {
     const size_t S = s->shards.size();
-    // rows of shard i for k-mer q: its interval, if it is one of rows of that shard (rsbwt_query's rule: capi.hip, interval_rows)
     auto width = [&](size_t i, size_t q) -> uint64_t {
         const uint64_t l = lo[i * Q + q], u = up[i * Q + q];
         return (l <= u && u < s->shards[i]->view.n) ? u - l + 1 : 0;
     };
-    size_t total = 0;
+    expanded_rows hr;
     for (size_t q = 0; q < Q; ++q) {
-        first[q] = total;
-        for (size_t i = 0; i < S; ++i) total += (size_t)width(i, q);
+        uint64_t m = 0;
+        for (size_t i = 0; i < S; ++i) m += width(i, q);
+        if (matches) matches[q] = m;
+        first[q] = hr.total;
+        if (max_rows && m > max_rows) ++hr.over;
+        else hr.total += (size_t)m;
     }
-    first[Q] = total;
-    *nreads = total;
-    if (total > cap_reads) return fail(RSBWT_ERANGE, "%zu reads over the set, room for %zu", total, cap_reads);
-    if (total == 0) return RSBWT_OK;
-    if (!reads || !read_len) return fail(RSBWT_EINVAL, "null argument");
-    std::vector<uint32_t> shard_of(total);
-    std::vector<uint64_t> rows(total);
-    size_t at = 0;
-    for (size_t q = 0; q < Q; ++q)
-        for (size_t i = 0; i < S; ++i) {
-            const uint64_t w = width(i, q), l = lo[i * Q + q];
-            for (uint64_t r = 0; r < w; ++r, ++at) {
-                shard_of[at] = (uint32_t)i;
-                rows[at] = l + r;
+    first[Q] = hr.total;
+    if (hr.total > cap) return hr;
+    hr.shard_of.reserve(hr.total);
+    hr.rows.reserve(hr.total);
+    for (size_t q = 0; q < Q; ++q) {
+        if (first[q + 1] == first[q]) continue;
+        for (size_t i = 0; i < S; ++i)
+            for (uint64_t r = 0, w = width(i, q); r < w; ++r) {
+                hr.shard_of.push_back((uint32_t)i);
+                hr.rows.push_back(lo[i * Q + q] + r);
             }
-        }
-    if (read_shard) memcpy(read_shard, shard_of.data(), total * sizeof(uint32_t));
-    return rsbwt_set_extract_body(s, shard_of.data(), rows.data(), total, reads, read_stride, read_len, nullptr);
+    }
+    return hr;
+}
+
+// what rsbwt_set_query makes of the batch's intervals lo / up [S][Q]: first[] (and matches[], *over: intervals_to_rows_host),
+// and the rows' reads in the caller's order
+static int set_query_rows(rsbwt_set_t *s, size_t Q, const std::vector<uint64_t> &lo, const std::vector<uint64_t> &up, uint64_t max_rows,
+                          uint64_t *first, uint64_t *matches, uint64_t *over, uint32_t *read_shard, char *reads, uint32_t read_stride,
+                          uint32_t *read_len, size_t cap_reads, size_t *nreads) {
+    const expanded_rows hr = intervals_to_rows_host(s, Q, lo, up, max_rows, cap_reads, first, matches);
+    *nreads = hr.total;
+    if (over) *over = hr.over;
+    if (hr.total > cap_reads) return fail(RSBWT_ERANGE, "%zu reads over the set, room for %zu", hr.total, cap_reads);
+    if (hr.total == 0) return RSBWT_OK;
+    if (!reads || !read_len) return fail(RSBWT_EINVAL, "null argument");
+    if (read_shard) memcpy(read_shard, hr.shard_of.data(), hr.total * sizeof(uint32_t));
+    return rsbwt_set_extract_body(s, hr.shard_of.data(), hr.rows.data(), hr.total, reads, read_stride, read_len, nullptr);
 }
 
 // query() of every shard (query.cpp:87-100), k-mer by k-mer: k-mer q's reads are first[q] .. first[q+1],
@@ -1162,7 +1219,7 @@ static int rsbwt_set_query_body(rsbwt_set_t *s, const char *kmers, size_t Q, uin
     std::vector<uint64_t> lo(S * Q), up(S * Q);
     const int rc = rsbwt_set_find_intervals_body(s, kmers, Q, k, stride, lo.data(), up.data());
     if (rc) return rc;
-    return set_query_rows(s, Q, lo, up, first, read_shard, reads, read_stride, read_len, cap_reads, nreads);
+    return set_query_rows(s, Q, lo, up, 0, first, nullptr, nullptr, read_shard, reads, read_stride, read_len, cap_reads, nreads);
 }
 // the same for queries of lengths of their own (rsbwt_set_find_intervals_var): one call answers a window of the service loop
 int rsbwt_set_query_var(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *first, uint32_t *read_shard,
@@ -1176,7 +1233,7 @@ int rsbwt_set_query_var(rsbwt_set_t *s, const char *text, const uint64_t *off, s
         std::vector<uint64_t> lo(S * Q), up(S * Q);
         const int rc = rsbwt_set_find_intervals_var_body(s, text, off, Q, lo.data(), up.data(), false);
         if (rc) return rc;
-        return set_query_rows(s, Q, lo, up, first, read_shard, reads, read_stride, read_len, cap_reads, nreads);
+        return set_query_rows(s, Q, lo, up, 0, first, nullptr, nullptr, read_shard, reads, read_stride, read_len, cap_reads, nreads);
     });
 }
 int rsbwt_set_query(rsbwt_set_t *s, const char *kmers, size_t Q, uint32_t k, size_t stride, uint64_t *first,
@@ -1195,44 +1252,32 @@ thread_local uint64_t capped_last_work[4] = {0, 0, 0, 0};
 
 enum { CAPPED_TAKE_HOST = 1 };  // (not an error: the device path leaves the call to the host path)
 
-// One device group holding every shard: the search leaves its pairs [S][Q] in HBM, the totals / scans / fill make first[],
-// matches[] and the rows there, the ragged walks (extract_lines.hip) take the rows where they are.  What crosses to the
-// host before the walks are launched: first[] and matches[] (the caller's answers; first[Q] sizes the launches) and one
-// counter -- never an interval or a row.
-int query_capped_device(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t max_rows, uint64_t *first,
-                        uint32_t *read_shard, char *reads, uint32_t read_stride, uint32_t *read_len, size_t cap_reads, size_t *nreads,
-                        uint64_t *matches) {
-    dev_group *g = s->groups[0];
+// What the capped calls of a set on ONE device group start with, on gc's stream: the search leaves its pairs [S][Q] in HBM,
+// the totals make matches[], first[] and the count of queries over the limit there; first[], matches[] (optional) and
+// that count cross to the host (the caller's answers; first[Q] sizes what follows) and the stream is waited for once --
+// never an interval or a row.  Everything sits in gc.la, with extra_bytes of the caller's own (d_extra) and scan scratch
+// for scan_items items (d_tmp: interval_rows_scan_bytes).
+struct capped_intervals {
+    uint8_t *d_pairs, *d_matches, *d_first, *d_extra, *d_tmp;
+    size_t tmp_bytes;
+    uint64_t total, over;  // first[Q]; queries over the limit
+};
+int capped_intervals_device(rsbwt_set_t *s, group_call &gc, const char *text, const uint64_t *off, size_t Q, uint64_t max_rows,
+                            size_t extra_bytes, size_t scan_items, const char *scratch_for, uint64_t *first, uint64_t *matches,
+                            capped_intervals *ci) {
+    dev_group *g = gc.g;
+    hipStream_t st = gc.st;
     const uint32_t S = (uint32_t)g->idx.size();
-    int rc = use_device(g->device);
-    if (rc) return rc;
-    call_ctx *c = g->pool.acquire();
-    if (!c) return fail(RSBWT_EHIP, "cannot create a HIP stream");
-    hipStream_t st = c->st[0];
-    scratch_cache::lease la, lb;
-    struct release_t {
-        dev_group *g;
-        call_ctx *c;
-        scratch_cache::lease *la, *lb;
-        ~release_t() {
-            (void)hipStreamSynchronize(c->st[0]);
-            g->scratch.give(*la, c->st[0]);
-            g->scratch.give(*lb, c->st[0]);
-            g->pool.release(c);
-        }
-    } release{g, c, &la, &lb};
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t cells = (size_t)S * Q;
-    const size_t a_pairs = al(cells * 16), a_q = al((Q + 1) * 8), a_cells = al((cells + 1) * 8), a_tmp = interval_rows_scan_bytes(cells + 1) + 256;
-    hipError_t e = g->scratch.take(a_pairs + 3 * a_q + 2 * a_cells + 256 + a_tmp, st, &la);
-    if (e != hipSuccess) return fail_hip(e, "scratch for a capped query");
-    uint8_t *d_pairs = (uint8_t *)la.p, *d_matches = d_pairs + a_pairs, *d_kept = d_matches + a_q, *d_first = d_kept + a_q,
-            *d_cellw = d_first + a_q, *d_cellpos = d_cellw + a_cells, *d_over = d_cellpos + a_cells, *d_tmp = d_over + 256;
+    const size_t a_pairs = al256((size_t)S * Q * 16), a_q = al256((Q + 1) * 8);
+    hipError_t e = g->scratch.take(a_pairs + 3 * a_q + extra_bytes + 256 + interval_rows_scan_bytes(scan_items) + 256, st, &gc.la);
+    if (e != hipSuccess) return fail_hip(e, scratch_for);
+    uint8_t *d_pairs = (uint8_t *)gc.la.p, *d_matches = d_pairs + a_pairs, *d_kept = d_matches + a_q, *d_first = d_kept + a_q,
+            *d_extra = d_first + a_q, *d_over = d_extra + extra_bytes, *d_tmp = d_over + 256;
     // ---- the search (for_each_var_slice); every slice's pairs land in the batch's [S][Q] block: the only slice writes
     // them there, one of several leaves them behind its start records and they are copied over row by row
-    auto a_rec = [&](size_t mq) { return al((size_t)S * mq * 16); };
-    rc = for_each_var_slice(
-        *c, st, text, off, Q, [&](size_t mq) { return a_rec(mq) + (mq == Q ? 0 : al((size_t)S * mq * 16)); },
+    auto a_rec = [&](size_t mq) { return al256((size_t)S * mq * 16); };
+    int rc = for_each_var_slice(
+        *gc.c, st, text, off, Q, [&](size_t mq) { return a_rec(mq) + (mq == Q ? 0 : al256((size_t)S * mq * 16)); },
         [&](size_t q0, size_t mq) -> int {  // nothing to search: pairs of all ones are no interval of any shard (upper >= n)
             HIP_OK(hipMemset2DAsync(d_pairs + q0 * 16, Q * 16, 0xFF, mq * 16, S, st));
             return RSBWT_OK;
@@ -1252,33 +1297,52 @@ int query_capped_device(rsbwt_set_t *s, const char *text, const uint64_t *off, s
             return RSBWT_OK;
         });
     if (rc) return rc;
-    // ---- totals, the limit, first[]; the cells of the kept rows
-    const size_t tmp_bytes = a_tmp - 256;
+    // ---- totals, the limit, first[]
+    const size_t tmp_bytes = interval_rows_scan_bytes(scan_items);
     e = launch_interval_totals(g->d_views, S, d_pairs, Q, max_rows, d_matches, d_kept, d_first, d_over, d_tmp, tmp_bytes, st);
-    if (e == hipSuccess) e = launch_interval_cells(g->d_views, S, d_pairs, Q, max_rows, d_matches, d_cellw, d_cellpos, d_tmp, tmp_bytes, st);
     if (e != hipSuccess) return fail_hip(e, "interval-rows kernels");
-    uint64_t over = 0;
+    *ci = capped_intervals{d_pairs, d_matches, d_first, d_extra, d_tmp, tmp_bytes, 0, 0};
     HIP_OK(hipMemcpyAsync(first, d_first, (Q + 1) * 8, hipMemcpyDeviceToHost, st));
     if (matches) HIP_OK(hipMemcpyAsync(matches, d_matches, Q * 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(&over, d_over, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(&ci->over, d_over, 8, hipMemcpyDeviceToHost, st));  // (the caller's struct: it outlives gc's synchronise)
     HIP_OK(hipStreamSynchronize(st));
-    const uint64_t total = first[Q];
+    ci->total = first[Q];
+    return RSBWT_OK;
+}
+
+// The reads of a capped query on one device group: the cells of the kept rows, the rows by cell for the ragged walks
+// (extract_lines.hip) and as (shard, cell row) in the caller's order, all made and taken where they are in HBM.
+int query_capped_device(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t max_rows, uint64_t *first,
+                        uint32_t *read_shard, char *reads, uint32_t read_stride, uint32_t *read_len, size_t cap_reads, size_t *nreads,
+                        uint64_t *matches) {
+    capped_intervals ci;  // (before gc: a copy into it may still be in flight when gc waits for the stream)
+    group_call gc(s->groups[0], true);
+    if (gc.rc) return gc.rc;
+    dev_group *g = gc.g;
+    hipStream_t st = gc.st;
+    const uint32_t S = (uint32_t)g->idx.size();
+    const size_t cells = (size_t)S * Q, a_cells = al256((cells + 1) * 8);
+    int rc = capped_intervals_device(s, gc, text, off, Q, max_rows, 2 * a_cells, cells + 1, "scratch for a capped query", first, matches, &ci);
+    if (rc) return rc;
+    const uint64_t total = ci.total;
     *nreads = (size_t)total;
-    capped_last_work[2] = over;
+    capped_last_work[2] = ci.over;
     capped_last_work[3] = (Q + 1) * 8 + (matches ? Q * 8 : 0) + 8;
     if (total > cap_reads) return fail(RSBWT_ERANGE, "%llu reads over the set, room for %zu", (unsigned long long)total, cap_reads);
     if (total == 0) return RSBWT_OK;
     if (!reads || !read_len) return fail(RSBWT_EINVAL, "null argument");
     if (total >= (1ull << 31)) return CAPPED_TAKE_HOST;  // (the walk kernels number a launch's rows in 32 bits)
-    // ---- the rows, by cell for the walks and as (shard, cell row) in the caller's order; the ragged walks; the copy back
+    uint8_t *d_cellw = ci.d_extra, *d_cellpos = d_cellw + a_cells;
+    hipError_t e = launch_interval_cells(g->d_views, S, ci.d_pairs, Q, max_rows, ci.d_matches, d_cellw, d_cellpos, ci.d_tmp, ci.tmp_bytes, st);
+    if (e != hipSuccess) return fail_hip(e, "interval-rows kernels");
     if ((rc = ensure_group_xviews(s, g, st)) != RSBWT_OK) return rc;
-    const size_t a_rows = al(total * 8), a_u32 = al(total * 4), a_out = al(total * (size_t)read_stride);
-    e = g->scratch.take(a_rows + 4 * a_u32 + a_out, st, &lb);
+    const size_t a_rows = al256(total * 8), a_u32 = al256(total * 4), a_out = al256(total * (size_t)read_stride);
+    e = g->scratch.take(a_rows + 4 * a_u32 + a_out, st, &gc.lb);
     if (e != hipSuccess) return fail(RSBWT_ENOMEM, "%llu reads of %u bytes do not fit the device's free memory: %s", (unsigned long long)total,
                                      read_stride, hipGetErrorString(e));
-    uint8_t *d_crow = (uint8_t *)lb.p, *d_out = d_crow + a_rows, *d_dest = d_out + a_out, *d_shard = d_dest + a_u32, *d_plen = d_shard + a_u32,
+    uint8_t *d_crow = (uint8_t *)gc.lb.p, *d_out = d_crow + a_rows, *d_dest = d_out + a_out, *d_shard = d_dest + a_u32, *d_plen = d_shard + a_u32,
             *d_rlen = d_plen + a_u32;
-    e = launch_interval_fill(g->d_views, S, d_pairs, Q, d_first, (size_t)total, d_shard, nullptr, d_cellpos, d_crow, d_dest, st);
+    e = launch_interval_fill(g->d_views, S, ci.d_pairs, Q, ci.d_first, (size_t)total, d_shard, nullptr, d_cellpos, d_crow, d_dest, st);
     if (e == hipSuccess)
         e = launch_extract_ragged(g->scratch, g->d_xviews, S, d_crow, (size_t)total, d_cellpos, Q, d_out, read_stride, d_plen, d_rlen, g->num_cus, st);
     if (e != hipSuccess) return fail_hip(e, "row expansion and extract kernel launches");
@@ -1291,10 +1355,7 @@ int query_capped_device(rsbwt_set_t *s, const char *text, const uint64_t *off, s
     HIP_OK(hipMemcpyAsync(hs.data(), d_shard, total * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     for (size_t t = 0; t < total; ++t) {
-        const size_t cell = hd[t];
-        const uint32_t keep = hl[cell] == 0xFFFFFFFFu ? 0u : hl[cell];
-        if (keep) memcpy(reads + t * (size_t)read_stride, ho.data() + cell * (size_t)read_stride, keep);
-        read_len[t] = hl[cell];
+        scatter_read(ho.data(), hl.data(), nullptr, hd[t], reads, read_stride, read_len, nullptr, t);
         if (read_shard) read_shard[t] = (uint32_t)g->idx[hs[t]];
     }
     return RSBWT_OK;
@@ -1319,27 +1380,13 @@ int query_capped_body(rsbwt_set_t *s, const char *text, const uint64_t *off, siz
         if (rc != CAPPED_TAKE_HOST) return rc;
         for (uint64_t &w : capped_last_work) w = 0;
     }
-    // several device groups (or a batch of 2^31 rows): the intervals come to the host, the limit is applied there, and the
-    // rows go the way rsbwt_set_query_var's go
+    // several device groups (or a batch of 2^31 rows): the intervals come to the host, the limit is applied there
+    // (intervals_to_rows_host), and the rows go the way rsbwt_set_query_var's go
     std::vector<uint64_t> lo(S * Q), up(S * Q);
     const int rc = rsbwt_set_find_intervals_var_body(s, text, off, Q, lo.data(), up.data(), false);
     if (rc) return rc;
-    uint64_t over = 0;
-    for (size_t q = 0; q < Q; ++q) {
-        uint64_t m = 0;
-        for (size_t i = 0; i < S; ++i) {
-            const uint64_t l = lo[i * Q + q], u = up[i * Q + q];
-            if (l <= u && u < s->shards[i]->view.n) m += u - l + 1;
-        }
-        if (matches) matches[q] = m;
-        if (max_rows && m > max_rows) {
-            ++over;
-            for (size_t i = 0; i < S; ++i) { lo[i * Q + q] = 1; up[i * Q + q] = 0; }
-        }
-    }
-    capped_last_work[2] = over;
     capped_last_work[3] = S * Q * 16;
-    const int rq = set_query_rows(s, Q, lo, up, first, read_shard, reads, read_stride, read_len, cap_reads, nreads);
+    const int rq = set_query_rows(s, Q, lo, up, max_rows, first, matches, &capped_last_work[2], read_shard, reads, read_stride, read_len, cap_reads, nreads);
     if (rq == RSBWT_OK) capped_last_work[1] = *nreads;
     return rq;
 }
@@ -1399,45 +1446,30 @@ static int set_locate_body(rsbwt_set_t *s, const uint32_t *shard_of, const uint6
     std::atomic<uint64_t> walked{0}, steps{0};
     const int rc = for_each_group(s, [&](size_t gi) -> int {
         dev_group *g = s->groups[gi];
-        const bool whole = s->groups.size() == 1;  // (the group's shard numbers are the set's)
-        std::vector<size_t> pos;
-        std::vector<uint32_t> lsh;
-        std::vector<uint64_t> lrows;
+        const bool whole = s->groups.size() == 1;  // (the group's shard numbers are the set's: the caller's arrays as they are)
+        group_share sh;
         if (!whole) {
-            std::vector<uint32_t> local(S, ~0u);
-            for (size_t j = 0; j < g->idx.size(); ++j) local[g->idx[j]] = (uint32_t)j;
-            for (size_t i = 0; i < n; ++i)
-                if (local[shard_of[i]] != ~0u) {
-                    pos.push_back(i);
-                    lsh.push_back(local[shard_of[i]]);
-                    lrows.push_back(rows[i]);
-                }
-            if (pos.empty()) return RSBWT_OK;
+            sh = share_of_group(s, g, shard_of, rows, n);
+            if (sh.pos.empty()) return RSBWT_OK;
         }
-        int rg = use_device(g->device);
-        if (rg) return rg;
-        call_ctx *c = g->pool.acquire();
-        if (!c) return fail(RSBWT_EHIP, "cannot create a HIP stream");
-        struct release_t {
-            dev_group *g;
-            call_ctx *c;
-            ~release_t() { g->pool.release(c); }
-        } release{g, c};
+        group_call gc(g);
+        if (gc.rc) return gc.rc;
+        int rg;
         uint64_t wk[2] = {0, 0};
         if (whole) {
-            rg = locate_host_views(g->scratch, *c, g->d_views, (uint32_t)g->idx.size(), g->num_cus, shard_of, rows, n, max_steps, read_row, ordinal,
+            rg = locate_host_views(g->scratch, *gc.c, g->d_views, (uint32_t)g->idx.size(), g->num_cus, shard_of, rows, n, max_steps, read_row, ordinal,
                                    offset, wk);
         } else {
-            const size_t m = pos.size();
+            const size_t m = sh.pos.size();
             std::vector<uint64_t> rr(read_row ? m : 0), od(ordinal ? m : 0);
             std::vector<uint32_t> of(offset ? m : 0);
-            rg = locate_host_views(g->scratch, *c, g->d_views, (uint32_t)g->idx.size(), g->num_cus, lsh.data(), lrows.data(), m, max_steps,
+            rg = locate_host_views(g->scratch, *gc.c, g->d_views, (uint32_t)g->idx.size(), g->num_cus, sh.shard.data(), sh.rows.data(), m, max_steps,
                                    read_row ? rr.data() : nullptr, ordinal ? od.data() : nullptr, offset ? of.data() : nullptr, wk);
             if (rg == RSBWT_OK)
                 for (size_t t = 0; t < m; ++t) {
-                    if (read_row) read_row[pos[t]] = rr[t];
-                    if (ordinal) ordinal[pos[t]] = od[t];
-                    if (offset) offset[pos[t]] = of[t];
+                    if (read_row) read_row[sh.pos[t]] = rr[t];
+                    if (ordinal) ordinal[sh.pos[t]] = od[t];
+                    if (offset) offset[sh.pos[t]] = of[t];
                 }
         }
         walked += wk[0];
@@ -1488,68 +1520,23 @@ namespace {
 int locate_capped_device(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t max_rows, uint32_t max_steps,
                          uint64_t *first, uint32_t *read_shard, uint64_t *rows, uint64_t *read_row, uint64_t *ordinal, uint32_t *offset,
                          size_t cap, size_t *nrows, uint64_t *matches, uint64_t *work2) {
-    dev_group *g = s->groups[0];
+    capped_intervals ci;  // (before gc: a copy into it may still be in flight when gc waits for the stream)
+    group_call gc(s->groups[0], true);
+    if (gc.rc) return gc.rc;
+    dev_group *g = gc.g;
+    hipStream_t st = gc.st;
     const uint32_t S = (uint32_t)g->idx.size();
-    int rc = use_device(g->device);
+    const int rc = capped_intervals_device(s, gc, text, off, Q, max_rows, 0, Q + 1, "scratch for a capped locate", first, matches, &ci);
     if (rc) return rc;
-    call_ctx *c = g->pool.acquire();
-    if (!c) return fail(RSBWT_EHIP, "cannot create a HIP stream");
-    hipStream_t st = c->st[0];
-    scratch_cache::lease la, lb;
-    struct release_t {
-        dev_group *g;
-        call_ctx *c;
-        scratch_cache::lease *la, *lb;
-        ~release_t() {
-            (void)hipStreamSynchronize(c->st[0]);
-            g->scratch.give(*la, c->st[0]);
-            g->scratch.give(*lb, c->st[0]);
-            g->pool.release(c);
-        }
-    } release{g, c, &la, &lb};
-    const size_t cells = (size_t)S * Q;
-    const size_t a_pairs = al256(cells * 16), a_q = al256((Q + 1) * 8), a_tmp = interval_rows_scan_bytes(Q + 1) + 256;
-    hipError_t e = g->scratch.take(a_pairs + 3 * a_q + 256 + a_tmp, st, &la);
-    if (e != hipSuccess) return fail_hip(e, "scratch for a capped locate");
-    uint8_t *d_pairs = (uint8_t *)la.p, *d_matches = d_pairs + a_pairs, *d_kept = d_matches + a_q, *d_first = d_kept + a_q,
-            *d_over = d_first + a_q, *d_tmp = d_over + 256;
-    // ---- the search (query_capped_device's: every slice's pairs land in the batch's [S][Q] block)
-    auto a_rec = [&](size_t mq) { return al256((size_t)S * mq * 16); };
-    rc = for_each_var_slice(
-        *c, st, text, off, Q, [&](size_t mq) { return a_rec(mq) + (mq == Q ? 0 : al256((size_t)S * mq * 16)); },
-        [&](size_t q0, size_t mq) -> int {
-            HIP_OK(hipMemset2DAsync(d_pairs + q0 * 16, Q * 16, 0xFF, mq * 16, S, st));
-            return RSBWT_OK;
-        },
-        [&](const var_slice &sl) -> int {
-            const size_t q0 = sl.q0, mq = sl.mq;
-            uint8_t *d_rec = sl.d_extra, *d_res = mq == Q ? d_pairs : d_rec + a_rec(mq);
-            const hipError_t ei = launch_search_init_var(g->d_views, S, sl.d_pk, sl.d_ok, sl.d_len, mq, sl.wpq, d_rec, st);
-            if (ei != hipSuccess) return fail_hip(ei, "start-record kernel launch");
-            search_extra ex;
-            ex.narrow = group_is_narrow(s, g, sl.k);
-            ex.d_init = d_rec;
-            ex.pairs = true;
-            const int rs = search_launch(*g, g->d_views, S, g->num_cus, sl.d_pk, sl.d_ok, mq, sl.k, d_res, nullptr, false, st, &ex);
-            if (rs) return rs;
-            if (mq != Q) HIP_OK(hipMemcpy2DAsync(d_pairs + q0 * 16, Q * 16, d_res, mq * 16, mq * 16, S, hipMemcpyDeviceToDevice, st));
-            return RSBWT_OK;
-        });
-    if (rc) return rc;
-    e = launch_interval_totals(g->d_views, S, d_pairs, Q, max_rows, d_matches, d_kept, d_first, d_over, d_tmp, a_tmp - 256, st);
-    if (e != hipSuccess) return fail_hip(e, "interval-rows kernels");
-    HIP_OK(hipMemcpyAsync(first, d_first, (Q + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (matches) HIP_OK(hipMemcpyAsync(matches, d_matches, Q * 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    const uint64_t total = first[Q];
+    const uint64_t total = ci.total;
     *nrows = (size_t)total;
     if (total > cap) return fail(RSBWT_ERANGE, "%llu rows over the set, room for %zu", (unsigned long long)total, cap);
     if (total == 0) return RSBWT_OK;
     const size_t a8 = al256(total * 8), a4 = al256(total * 4);
-    e = g->scratch.take(3 * a8 + 2 * a4 + 256, st, &lb);
+    hipError_t e = g->scratch.take(3 * a8 + 2 * a4 + 256, st, &gc.lb);
     if (e != hipSuccess) return fail(RSBWT_ENOMEM, "%llu rows do not fit the device's free memory: %s", (unsigned long long)total, hipGetErrorString(e));
-    uint8_t *d_rows = (uint8_t *)lb.p, *d_rr = d_rows + a8, *d_od = d_rr + a8, *d_of = d_od + a8, *d_sh = d_of + a4, *d_wk = d_sh + a4;
-    e = launch_interval_fill(g->d_views, S, d_pairs, Q, d_first, (size_t)total, d_sh, d_rows, nullptr, nullptr, nullptr, st);
+    uint8_t *d_rows = (uint8_t *)gc.lb.p, *d_rr = d_rows + a8, *d_od = d_rr + a8, *d_of = d_od + a8, *d_sh = d_of + a4, *d_wk = d_sh + a4;
+    e = launch_interval_fill(g->d_views, S, ci.d_pairs, Q, ci.d_first, (size_t)total, d_sh, d_rows, nullptr, nullptr, nullptr, st);
     if (e != hipSuccess) return fail_hip(e, "row expansion");
     const bool walk = read_row || ordinal || offset;
     unsigned long long wk[2] = {0, 0};
@@ -1594,45 +1581,19 @@ int rsbwt_set_locate_var_capped(rsbwt_set_t *s, const char *text, const uint64_t
             return rc;
         }
         // several device groups: the intervals come to the host, the limit and the expansion run there
-        // (query_capped_body's rules), and the rows go the way rsbwt_set_locate's go
+        // (intervals_to_rows_host), and the rows go the way rsbwt_set_locate's go
         std::vector<uint64_t> lo(S * Q), up(S * Q);
         int rc = rsbwt_set_find_intervals_var_body(s, text, off, Q, lo.data(), up.data(), false);
         if (rc) return rc;
-        auto width = [&](size_t i, size_t q) -> uint64_t {
-            const uint64_t l = lo[i * Q + q], u = up[i * Q + q];
-            return (l <= u && u < s->shards[i]->view.n) ? u - l + 1 : 0;
-        };
-        size_t total = 0;
-        for (size_t q = 0; q < Q; ++q) {
-            uint64_t m = 0;
-            for (size_t i = 0; i < S; ++i) m += width(i, q);
-            if (matches) matches[q] = m;
-            first[q] = total;
-            if (max_rows && m > max_rows) {
-                for (size_t i = 0; i < S; ++i) { lo[i * Q + q] = 1; up[i * Q + q] = 0; }
-            } else {
-                total += (size_t)m;
-            }
-        }
-        first[Q] = total;
+        const expanded_rows hr = intervals_to_rows_host(s, Q, lo, up, max_rows, cap, first, matches);
+        const size_t total = hr.total;
         *nrows = total;
         if (total > cap) return fail(RSBWT_ERANGE, "%zu rows over the set, room for %zu", total, cap);
         if (total == 0) return RSBWT_OK;
-        std::vector<uint32_t> sh(total);
-        std::vector<uint64_t> rw(total);
-        size_t at = 0;
-        for (size_t q = 0; q < Q; ++q)
-            for (size_t i = 0; i < S; ++i) {
-                const uint64_t w = width(i, q), l = lo[i * Q + q];
-                for (uint64_t r = 0; r < w; ++r, ++at) {
-                    sh[at] = (uint32_t)i;
-                    rw[at] = l + r;
-                }
-            }
-        if (read_shard) memcpy(read_shard, sh.data(), total * sizeof(uint32_t));
-        if (rows) memcpy(rows, rw.data(), total * sizeof(uint64_t));
+        if (read_shard) memcpy(read_shard, hr.shard_of.data(), total * sizeof(uint32_t));
+        if (rows) memcpy(rows, hr.rows.data(), total * sizeof(uint64_t));
         if (!read_row && !ordinal && !offset) return RSBWT_OK;
-        rc = set_locate_body(s, sh.data(), rw.data(), total, max_steps, read_row, ordinal, offset, wk);
+        rc = set_locate_body(s, hr.shard_of.data(), hr.rows.data(), total, max_steps, read_row, ordinal, offset, wk);
         locate_set_last_work(wk[0], wk[1]);
         return rc;
     });

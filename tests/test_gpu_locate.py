@@ -248,6 +248,56 @@ def test_gpu_set_locate_on_two_logical_devices(rsb, refs, monkeypatch):
         assert np.array_equal(one[key], two[key]), key
 
 
+def test_gpu_locate_queries_host_path_at_every_limit(rsb, refs, monkeypatch):
+    """rsbwt_set_locate_var_capped on two device groups (limit and expansion on the host) against the one-group set (both
+    on the GPU), at limits 0, 1 and 5, in the two forms that walk nothing: every output null (the sizing call), and
+    shard / row wanted with read_row / ordinal / offset null"""
+    L = rsb.lib()
+    if L.rsbwt_device_count() < 2:
+        monkeypatch.setenv("RSBWT_ENABLE_TEST_HOOKS", "1")
+        monkeypatch.setenv("RSBWT_TEST_DEVICE_ALIASES", "2")
+    ref = refs("pop")
+    span = F.SPANS["pop"]["far"]
+    cut = [ref.fx.shards[p][i][o:o + k] for p in (0, 1) for i, o, k in ((0, 3, 9), (7, 17, 12), (11, 30, 10))]  # 4 to 12 rows each
+    qs = ref.fx.queries(15, 1) + cut + ["A", "ACNT", ""]
+    Q = len(qs)
+    pv = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
+
+    def run(devices):
+        gs = [rsb.GpuBWT(runs=runs, num_strings=len(sh), ktab_depth=6, window_span=span, for_reads=True, device=d)
+              for d, sh, runs in zip(devices, ref.fx.shards, ref.fx.runs())]
+        ss = rsb.ShardSet(gs)
+        try:
+            assert L.rsbwt_set_devices(ss._s) == len(set(devices))
+            text, off = ss._var_text(qs)
+            out = []
+            for max_rows in (0, 1, 5):
+                first, matches = np.full(Q + 1, 77, np.uint64), np.full(Q, 77, np.uint64)
+                n = C.c_size_t(12345)
+                rc = L.rsbwt_set_locate_var_capped(ss._s, pv(text), pv(off), Q, max_rows, 0, pv(first), None, None, None, None, None, 0,
+                                                   C.byref(n), pv(matches))
+                total = n.value
+                assert rc == (-7 if total else 0) and total == int(first[Q]), (devices, max_rows, rc)
+                first2, matches2 = np.full(Q + 1, 77, np.uint64), np.full(Q, 77, np.uint64)
+                sh, rows = np.full(total + 1, 0xA5A5A5A5, np.uint32), np.full(total + 1, 2 ** 64 - 1, np.uint64)
+                n2 = C.c_size_t(12345)
+                rc = L.rsbwt_set_locate_var_capped(ss._s, pv(text), pv(off), Q, max_rows, 0, pv(first2), pv(sh), pv(rows), None, None, None,
+                                                   total, C.byref(n2), pv(matches2))
+                assert rc == 0, L.rsbwt_last_error()
+                assert sh[total] == 0xA5A5A5A5 and rows[total] == 2 ** 64 - 1
+                assert rsb.ShardSet.locate_last_work() == dict(located=0, lf_steps=0)
+                out.append(dict(nrows=np.array([total, n2.value]), first=first, matches=matches, first2=first2, matches2=matches2, shard=sh, row=rows))
+            return out
+        finally:
+            _close(ss, gs)
+    one, two = run([0, 0]), run([0, 1])
+    assert int(one[0]["nrows"][0]) > int(one[2]["nrows"][0]) > int(one[1]["nrows"][0]) > 0  # (each limit cuts: "A" alone is thousands of rows)
+    for max_rows, a, b in zip((0, 1, 5), one, two):
+        assert a["nrows"][0] == a["nrows"][1]
+        for key in a:
+            assert np.array_equal(a[key], b[key]), (max_rows, key)
+
+
 # ---- 8. the query form against plain string search -------------------------------------------------------------------
 
 def _check_queries(ss, ref, ts, qs, where):

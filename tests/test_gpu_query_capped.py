@@ -335,6 +335,73 @@ def test_gpu_two_device_groups_give_the_one_device_answer(rsb, oracle, two_devic
         assert wa[:3] == [a[1], 0, wa[2]] and wb[:3] == [0, b[1], wa[2]]
 
 
+# ---- 6b. a batch of two slices ----------------------------------------------------------------------------------------------
+
+SLICE = 65536  # where the variable-length loop cuts a batch (csrc/capi.hip, for_each_var_slice)
+
+
+def _cut_queries(fx):
+    """40 queries cut from reads, 9 to 45 symbols: between 1 and about ten rows each over the set"""
+    import random
+    rng = random.Random("slices/" + fx.name)
+    reads = sorted({r for sh in fx.shards for r in sh})
+    qs = []
+    for k in (9, 12, 20, 45):
+        for _ in range(10):
+            r = rng.choice([x for x in reads if len(x) >= k])
+            s = rng.randrange(len(r) - k + 1)
+            qs.append(r[s:s + k])
+    return qs
+
+
+@pytest.mark.parametrize("tail", ["real", "empty"])
+def test_gpu_capped_calls_over_two_slices(rsb, pop_set, tail):
+    """65,536 + 40 queries: 40 real ones, empty strings up to the cut, and a second slice of the 40 real ones again
+    ("real": its pairs are copied into the batch's [S][Q] block row by row) or of 40 empty strings ("empty": the block's
+    columns are set, nothing is launched).  Reads and positions of each real segment are those of the 40-query call; the
+    empty queries have no matches and zero-width first[]."""
+    L = rsb.lib()
+    real = _cut_queries(F.fixture("pop"))
+    R = len(real)
+    again = tail == "real"
+    qs = real + [""] * (SLICE - R) + (real if again else [""] * R)
+    assert len(qs) == SLICE + R and R == 40
+
+    def check_first(first, matches, f40, m40, where):
+        n40 = int(f40[R])
+        assert np.array_equal(first[:R + 1], f40) and np.array_equal(matches[:R], m40), where
+        assert (first[R:SLICE + 1] == n40).all() and not matches[R:SLICE].any(), where
+        if again:
+            assert np.array_equal(first[SLICE:] - np.uint64(n40), f40) and np.array_equal(matches[SLICE:], m40), where
+        else:
+            assert (first[SLICE:] == n40).all() and not matches[SLICE:].any(), where
+        return n40
+
+    for max_rows in (0, 7):
+        rc, n40, *_ = _raw_call(L, pop_set, real, max_rows, 0, 256)
+        assert rc == ERANGE and n40 > 0
+        want = _raw_call(L, pop_set, real, max_rows, n40, 256)
+        assert want[0] == 0 and want[1] == n40
+        assert max_rows == 0 or ((want[6] > max_rows).any() and (want[6] <= max_rows).any())
+        total = n40 * (2 if again else 1)
+        got = _raw_call(L, pop_set, qs, max_rows, total, 256)
+        assert got[0] == 0 and got[1] == total, L.rsbwt_last_error()
+        assert check_first(got[2], got[6], want[2], want[6], ("reads", max_rows)) == n40
+        for x, y, what in zip(got[3:6], want[3:6], ("read_shard", "read_len", "reads")):
+            assert np.array_equal(x[:n40], y[:n40]), (what, max_rows)
+            assert not again or np.array_equal(x[n40:total], y[:n40]), (what, max_rows, "second slice")
+        assert _last_work(L)[:2] == [total, 0]
+    for max_rows in (0, 5):
+        want = pop_set.locate_queries(real, max_rows=max_rows)
+        got = pop_set.locate_queries(qs, max_rows=max_rows)
+        n40 = check_first(got["first"], got["matches"], want["first"], want["matches"], ("locate", max_rows))
+        assert n40 > 0 and (max_rows == 0 or ((want["matches"] > max_rows).any() and (want["matches"] <= max_rows).any()))
+        for key in ("shard", "row", "read_row", "ordinal", "offset"):
+            assert got[key].size == n40 * (2 if again else 1), (key, max_rows)
+            assert np.array_equal(got[key][:n40], want[key]), (key, max_rows)
+            assert not again or np.array_equal(got[key][n40:], want[key]), (key, max_rows, "second slice")
+
+
 # ---- 7. the service loop: a window that holds "A" ---------------------------------------------------------------------------
 
 def _reads_request(q):

@@ -532,6 +532,56 @@ void rsbwt_set_kmer_last_work(uint64_t *work5);
 /* the same call's wall time: {total, inside the calls that wait for the device (search, exact-match, identity walks,
  * extraction), the rest = host work} in ms */
 void rsbwt_set_kmer_last_times(double *ms3);
+/* SiteMatch candidates: find_gt_reads (src/service/service.cpp:507-711; GtTask::run calls it once per tile, :1048-1072)
+ * over every shard -- the BWT half of a SiteMatch request; the alignment (align_gt_read) stays with the caller.  Query q =
+ * text[off[q] .. off[q+1]) of L symbols with its site pos[q] (1-based, as find_gt_reads receives it); k, skip and M =
+ * max_interval_size (0 = 10,000, :85) hold for the call.  k <= 0, skip < 0, L < k or pos > L: the query contributes
+ * nothing.  Tile i = 0 .. (L-k)/(skip+1) is w[s0:e0), s0 = (skip+1) i, e0 = s0 + k; one holding a symbol outside ACGT
+ * contributes nothing.  A tile whose interval holds at most M rows is ONE leg (leg = 0).  Any other tile is lengthened
+ * one symbol at a time until the interval of w[a:b) holds at most M rows -- 0 for an absent string or one that took in a
+ * symbol outside ACGT, then (lower, upper) = (1, 0) -- in two legs:
+ *   tile LEFT of the site (pos > e0):   leg 1 grows right; leg 2 (only if s0 > 0) takes s0 - 1 and goes on left while
+ *                                       a > 0, then right;
+ *   tile RIGHT of it (pos <= s0):       leg 1 grows left; leg 2 (only if e0 < L) takes e0 and goes on right while b < L,
+ *                                       then left;
+ *   tile COVERING it:                   leg 1 grows right only, leg 2 left only.
+ * A leg that would need a < 0 or b > L has no answer and is left out (the reference loops forever or throws
+ * std::out_of_range there); the tile's other leg still counts.  Every row j of a leg's interval is a candidate; with the
+ * reference's start = a + 1 and end = b the span filter keeps it iff
+ *   LEFT:   pos - end <= (|extractPostfix(j)| - k) + 4        RIGHT:   start - pos <= |extractPrefix(j)| + 4
+ * (the differences in unsigned 64-bit arithmetic as the reference takes them: a leg lengthened past pos keeps no row;
+ * k is the tile's length, not the lengthened string's); COVERING keeps every row.
+ *   rsbwt_set_gt_legs   the legs of query q are legs[first[q] .. first[q+1]) (first has Q + 1 entries), ordered by
+ *                       (tile, leg, shard); cap = 0 sizes the buffer (RSBWT_ERANGE, *nlegs set).  Needs no
+ *                       RSBWT_OPEN_READS.
+ *   rsbwt_set_gt_reads  the distinct read strings over the kept rows: those of query q in shard p are first[q*S+p] ..
+ *                       first[q*S+p+1] (first has Q*S + 1 entries), ascending read_row (rsbwt_locate's: the row of the
+ *                       read's full suffix; read_row may be NULL); a string that occurs at several read_rows is reported
+ *                       once, at the lowest.  reads / read_stride / read_len as rsbwt_set_kmer_reads; cap_reads = 0 sizes
+ *                       the buffers (RSBWT_ERANGE, *nreads set).
+ *   rsbwt_set_gt_count  counts[q*S+p] = how many reads that is.
+ * The read calls need every shard opened with RSBWT_OPEN_READS (else RSBWT_EINVAL).  A query longer than 2^31 - 1
+ * symbols is RSBWT_EINVAL, and so is a candidate row whose LF walk to its read's start does not end within 2^20 steps (a
+ * corrupt index): no read is left out silently.  Each device group narrows, expands, walks, filters and compacts its
+ * shards' rows where they are; the legs and one record per row the filter kept come back, and each distinct read is
+ * extracted once.
+ * rsbwt_set_gt_last_work: the calling thread's last call: {legs, legs with no answer, LF steps spent lengthening,
+ * candidate rows, rows the device's filter kept (a LEFT row stays there until its read's length decides), distinct reads
+ * extracted}; a legs call leaves the last three 0, a call that finds no tile leaves all six 0. */
+typedef struct rsbwt_gt_leg {
+    uint64_t query;
+    uint32_t tile, leg, shard; /* leg: 0 = the tile itself, 1 / 2 = the lengthened legs */
+    uint32_t a, b, reserved;   /* the final string is w[a:b): the reference's start = a + 1, end = b */
+    uint64_t lower, upper;     /* findInterval(w[a:b)) in that shard */
+} rsbwt_gt_leg;
+int rsbwt_set_gt_legs(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, int32_t k, int32_t skip,
+                      uint64_t M, uint64_t *first, rsbwt_gt_leg *legs, size_t cap, size_t *nlegs);
+int rsbwt_set_gt_reads(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, int32_t k, int32_t skip,
+                       uint64_t M, uint64_t *first, char *reads, uint32_t read_stride, uint32_t *read_len, uint64_t *read_row,
+                       size_t cap_reads, size_t *nreads);
+int rsbwt_set_gt_count(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, int32_t k, int32_t skip,
+                       uint64_t M, uint64_t *counts);
+void rsbwt_set_gt_last_work(uint64_t *work6);
 /* Device-resident forms, for a set on ONE device (one process per GPU: bench.py --mode 1mm|extract).
  * d_hits [num_shards][cap_per_shard] x 32-byte records (rsbwt_hits_1mm_dev's), d_totals u64[num_shards];
  * d_rows [num_shards][n] (row numbers are per shard), d_out [num_shards][n][stride], d_len / d_prefix_len [num_shards][n]. */

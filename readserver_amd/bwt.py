@@ -242,6 +242,8 @@ def find_intervals_1mm(pBWT, kmers):
 
 HIT_1MM = np.dtype([("lower", "<u8"), ("upper", "<u8"), ("query", "<u4"), ("pos", "<i2"), ("base", "S1"),
                     ("reserved", "u1")])  # = rsbwt_hit_1mm
+GT_LEG = np.dtype([("query", "<u8"), ("tile", "<u4"), ("leg", "<u4"), ("shard", "<u4"), ("a", "<u4"), ("b", "<u4"), ("reserved", "<u4"),
+                   ("lower", "<u8"), ("upper", "<u8")])  # = rsbwt_gt_leg
 
 
 def hits_1mm_batch(pBWT, kmers, cap=None):
@@ -536,6 +538,70 @@ class ShardSet:
         t = (C.c_double * 3)()
         lib().rsbwt_set_kmer_last_times(t)
         return dict(total_ms=t[0], device_ms=t[1], host_ms=t[2])
+
+    # -- SiteMatch candidates (find_gt_reads, src/service/service.cpp:507-711): rsbwt_set_gt_*
+    def gt_legs(self, queries, pos, k, skip=0, max_interval_size=0):
+        """per query: the legs of its tiles as (tile, leg, shard, a, b, lower, upper), ordered by (tile, leg, shard): the
+        final string of a leg is query[a:b), its interval in that shard [lower, upper]; leg 0 = the tile itself, 1 / 2 =
+        the lengthened legs (rsbwt_set_gt_legs)"""
+        text, off = self._var_text(queries)
+        Q = len(queries)
+        p = np.ascontiguousarray(pos, np.uint64)
+        first = np.zeros(Q + 1, np.uint64)
+        n = C.c_size_t()
+        rc = lib().rsbwt_set_gt_legs(self._s, _ptr(text), _ptr(off), Q, _ptr(p), k, skip, max_interval_size, _ptr(first), None, 0, C.byref(n))
+        if rc not in (0, -7):
+            check(rc)
+        total = n.value
+        legs = np.zeros(max(total, 1), GT_LEG)
+        if total:
+            check(lib().rsbwt_set_gt_legs(self._s, _ptr(text), _ptr(off), Q, _ptr(p), k, skip, max_interval_size, _ptr(first), _ptr(legs), total,
+                                          C.byref(n)))
+        return [[(int(r["tile"]), int(r["leg"]), int(r["shard"]), int(r["a"]), int(r["b"]), int(r["lower"]), int(r["upper"]))
+                 for r in legs[int(first[q]):int(first[q + 1])]] for q in range(Q)]
+
+    def gt_reads(self, queries, pos, k, skip=0, max_interval_size=0, read_stride=256, with_rows=False):
+        """[query][shard] -> the distinct reads over the rows the span filter keeps, ascending read_row (with_rows: (read_row,
+        read) pairs) (rsbwt_set_gt_reads)"""
+        text, off = self._var_text(queries)
+        Q, S = len(queries), len(self.shards)
+        p = np.ascontiguousarray(pos, np.uint64)
+        first = np.zeros(Q * S + 1, np.uint64)
+        n = C.c_size_t()
+        rc = lib().rsbwt_set_gt_reads(self._s, _ptr(text), _ptr(off), Q, _ptr(p), k, skip, max_interval_size, _ptr(first), None, read_stride, None,
+                                      None, 0, C.byref(n))
+        if rc not in (0, -7):
+            check(rc)
+        total = n.value
+        reads = np.zeros((max(total, 1), read_stride), np.uint8)
+        ln = np.zeros(max(total, 1), np.uint32)
+        rr = np.zeros(max(total, 1), np.uint64)
+        if total:
+            check(lib().rsbwt_set_gt_reads(self._s, _ptr(text), _ptr(off), Q, _ptr(p), k, skip, max_interval_size, _ptr(first), _ptr(reads),
+                                           read_stride, _ptr(ln), _ptr(rr), total, C.byref(n)))
+            if (ln[:total] == 0xFFFFFFFF).any():
+                raise RsbwtError(-1, "a read does not fit read_stride")
+
+        def one(r):
+            t = reads[r, :ln[r]].tobytes().decode()
+            return (int(rr[r]), t) if with_rows else t
+        return [[[one(r) for r in range(int(first[q * S + s]), int(first[q * S + s + 1]))] for s in range(S)] for q in range(Q)]
+
+    def gt_count(self, queries, pos, k, skip=0, max_interval_size=0):
+        """[query][shard] -> the number of those reads (rsbwt_set_gt_count)"""
+        text, off = self._var_text(queries)
+        Q, S = len(queries), len(self.shards)
+        p = np.ascontiguousarray(pos, np.uint64)
+        out = np.zeros(Q * S, np.uint64)
+        check(lib().rsbwt_set_gt_count(self._s, _ptr(text), _ptr(off), Q, _ptr(p), k, skip, max_interval_size, _ptr(out)))
+        return out.reshape(Q, S)
+
+    @staticmethod
+    def gt_last_work():
+        """{legs, no_answer, narrow_steps, candidates, kept, extracted} of this thread's last gt call"""
+        w = np.zeros(6, np.uint64)
+        lib().rsbwt_set_gt_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return dict(zip(("legs", "no_answer", "narrow_steps", "candidates", "kept", "extracted"), (int(x) for x in w)))
 
     # -- BASELINE configs[3] / configs[4] over the set: per-shard results side by side, the way the front-end
     # concatenates its partitions' replies (src/service/server.cpp:199-261)

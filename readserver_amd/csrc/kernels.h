@@ -215,6 +215,44 @@ hipError_t launch_interval_cells(const shard_view *d_views, uint32_t S, const vo
                                  void *d_cellw, void *d_cellpos, void *d_temp, size_t temp_bytes, hipStream_t stream);
 hipError_t launch_interval_fill(const shard_view *d_views, uint32_t S, const void *d_pairs, size_t Q, const void *d_first, size_t cap,
                                 void *d_shard, void *d_rows, const void *d_cellpos, void *d_cell_rows, void *d_dest, hipStream_t stream);
+// gt_narrow.hip: SiteMatch's candidate legs (find_gt_reads, src/service/service.cpp:507-711).  A batch is its queries'
+// text back to back plus, per query, where it starts, its length and its site; a SLOT is one all-ACGT tile of one
+// query, an ITEM one leg of a slot (item = 2 * slot + leg).  nprev[i] says where the last symbol outside ACGT at or
+// before text position i lies: 1 + its index inside its query, 0 for none.
+struct gt_batch {
+    const char *text;
+    const uint32_t *nprev;
+    const uint64_t *q_off;
+    const uint32_t *q_len;
+    const uint64_t *q_pos;
+    const uint32_t *slot_query, *slot_tile;
+    size_t nitems;
+    uint32_t k, step;  // tile length; skip + 1
+    uint64_t M;        // max interval size
+};
+// a leg: the final string w[a:b) and its interval; label 0 = the tile itself (its interval is at or under the limit), 1 / 2 = the
+// first / second lengthened leg; a == 0xFFFFFFFF: no leg -- reserved = 1 when one was owed and the string could not be lengthened
+// any further (it would need a < 0 or b > L)
+struct gt_leg {
+    uint32_t a, b;
+    uint64_t lower, upper;
+    uint32_t label, reserved;
+};
+//   launch_gt_narrow: one lane per (item, shard): d_legs gt_leg[nshards][nitems], d_pairs {lower, upper}[nshards][nitems] as
+//     the interval-rows kernels take them (all ones for no leg); d_work[0] += LF steps taken while lengthening
+//   launch_gt_filter: the span filter over the legs' rows (launch_interval_fill's d_shard, launch_locate's d_offset and
+//     d_read_row, d_first u64[nitems + 1]) and their compaction: d_kept_rows gt_kept_row[total] receives one record per row
+//     kept, d_counters[0] of them in all, in no particular order (d_counters zeroed by the caller); d_counters[1] += rows
+//     whose walk did not end (offset UINT32_MAX)
+struct gt_kept_row {
+    uint32_t item, shard, offset;  // shard: the launch's number
+    uint32_t pending;              // 1: a LEFT row that stays unless its read is too short
+    uint64_t read_row;
+};
+hipError_t launch_gt_narrow(const shard_view *d_shards, uint32_t nshards, const gt_batch &bt, void *d_legs, void *d_pairs,
+                            unsigned long long *d_work, hipStream_t stream);
+hipError_t launch_gt_filter(const gt_batch &bt, const void *d_legs, const void *d_first, const void *d_shard_of, const void *d_offset,
+                            const void *d_read_row, uint64_t total, void *d_kept_rows, unsigned long long *d_counters, hipStream_t stream);
 // (SEL_SHIFT, sample_window, window_samples, window_psi_hint: line_format.h -- shared with the host-side layout test)
 // query / query_exactmatch (query.cpp:87-120) over extracted reads
 hipError_t launch_match_reads(const void *d_reads, const void *d_len, size_t n, uint32_t stride, const void *d_owner,

@@ -20,7 +20,10 @@
 #include <algorithm>
 #include <atomic>
 #include <new>
+#include <string>
 #include <thread>
+#include <unordered_set>
+#include <utility>
 #include <vector>
 
 #include "../../include/rsbwt.h"
@@ -1597,6 +1600,355 @@ int rsbwt_set_locate_var_capped(rsbwt_set_t *s, const char *text, const uint64_t
         locate_set_last_work(wk[0], wk[1]);
         return rc;
     });
+}
+
+// ---- SiteMatch candidates (gt_narrow.hip): find_gt_reads (src/service/service.cpp:507-711) over every shard ----
+namespace {
+// the calling thread's last gt call: legs, legs with no answer, LF steps spent lengthening, candidate rows, rows kept by
+// the device's filter, reads extracted
+thread_local uint64_t gt_last_work[6] = {0, 0, 0, 0, 0, 0};
+
+// the host side of a batch (kernels.h, gt_batch): the queries that can have tiles, their all-ACGT tiles as slots
+struct gt_plan {
+    std::vector<uint64_t> q_off, q_pos;
+    std::vector<uint32_t> q_len, nprev, slot_query, slot_tile;
+    size_t nitems = 0;
+    uint32_t k = 0, step = 0;
+    uint64_t M = 0;
+    size_t text_len = 0;
+};
+struct gt_row {  // a row the device's filter kept
+    uint32_t item, shard, offset;  // shard: the set's number
+    uint32_t pending;              // a LEFT row: its read's length decides
+    uint64_t read_row;
+};
+struct gt_group_out {
+    std::vector<gt_leg> legs;  // [S_g][nitems]
+    std::vector<gt_row> rows;
+    uint64_t steps = 0, candidates = 0, kept = 0;
+};
+
+int gt_make_plan(const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, int32_t k, int32_t skip, uint64_t M, gt_plan *pl) {
+    pl->M = M ? M : 10000;  // service.cpp:85, max_interval_size
+    pl->text_len = Q ? (size_t)(off[Q] - off[0]) : 0;
+    pl->q_off.resize(Q);
+    pl->q_pos.assign(pos, pos + Q);
+    pl->q_len.resize(Q);
+    pl->nprev.assign(pl->text_len, 0);
+    const char *t0 = Q ? text + off[0] : nullptr;
+    for (size_t q = 0; q < Q; ++q) {
+        const uint64_t L = off[q + 1] - off[q];
+        if (L > 0x7FFFFFFFull) return fail(RSBWT_EINVAL, "query %zu: %llu symbols, at most 2^31 - 1", q, (unsigned long long)L);
+        if (q >= 0xFFFFFFFFull) return fail(RSBWT_EINVAL, "at most 2^32 - 1 queries per call");
+        const uint64_t base = off[q] - off[0];
+        pl->q_off[q] = base;
+        pl->q_len[q] = (uint32_t)L;
+        uint32_t last = 0;
+        for (uint64_t i = 0; i < L; ++i) {
+            const char ch = t0[base + i];
+            if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T') last = (uint32_t)i + 1u;
+            pl->nprev[base + i] = last;
+        }
+        if (k <= 0 || skip < 0 || L < (uint64_t)k || pos[q] > L) continue;
+        const uint64_t step = (uint64_t)skip + 1;
+        for (uint64_t i = 0; i <= (L - (uint64_t)k) / step; ++i) {
+            const uint64_t s0 = step * i, e0 = s0 + (uint64_t)k;
+            if (pl->nprev[base + e0 - 1] > s0) continue;  // don't bother with N (:513)
+            pl->slot_query.push_back((uint32_t)q);
+            pl->slot_tile.push_back((uint32_t)i);
+        }
+    }
+    pl->k = k > 0 ? (uint32_t)k : 0;
+    pl->step = skip >= 0 ? (uint32_t)skip + 1u : 1u;
+    pl->nitems = 2 * pl->slot_query.size();
+    if (pl->nitems >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu tile legs in one call: at most 2^31", pl->nitems);
+    return RSBWT_OK;
+}
+
+// One device group's share: the batch goes up once, every (item, shard of the group) is narrowed by one launch, and --
+// for the read calls -- the legs' rows are made, walked and filtered where they are; what comes back is the legs and
+// the rows the filter kept.
+int gt_group_run(rsbwt_set_t *s, dev_group *g, const gt_plan &pl, const char *t0, bool want_rows, gt_group_out *out) {
+    group_call gc(g, true);
+    if (gc.rc) return gc.rc;
+    hipStream_t st = gc.st;
+    const uint32_t S = (uint32_t)g->idx.size();
+    const size_t Q = pl.q_off.size(), slots = pl.slot_query.size(), N = pl.nitems, cells = (size_t)S * N;
+    const size_t a_text = al256(pl.text_len + 1), a_np = al256(pl.text_len * 4 + 4), a_q8 = al256(Q * 8), a_q4 = al256(Q * 4), a_s4 = al256(slots * 4),
+                 a_legs = al256(cells * sizeof(gt_leg)), a_pairs = al256(cells * 16), a_i = al256((N + 1) * 8),
+                 tmp_bytes = interval_rows_scan_bytes(N + 1);
+    hipError_t e = g->scratch.take(a_text + a_np + 2 * a_q8 + a_q4 + 2 * a_s4 + a_legs + a_pairs + 3 * a_i + 512 + tmp_bytes + 256, st, &gc.la);
+    if (e != hipSuccess) return fail_hip(e, "scratch for the SiteMatch legs");
+    uint8_t *d_text = (uint8_t *)gc.la.p, *d_np = d_text + a_text, *d_qoff = d_np + a_np, *d_qpos = d_qoff + a_q8, *d_qlen = d_qpos + a_q8,
+            *d_sq = d_qlen + a_q4, *d_stile = d_sq + a_s4, *d_legs = d_stile + a_s4, *d_pairs = d_legs + a_legs, *d_matches = d_pairs + a_pairs,
+            *d_keptq = d_matches + a_i, *d_first = d_keptq + a_i, *d_over = d_first + a_i, *d_wk = d_over + 256, *d_tmp = d_wk + 256;
+    if (pl.text_len) {
+        HIP_OK(hipMemcpyAsync(d_text, t0, pl.text_len, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_np, pl.nprev.data(), pl.text_len * 4, hipMemcpyHostToDevice, st));
+    }
+    HIP_OK(hipMemcpyAsync(d_qoff, pl.q_off.data(), Q * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_qpos, pl.q_pos.data(), Q * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_qlen, pl.q_len.data(), Q * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_sq, pl.slot_query.data(), slots * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_stile, pl.slot_tile.data(), slots * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(d_wk, 0, 256, st));
+    gt_batch bt;
+    bt.text = (const char *)d_text;
+    bt.nprev = (const uint32_t *)d_np;
+    bt.q_off = (const uint64_t *)d_qoff;
+    bt.q_len = (const uint32_t *)d_qlen;
+    bt.q_pos = (const uint64_t *)d_qpos;
+    bt.slot_query = (const uint32_t *)d_sq;
+    bt.slot_tile = (const uint32_t *)d_stile;
+    bt.nitems = N;
+    bt.k = pl.k;
+    bt.step = pl.step;
+    bt.M = pl.M;
+    unsigned long long *wk = (unsigned long long *)d_wk;  // [0] lengthening steps, [1] rows kept, [2] rows whose walk did not end
+    e = launch_gt_narrow(g->d_views, S, bt, d_legs, d_pairs, wk, st);
+    if (e != hipSuccess) return fail_hip(e, "SiteMatch narrowing kernel launch");
+    out->legs.resize(cells);
+    HIP_OK(hipMemcpyAsync(out->legs.data(), d_legs, cells * sizeof(gt_leg), hipMemcpyDeviceToHost, st));
+    uint64_t total = 0;
+    if (want_rows) {
+        e = launch_interval_totals(g->d_views, S, d_pairs, N, 0, d_matches, d_keptq, d_first, d_over, d_tmp, tmp_bytes, st);
+        if (e != hipSuccess) return fail_hip(e, "interval-rows kernels");
+        HIP_OK(hipMemcpyAsync(&total, d_first + N * 8, 8, hipMemcpyDeviceToHost, st));
+    }
+    HIP_OK(hipStreamSynchronize(st));
+    unsigned long long hwk[3] = {0, 0, 0};
+    if (total >= (1ull << 31)) return fail(RSBWT_ERANGE, "%llu candidate rows in one call: at most 2^31", (unsigned long long)total);
+    if (total != 0) {
+        const size_t a8 = al256(total * 8), a4 = al256(total * 4), a_rec = al256(total * sizeof(gt_kept_row));
+        e = g->scratch.take(2 * a8 + 2 * a4 + a_rec, st, &gc.lb);
+        if (e != hipSuccess) return fail(RSBWT_ENOMEM, "%llu candidate rows do not fit the device's free memory: %s", (unsigned long long)total, hipGetErrorString(e));
+        uint8_t *d_rows = (uint8_t *)gc.lb.p, *d_rr = d_rows + a8, *d_sh = d_rr + a8, *d_of = d_sh + a4, *d_rec = d_of + a4;
+        e = launch_interval_fill(g->d_views, S, d_pairs, N, d_first, (size_t)total, d_sh, d_rows, nullptr, nullptr, nullptr, st);
+        if (e == hipSuccess) e = launch_locate(g->scratch, g->d_views, S, d_sh, d_rows, (size_t)total, 0, d_rr, nullptr, d_of, nullptr, g->num_cus, st);
+        if (e == hipSuccess) e = launch_gt_filter(bt, d_legs, d_first, d_sh, d_of, d_rr, total, d_rec, wk + 1, st);
+        if (e != hipSuccess) return fail_hip(e, "row expansion, locate and filter kernel launches");
+        // the counters first (they size the copy), then the kept rows' records and nothing else
+        HIP_OK(hipMemcpyAsync(hwk, d_wk, sizeof hwk, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        if (hwk[2] != 0)
+            return fail(RSBWT_EINVAL, "%llu candidate rows whose walk to their read's start does not end (a corrupt index, or a read longer than 2^20 symbols)",
+                        hwk[2]);
+        if (hwk[1] > total) return fail(RSBWT_EHIP, "the row filter kept %llu of %llu rows", hwk[1], (unsigned long long)total);
+        std::vector<gt_kept_row> kr((size_t)hwk[1]);
+        if (!kr.empty()) {
+            HIP_OK(hipMemcpyAsync(kr.data(), d_rec, kr.size() * sizeof(gt_kept_row), hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+        }
+        out->rows.reserve(kr.size());
+        for (const gt_kept_row &r : kr) out->rows.push_back(gt_row{r.item, (uint32_t)g->idx[r.shard], r.offset, r.pending, r.read_row});
+    } else {
+        HIP_OK(hipMemcpyAsync(hwk, d_wk, 16, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+    }
+    out->steps = hwk[0];
+    out->candidates = total;
+    out->kept = hwk[1];
+    return RSBWT_OK;
+}
+
+// reads[q * S + p]: the (read_row, string) pairs of query q in shard p, ascending read_row, a string once (null: legs only)
+typedef std::vector<std::vector<std::pair<uint64_t, std::string>>> gt_reads_t;
+
+int gt_call(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, int32_t k, int32_t skip, uint64_t M,
+            std::vector<rsbwt_gt_leg> *legs, std::vector<uint64_t> *legs_first, gt_reads_t *reads, uint32_t stride) {
+    for (uint64_t &w : gt_last_work) w = 0;
+    if (!s || (Q && (!off || !pos))) return fail(RSBWT_EINVAL, "null argument");
+    if (Q && !text && off[Q] != off[0]) return fail(RSBWT_EINVAL, "null argument");
+    for (size_t q = 0; q < Q; ++q)
+        if (off[q] > off[q + 1]) return fail(RSBWT_EINVAL, "query %zu: offsets not ascending", q);
+    const size_t S = s->shards.size();
+    for (rsbwt_t *h : s->shards) {
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
+        if (reads && !rsbwt_opened_for_reads(h)) return fail(RSBWT_EINVAL, "SiteMatch reads need shards opened with RSBWT_OPEN_READS");
+    }
+    if (S > 65535) return fail(RSBWT_EINVAL, "%zu shards: at most 65535", S);
+    if (legs_first) legs_first->assign(Q + 1, 0);
+    if (reads) reads->assign(Q * S, {});
+    gt_plan pl;
+    int rc = gt_make_plan(text, off, Q, pos, k, skip, M, &pl);
+    if (rc) return rc;
+    if (pl.nitems == 0) return RSBWT_OK;
+    const size_t N = pl.nitems;
+    std::vector<gt_group_out> outs(s->groups.size());
+    rc = for_each_group(s, [&](size_t gi) -> int { return gt_group_run(s, s->groups[gi], pl, text + off[0], reads != nullptr, &outs[gi]); });
+    if (rc) return rc;
+    // ---- the legs in (query, tile, leg, shard) order; where shard p's record of an item lies
+    std::vector<std::pair<size_t, size_t>> where(S);  // shard of the set -> (group, shard of the group)
+    for (size_t gi = 0; gi < s->groups.size(); ++gi)
+        for (size_t j = 0; j < s->groups[gi]->idx.size(); ++j) where[s->groups[gi]->idx[j]] = {gi, j};
+    auto rec_of = [&](size_t p, size_t item) -> const gt_leg & { return outs[where[p].first].legs[where[p].second * N + item]; };
+    uint64_t nlegs = 0, nnone = 0;
+    // (a tile is one leg in one shard and two in another: the order is by the leg's label, not by the item that made it)
+    std::vector<rsbwt_gt_leg> of_tile;
+    for (size_t slot = 0; slot < N / 2; ++slot) {
+        const uint32_t q = pl.slot_query[slot];
+        of_tile.clear();
+        for (size_t item = 2 * slot; item < 2 * slot + 2; ++item)
+            for (size_t p = 0; p < S; ++p) {
+                const gt_leg &r = rec_of(p, item);
+                if (r.a == 0xFFFFFFFFu) nnone += r.reserved;
+                else of_tile.push_back(rsbwt_gt_leg{q, pl.slot_tile[slot], r.label, (uint32_t)p, r.a, r.b, 0u, r.lower, r.upper});
+            }
+        std::sort(of_tile.begin(), of_tile.end(),
+                  [](const rsbwt_gt_leg &x, const rsbwt_gt_leg &y) { return x.leg != y.leg ? x.leg < y.leg : x.shard < y.shard; });
+        nlegs += of_tile.size();
+        if (legs_first) (*legs_first)[q + 1] += of_tile.size();
+        if (legs) legs->insert(legs->end(), of_tile.begin(), of_tile.end());
+    }
+    if (legs_first)
+        for (size_t q = 0; q < Q; ++q) (*legs_first)[q + 1] += (*legs_first)[q];
+    gt_last_work[0] = nlegs;
+    gt_last_work[1] = nnone;
+    for (const gt_group_out &o : outs) {
+        gt_last_work[2] += o.steps;
+        gt_last_work[3] += o.candidates;
+        gt_last_work[4] += o.kept;
+    }
+    if (!reads) return RSBWT_OK;
+    // ---- every distinct read of a kept row extracted once (kmer_reads.hip's rule for a read longer than the stride: it is
+    // fetched again at 64 KB and still counts as one read extracted)
+    std::vector<std::pair<uint32_t, uint64_t>> ids;
+    for (const gt_group_out &o : outs)
+        for (const gt_row &r : o.rows) ids.push_back({r.shard, r.read_row});
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+    const size_t R = ids.size();
+    if (R == 0) return RSBWT_OK;
+    std::vector<uint32_t> shard_of(R), rlen(R);
+    std::vector<uint64_t> rows(R);
+    for (size_t i = 0; i < R; ++i) {
+        shard_of[i] = ids[i].first;
+        rows[i] = ids[i].second;
+    }
+    std::vector<std::string> str(R);
+    {
+        std::vector<char> buf(R * (size_t)stride);
+        rc = rsbwt_set_extract_body(s, shard_of.data(), rows.data(), R, buf.data(), stride, rlen.data(), nullptr);
+        if (rc) return rc;
+        gt_last_work[5] += R;
+        std::vector<size_t> over;
+        for (size_t i = 0; i < R; ++i) {
+            if (rlen[i] == 0xFFFFFFFFu) over.push_back(i);
+            else str[i].assign(buf.data() + i * (size_t)stride, rlen[i]);
+        }
+        if (!over.empty()) {
+            const uint32_t wide = 65536;
+            std::vector<uint32_t> osh(over.size()), olen(over.size());
+            std::vector<uint64_t> orow(over.size());
+            for (size_t i = 0; i < over.size(); ++i) {
+                osh[i] = shard_of[over[i]];
+                orow[i] = rows[over[i]];
+            }
+            std::vector<char> obuf(over.size() * (size_t)wide);
+            rc = rsbwt_set_extract_body(s, osh.data(), orow.data(), over.size(), obuf.data(), wide, olen.data(), nullptr);
+            if (rc) return rc;
+            for (size_t i = 0; i < over.size(); ++i) {
+                if (olen[i] == 0xFFFFFFFFu)
+                    return fail(RSBWT_EINVAL, "shard %u row %llu: a read longer than %u symbols (or a walk that does not end)", osh[i],
+                                (unsigned long long)orow[i], wide);
+                str[over[i]].assign(obuf.data() + i * (size_t)wide, olen[i]);
+            }
+        }
+    }
+    // ---- a LEFT row stays iff pos - end <= (|postfix| - k) + 4, unsigned as the reference takes it (:538); then each
+    // (query, shard)'s reads by read_row, a string once
+    for (const gt_group_out &o : outs)
+        for (const gt_row &r : o.rows) {
+            const size_t ri = (size_t)(std::lower_bound(ids.begin(), ids.end(), std::make_pair(r.shard, r.read_row)) - ids.begin());
+            const uint32_t q = pl.slot_query[r.item >> 1];
+            if (r.pending) {
+                const uint64_t end = rec_of(r.shard, r.item).b, postfix = (uint64_t)str[ri].size() - r.offset;
+                if (pl.q_pos[q] - end > postfix - pl.k + 4ull) continue;
+            }
+            (*reads)[(size_t)q * S + r.shard].push_back({r.read_row, std::string()});
+            (*reads)[(size_t)q * S + r.shard].back().second = str[ri];
+        }
+    for (auto &cell : *reads) {
+        std::sort(cell.begin(), cell.end());
+        std::vector<std::pair<uint64_t, std::string>> kept;
+        std::unordered_set<std::string> seen;
+        for (auto &pr : cell)
+            if (seen.insert(pr.second).second) kept.push_back(std::move(pr));
+        cell.swap(kept);
+    }
+    return RSBWT_OK;
+}
+}  // namespace
+
+int rsbwt_set_gt_legs(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, int32_t k, int32_t skip, uint64_t M,
+                      uint64_t *first, rsbwt_gt_leg *legs, size_t cap, size_t *nlegs) {
+    return guarded("rsbwt_set_gt_legs", [&]() -> int {
+        if (!nlegs || (!first && Q)) return fail(RSBWT_EINVAL, "null argument");
+        *nlegs = 0;
+        std::vector<rsbwt_gt_leg> out;
+        std::vector<uint64_t> fq;
+        const int rc = gt_call(s, text, off, Q, pos, k, skip, M, &out, &fq, nullptr, 0);
+        if (rc) return rc;
+        if (first) memcpy(first, fq.data(), (Q + 1) * 8);
+        *nlegs = out.size();
+        if (out.size() > cap) return fail(RSBWT_ERANGE, "%zu legs, room for %zu", out.size(), cap);
+        if (out.empty()) return RSBWT_OK;
+        if (!legs) return fail(RSBWT_EINVAL, "null argument");
+        memcpy(legs, out.data(), out.size() * sizeof(rsbwt_gt_leg));
+        return RSBWT_OK;
+    });
+}
+
+int rsbwt_set_gt_reads(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, int32_t k, int32_t skip, uint64_t M,
+                       uint64_t *first, char *reads, uint32_t read_stride, uint32_t *read_len, uint64_t *read_row, size_t cap_reads,
+                       size_t *nreads) {
+    return guarded("rsbwt_set_gt_reads", [&]() -> int {
+        if (!nreads || (!first && Q)) return fail(RSBWT_EINVAL, "null argument");
+        *nreads = 0;
+        if (read_stride == 0) return fail(RSBWT_EINVAL, "read_stride must be positive");
+        gt_reads_t res;
+        const int rc = gt_call(s, text, off, Q, pos, k, skip, M, nullptr, nullptr, &res, std::max<uint32_t>(read_stride, 256));
+        if (rc) return rc;
+        size_t total = 0;
+        for (size_t c = 0; c < res.size(); ++c) {
+            first[c] = total;
+            total += res[c].size();
+        }
+        if (first) first[res.size()] = total;
+        *nreads = total;
+        if (total > cap_reads) return fail(RSBWT_ERANGE, "%zu reads, room for %zu", total, cap_reads);
+        if (total == 0) return RSBWT_OK;
+        if (!reads || !read_len) return fail(RSBWT_EINVAL, "null argument");
+        size_t r = 0;
+        for (const auto &cell : res)
+            for (const auto &pr : cell) {
+                if (pr.second.size() > read_stride) {
+                    read_len[r] = 0xFFFFFFFFu;
+                } else {
+                    memcpy(reads + r * (size_t)read_stride, pr.second.data(), pr.second.size());
+                    read_len[r] = (uint32_t)pr.second.size();
+                }
+                if (read_row) read_row[r] = pr.first;
+                ++r;
+            }
+        return RSBWT_OK;
+    });
+}
+
+int rsbwt_set_gt_count(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, int32_t k, int32_t skip, uint64_t M,
+                       uint64_t *counts) {
+    return guarded("rsbwt_set_gt_count", [&]() -> int {
+        if (!counts && Q) return fail(RSBWT_EINVAL, "null argument");
+        gt_reads_t res;
+        const int rc = gt_call(s, text, off, Q, pos, k, skip, M, nullptr, nullptr, &res, 256);
+        if (rc) return rc;
+        for (size_t c = 0; c < res.size(); ++c) counts[c] = res[c].size();
+        return RSBWT_OK;
+    });
+}
+
+void rsbwt_set_gt_last_work(uint64_t *work6) {
+    if (work6) memcpy(work6, gt_last_work, sizeof gt_last_work);
 }
 
 static size_t hits_1mm_scratch_one(const rsbwt_set_t *s, size_t m, uint32_t k) {

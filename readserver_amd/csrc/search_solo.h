@@ -7,7 +7,9 @@
 // nearly every pass, and the launch falls short of the request rate the memory system can take.
 // Here a lane owns a whole search: it looks up Occ(b, lower - 1); when upper lies within the symbols
 // the same line holds (the usual case once the interval is narrow) Occ(b, upper) is ranked out of the
-// same staged line in the same pass, otherwise upper is a lookup of its own in the next pass.  64
+// same staged line in the same pass (its own pieces, or the window's spill chunk); an upper further on
+// in the same window goes on from that line into the window's continuation, and only an upper in
+// another window is a lookup of its own in the next pass -- a step fetches no line of a window twice.  64
 // searches per wave keep 64 lookups in flight whatever the intervals' width; a wide interval costs
 // two passes per step instead of one, which a request-bound launch does not feel.
 // Same start records, results, trace and counters as search_lines_kernel.
@@ -181,6 +183,9 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
         uint32_t sub = 0;
         uint64_t occL = 0, cacc = 0;
         uint32_t cont = 0, cblk = 0, cdw = 0, co = 0, tries = 0, w = 0;
+        // (bit 31 of `tries`, set when the lookup of lower - 1 starts: the step's upper lies in the same window, so what
+        // that lookup stages serves upper as well)
+        constexpr uint32_t SAME_WINDOW = 1u << 31;
         // WALK: Occ of the three other bases at lower - 1 (kept until the step's upper lookup is in too) and whether
         // both lookups of the step found their position among a staged line's own pieces
         uint64_t altL0 = 0, altL1 = 0, altL2 = 0, altU0 = 0, altU1 = 0, altU2 = 0;
@@ -412,6 +417,7 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                     o = pin + 1u;
                     if (line >= nlines) line = 0;  // never for p < n; keeps a bad position from faulting
                     if (COUNT_WORK) w_occ += 1;
+                    if (sub == 0u) tries = hi - p <= (uint64_t)(S - o) ? SAME_WINDOW : 0u;  // (an interval that is none, hi < lo - 1, wraps: not set)
                 }
             }
             const bool looking = stepping && !no_fetch;
@@ -430,13 +436,16 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
 
             // ---- Occ(b, p) out of this lane's staged line (RLEBWT::getOcc, rlebwt.cpp:268-301)
             bool do_scan = false, own_line = false;
-            uint64_t base = 0, cnt_b = 0;
-            uint32_t dw = HDR_DWORDS, rem = 0, oe_here = 0;
+            uint64_t base = 0;
+            uint32_t dw = HDR_DWORDS, rem = 0;
             uint32_t s1 = 0, s2 = 0, s3 = 0, span = 0, hb = 0;
             const sym_tab stab = make_sym_tab(b);  // v_perm_b32 table of the symbol (rank_device.h)
+            const uint32_t cont_in = cont;  // what this pass's line is: 0 = a window line, else the continuation fetched
+            uint32_t more = 0;  // how the window goes on past the staged line's own pieces: KIND_FAR / KIND_CHUNK (cblk, cdw, cacc set), 0 = it does not
             if (looking) {
                 if (cont != KIND_CHUNK) {
-                    const uint32_t oe = cont ? co : o;
+                    if (cont == 0u) co = o;  // (co: the position's offset in the line being read, window line or continuation)
+                    const uint32_t oe = co;
                     const uint2 cw = *reinterpret_cast<const lds_u2 *>(SOLO_MINE(2u * (b - 1u)));
                     const uint4 h0 = *reinterpret_cast<const lds_u4 *>(SOLO_MINE(0));
                     const uint64_t cnt = ((uint64_t)(cw.y & 0xFFu) << 32) | cw.x;
@@ -446,6 +455,19 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                     s3 = s2 + (m1 & 0x3FFu);
                     span = s3 + ((m1 >> 10) & 0x3FFu);
                     const uint32_t kind = (m1 >> 20) & 3u;
+                    // where a lookup that does not end among this line's pieces goes on -- this one, or upper's after it
+                    cacc = cnt;
+                    if (kind == KIND_FAR) {
+                        cblk = *SOLO_MINE(LINE_DWORDS - 1u);
+                        if (cblk >= nlines) cblk = 0;  // never for a built index
+                        more = KIND_FAR;
+                    } else if (kind == KIND_CHUNK && cont == 0u) {
+                        const uint32_t m2 = *SOLO_MINE(5) >> 8, m3 = *SOLO_MINE(7) >> 8;
+                        cdw = 2u * (((m2 >> 22) & 3u) | (((m3 >> 22) & 3u) << 2));
+                        cblk = (w >> GROUP_SHIFT) * (GROUP + 1u) + GROUP;
+                        if (cblk >= nlines) cblk = 0;  // never for p < n
+                        more = KIND_CHUNK;
+                    }
                     if (oe <= span) {
                         const uint32_t cq = (oe > s1 ? 1u : 0u) + (oe > s2 ? 1u : 0u) + (oe > s3 ? 1u : 0u);
                         const uint32_t start = cq == 0u ? 0u : cq == 1u ? s1 : cq == 2u ? s2 : s3;
@@ -462,20 +484,8 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                         rem = oe - start;
                         do_scan = true;
                         own_line = true;  // the staged line's own pieces hold the position: they may hold upper too
-                        oe_here = oe;
-                        cnt_b = cnt;
-                    } else if (kind == KIND_FAR) {
-                        cblk = *SOLO_MINE(LINE_DWORDS - 1u);
-                        if (cblk >= nlines) cblk = 0;  // never for a built index
-                        cont = KIND_FAR;
-                        co = oe - span;
-                    } else if (kind == KIND_CHUNK && cont == 0u) {
-                        const uint32_t m2 = *SOLO_MINE(5) >> 8, m3 = *SOLO_MINE(7) >> 8;
-                        cacc = cnt;
-                        cdw = 2u * (((m2 >> 22) & 3u) | (((m3 >> 22) & 3u) << 2));
-                        cblk = (w >> GROUP_SHIFT) * (GROUP + 1u) + GROUP;
-                        if (cblk >= nlines) cblk = 0;  // never for p < n
-                        cont = KIND_CHUNK;
+                    } else if (more != 0u) {
+                        cont = more;
                         co = oe - span;
                     } else {  // a position beyond what the index holds: never for p < n
                         base = cnt;
@@ -492,7 +502,7 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                     do_scan = true;
                 }
                 // a window has at most 33 lines: the bound only guards against a corrupt chain
-                if (!do_scan && ++tries > 72u) do_scan = true;
+                if (!do_scan && (++tries & ~SAME_WINDOW) > 72u) do_scan = true;
             }
             uint64_t occ = 0;
             {
@@ -506,15 +516,20 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                     occ = (occ + (((uint64_t)q * 0x9E3779B97F4A7C15ull) >> (23u + (((uint32_t)q + (uint32_t)j) & 31u)))) & ((1ull << 41) - 1ull);
 #endif
             }
-            // ---- upper out of the same line: lower - 1 was found among the line's own pieces, and
-            // upper lies d symbols further on, still among them
+            // ---- upper out of the same line: lower - 1 was found among the line's own pieces, and upper lies d symbols
+            // further on, still among them (`second`) -- or past them in the same window: its lookup goes on from the header
+            // already staged, as a first lookup's does, instead of starting at the window line again.  lower - 1 found in
+            // the window's spill chunk (`second_chunk`): the chunk holds all the window has past its line's own pieces
+            // (line_format.h, build_group: `first && ends`), at most 24 of them, so an upper of the same window is ranked
+            // off it in this pass.  A step fetches each line of a window once; only an upper in ANOTHER window starts anew.
             bool step_done = false;
             uint64_t occU = 0;
-            bool second = false;
+            bool second = false, second_chunk = false;
             uint32_t oh = 0;
             // WALK: this pass's lookup found its position among the staged line's own pieces (the three other bases can be
             // ranked off the same line: for lower - 1 or for upper), or came out of a continuation line (they cannot)
             bool ev1 = false, ev1_is_L = false;
+            const uint32_t co_in = co;  // (the position this pass looked up, as an offset in its line)
             if (WALK && do_scan && (uint32_t)j < trace_n) {
                 if (own_line) {
                     ev1 = true;
@@ -524,15 +539,23 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                 }
             }
             if (do_scan) {
+                const bool same_w = (tries & SAME_WINDOW) != 0u;
                 cont = 0;
                 tries = 0;
                 if (sub == 0u) {
                     occL = occ;
                     sub = 1u;
                     const uint64_t d = hi - (lo - 1ull);  // >= 1 for a live interval
-                    if (own_line && d <= (uint64_t)(span - oe_here)) {
+                    if (own_line && d <= (uint64_t)(span - co)) {
                         second = true;
-                        oh = oe_here + (uint32_t)d;
+                        oh = co + (uint32_t)d;
+                    } else if (own_line && same_w && more != 0u) {
+                        cont = more;
+                        co = co + (uint32_t)d - span;
+                        if (COUNT_WORK) w_occ += 1;
+                    } else if (cont_in == KIND_CHUNK && same_w) {
+                        second_chunk = true;
+                        oh = co + (uint32_t)d;
                     }
                 } else {
                     occU = occ;
@@ -549,14 +572,14 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                 const uint2 x2 = *reinterpret_cast<const lds_u2 *>(SOLO_MINE(qd + 4u));
                 const uint32_t e6[6] = {x0.x, x0.y, x1.x, x1.y, x2.x, x2.y};
                 const uint32_t m = matched24_tab(e6, stab);
-                const uint32_t dw2 = HDR_DWORDS + 6u * cq;
-                const uint2 y0 = *reinterpret_cast<const lds_u2 *>(SOLO_MINE(dw2));
-                const uint2 y1 = *reinterpret_cast<const lds_u2 *>(SOLO_MINE(dw2 + 2u));
-                const uint2 y2 = *reinterpret_cast<const lds_u2 *>(SOLO_MINE(dw2 + 4u));
+                const uint32_t dw2 = second_chunk ? dw : HDR_DWORDS + 6u * cq;  // (the chunk's pieces: where lower - 1 was ranked)
+                const uint2 y0 = *reinterpret_cast<const lds_u2 *>(SOLO_MINE(dw2 & 31u));
+                const uint2 y1 = *reinterpret_cast<const lds_u2 *>(SOLO_MINE((dw2 + 2u) & 31u));
+                const uint2 y2 = *reinterpret_cast<const lds_u2 *>(SOLO_MINE((dw2 + 4u) & 31u));
                 const uint32_t r6[6] = {y0.x, y0.y, y1.x, y1.y, y2.x, y2.y};
-                const uint32_t sc = rank24(r6, stab, b, second ? oh - start : 0u);
-                if (second) {
-                    occU = cnt_b + (cq >= 2u ? hb : 0u) + ((cq & 1u) ? m : 0u) + sc;
+                const uint32_t sc = rank24(r6, stab, b, second ? oh - start : second_chunk ? oh : 0u);
+                if (second || second_chunk) {
+                    occU = second ? cacc + (cq >= 2u ? hb : 0u) + ((cq & 1u) ? m : 0u) + sc : base + sc;
                     step_done = true;
                     if (COUNT_WORK) w_occ += 1;
                 }
@@ -575,7 +598,7 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                     const bool want = ev == 0u ? ev1 : (second && (uint32_t)j < trace_n);
                     if (__builtin_amdgcn_ballot_w64(want) == 0ull) continue;
                     uint64_t t3[3];
-                    staged_occ_alts(Lrow, hh, want ? (ev == 0u ? oe_here : oh) : 1u, b - 1u, t3);
+                    staged_occ_alts(Lrow, hh, want ? (ev == 0u ? co_in : oh) : 1u, b - 1u, t3);
                     if (want) {
                         if (ev == 0u && ev1_is_L) { altL0 = t3[0]; altL1 = t3[1]; altL2 = t3[2]; }
                         else { altU0 = t3[0]; altU1 = t3[1]; altU2 = t3[2]; }

@@ -18,15 +18,17 @@
 // workgroup): a lane's result is 16 bytes at its query's place, and lanes finish at passes of their own -- 8e7 scattered
 // 16-byte stores per headline launch, 6.6e7 EA write requests (profiles/r05_pmc_search_kernel.json).  A wave draws its
 // queries in order, so the 8 results of one 128-byte line of the result array all come from ONE wave, a few passes
-// apart: they are collected in LDS -- RES_BUFS buffers per wave, a group of 8 consecutive queries (g = q >> 3) in buffer
-// g mod RES_BUFS if that was free when the group's first query was drawn -- and the lane that brings the last one in (an
-// LDS counter per buffer) has lanes 0..7 store the line whole.  A group whose buffer was still taken is not staged: its
+// apart: they are collected in LDS -- RES_BUFS buffers per wave, a group of 8 consecutive queries (g = q >> 3) in ANY
+// buffer that was free when the group's first query was drawn (the groups that begin among a pass's draws take the free
+// buffers in order; a lane keeps its query's buffer number with the query) -- and the lane that brings the last one in
+// (an LDS counter per buffer) has lanes 0..7 store the line whole.  A group that found no buffer free is not staged: its
 // lanes store as before.  2 KB per wave in all: with the line slots exactly the 160 KB of a CU at four workgroups.
 // A staged result is 8 bytes, {lower:40, width:24}: every interval the search produces has upper = lower + width - 1
 // (mod 2^64) -- a live one, an empty one after a step (width 0), the invalid (1, 0), the wrapped (0, 2^64 - 1) -- so
 // the flush rebuilds {lower, upper} exactly; 28 buffers of 64 bytes and their {tag, results still out} fit where 15
-// lines of 16-byte results did.  A result that does not fit (width >= 2^24 - 1, lower >= 2^40) is stored by its own lane
-// as an unstaged one is, and its slot says so (width RES_ESCAPED): the flush leaves that place alone.
+// lines of 16-byte results did (the tag is no longer looked at: a buffer is known by its number).  A result that does
+// not fit (width >= 2^24 - 1, lower >= 2^40) is stored by its own lane as an unstaged one is, and its slot says so
+// (width RES_ESCAPED): the flush leaves that place alone.
 //
 // FUSED (a single shard behind a k-mer table, k <= 32, no trace): the kernel computes the start records itself -- no
 // start-record launch before it, no 16 bytes written and read back per search.  The record of a search is its k-mer
@@ -63,15 +65,16 @@ constexpr uint32_t SOLO_COUNT_UNSTAGED = 8u;  // `pairs` bit 3 (counting launche
 constexpr uint32_t RES_WAVE_LDS = 2048u;      // a wave's share of the staged results' LDS
 constexpr uint32_t SOLO_RESULTS_LDS = WG_WAVES * RES_WAVE_LDS;
 constexpr uint32_t RES_SLOT_BYTES = 8u;       // a staged result: {lower:40, width:24}
-constexpr uint32_t RES_STATE_BYTES = 8u;      // a buffer's {tag, results still out}
+constexpr uint32_t RES_STATE_BYTES = 8u;      // a buffer's {unused, results still out}
 constexpr uint32_t RES_BUFS = RES_WAVE_LDS / (8u * RES_SLOT_BYTES + RES_STATE_BYTES);  // buffers per wave (8 results each)
 static_assert(RES_BUFS * (8u * RES_SLOT_BYTES + RES_STATE_BYTES) <= RES_WAVE_LDS, "a wave's buffers and their state fit its 2 KB");
 static_assert(RES_WAVE_LDS == 2048u && RES_BUFS == 28u, "2 KB per wave: with the line slots a CU's 160 KB at four workgroups");
-static_assert(RES_BUFS >= 9u && RES_BUFS <= 64u, "a lane per buffer claims; at most 9 groups begin among a pass's 64 draws");
+static_assert(RES_BUFS >= 9u && RES_BUFS <= 32u, "the free buffers are a 32-bit mask; at most 9 groups begin among a pass's 64 draws");
+constexpr uint32_t RES_NONE = 0xFFu;          // a query's buffer number when its group found none free
 constexpr uint32_t RES_WIDTH_BITS = 24u;
 constexpr uint32_t RES_ESCAPED = (1u << RES_WIDTH_BITS) - 1u;  // the slot's width when its result left by the lane's own store
 
-// The staged results pass from lane to lane through plain LDS accesses (the claiming lanes' tags and counts to the
+// The staged results pass from lane to lane through plain LDS accesses (the claiming lanes' counts to the
 // lanes whose searches end; their slots to lanes 0..7 at the flush).  A wavefront-scope release / acquire fence on LDS
 // is what orders those accesses for the compiler -- it emits no instruction: a wave's LDS operations complete in
 // order -- and the wave barrier between them keeps the machine scheduler from moving anything across the hand-off.
@@ -106,7 +109,7 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
     // (group numbers are kept in 32 bits)
     const bool stage_out = CAN_STAGE && (pairs_arg & SOLO_STAGED_RESULTS) != 0u && pairs != 2u && Q < (1ull << 34);
     uint2 *results = reinterpret_cast<uint2 *>(s_results + wave * (RES_WAVE_LDS / 16u));  // [RES_BUFS][8] x {lower:40, width:24}
-    uint32_t *res_state = reinterpret_cast<uint32_t *>(results + RES_BUFS * 8u);  // [RES_BUFS] x {tag, out}
+    uint32_t *res_state = reinterpret_cast<uint32_t *>(results + RES_BUFS * 8u);  // [RES_BUFS] x {unused, out}
     const bool count_unstaged = COUNT_WORK && (pairs_arg & SOLO_COUNT_UNSTAGED) != 0u;
     const lds_u32 *mine0 = reinterpret_cast<const lds_u32 *>(stage + (lane & 7u) * 64u + (lane >> 3) * SLOT_U4);
 #define SOLO_MINE(d) (mine0 + (((((uint32_t)(d)) >> 2) ^ swz) << 2) + (((uint32_t)(d)) & 3u))
@@ -163,9 +166,13 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
 
         const uint32_t QCHUNK = qchunk;
         if (CAN_STAGE && stage_out && lane < RES_BUFS) {  // every buffer free (the previous shard's groups have all left)
-            res_state[2u * lane] = ~0u;
             res_state[2u * lane + 1u] = 0u;
         }
+        // staged results: the buffer of the running query (bits 0..7) and of the one in reserve (bits 8..15), RES_NONE =
+        // unstaged; and, wave-uniform, the group begun last among this wave's draws with its buffer: the only group whose
+        // later queries can still be drawn (a pass draws consecutive queries; a group never straddles two chunks)
+        uint32_t res_buf = RES_NONE | (RES_NONE << 8);
+        uint32_t open_g = ~0u, open_b = RES_NONE;
         uint64_t pool_next = 0, pool_end = 0;  // wave-uniform
         bool drained = false;
         size_t q = 0;  // the query this lane is stepping
@@ -258,6 +265,7 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                 has_q = true;
                 has_n = false;
                 q = nq;
+                if (CAN_STAGE) res_buf >>= 8;  // (the reserve's bits are set anew at the next draw)
                 sub = 0;
                 cont = 0;
                 if (nrec.x & INIT_INVALID) {
@@ -310,22 +318,29 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                 const uint64_t r0 = pool_next;
                 pool_next = taken < pool_end ? taken : pool_end;
                 if (CAN_STAGE && stage_out && pool_next > r0) {
-                    // the groups of 8 queries that BEGIN among this pass's draws (at most 9): each gets its buffer,
-                    // g mod RES_BUFS, if that is free (chunks are multiples of 64 and this wave's alone: a group is drawn here whole)
+                    // the groups of 8 queries that BEGIN among this pass's draws (at most 9) take the free buffers in
+                    // order, the i-th group the i-th buffer whose results are all out; none left = unstaged (chunks are
+                    // multiples of 64 and this wave's alone: a group is drawn here whole).  A query drawn into a group
+                    // begun in an earlier pass learns that group's buffer from the wave-uniform pair.
+                    const uint32_t gq = (uint32_t)(nq >> 3);
+                    uint32_t nb = gq == open_g ? open_b : RES_NONE;
                     const uint64_t first = (r0 + 7ull) & ~7ull;
                     if (first < pool_next) {
                         const uint32_t ga = (uint32_t)(first >> 3), gb = (uint32_t)((pool_next - 1ull) >> 3) + 1u;
-                        const uint32_t gam = ga % RES_BUFS;
-                        if (lane < RES_BUFS) {
-                            const uint32_t d = lane >= gam ? lane - gam : lane + RES_BUFS - gam;
-                            const uint32_t g = ga + d;
-                            if (g < gb && res_state[2u * lane + 1u] == 0u) {
+                        uint32_t free_bufs = (uint32_t)__builtin_amdgcn_ballot_w64(lane < RES_BUFS && res_state[2u * lane + 1u] == 0u);
+                        for (uint32_t g = ga; g < gb; ++g) {
+                            const uint32_t bsel = free_bufs != 0u ? (uint32_t)__builtin_ctz(free_bufs) : RES_NONE;
+                            free_bufs &= free_bufs - 1u;
+                            if (gq == g) nb = bsel;
+                            if (lane == bsel) {
                                 const uint64_t q0 = (uint64_t)g << 3;
-                                res_state[2u * lane] = g;
                                 res_state[2u * lane + 1u] = (uint32_t)((q0 + 8ull < pool_end ? q0 + 8ull : pool_end) - q0);
                             }
+                            open_b = bsel;
                         }
+                        open_g = gb - 1u;
                     }
+                    if (got_n) res_buf = (res_buf & 0xFFu) | (nb << 8);
                     solo_lds_handoff();  // the claims are released to the lanes whose searches end
                 }
             }
@@ -678,7 +693,7 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                 nimp = imp;
                 if (WL && !imp) nq = (size_t)wl_index;  // from here on the search is known by its result index
             }
-            if (CAN_STAGE && stage_out) solo_lds_handoff();  // the claims are acquired before a tag is checked
+            if (CAN_STAGE && stage_out) solo_lds_handoff();  // the claims are acquired before a count is taken down
             if (alive && done) {
                 if (trace_s) {  // (WL: `trace` carries the table entries read ahead, not a trace)
                     // the positions it never reached: a search resumed there ends where this one did
@@ -698,9 +713,9 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                         atomicOr(hit_map + (qi >> 6), 1ull << (qi & 63u));
                     }
                 } else {
-                    const uint32_t g32 = (uint32_t)(q >> 3), rb = g32 % RES_BUFS;
+                    const uint32_t rb = res_buf & 0xFFu;
                     bool own_store = true;
-                    if (CAN_STAGE && stage_out && res_state[2u * rb] == g32) {
+                    if (CAN_STAGE && stage_out && rb != RES_NONE) {
                         const uint64_t width = hi - lo + 1ull;  // (mod 2^64: 0 for every empty interval)
                         own_store = width >= (uint64_t)RES_ESCAPED || (lo >> COUNT_BITS) != 0ull;
                         results[rb * 8u + ((uint32_t)q & 7u)] =
@@ -727,8 +742,9 @@ search_solo_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
                 while (fm != 0ull) {
                     const int src = __builtin_ctzll(fm);
                     fm &= fm - 1ull;
-                    // (q still names the query that has just ended)
-                    const uint32_t g = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(q >> 3), src), bsel = g % RES_BUFS;
+                    // (q and res_buf still name the query that has just ended and its buffer)
+                    const uint32_t g = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(q >> 3), src);
+                    const uint32_t bsel = (uint32_t)__builtin_amdgcn_readlane((int)res_buf, src) & 0xFFu;
                     const size_t qq = ((size_t)g << 3) + lane;
                     if (lane < 8u && qq < Qs) {
                         const uint2 v = results[bsel * 8u + lane];

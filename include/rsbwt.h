@@ -148,8 +148,10 @@ int rsbwt_attach_ktab(rsbwt_t *h, uint32_t T);
 int rsbwt_attach_ktab_format(rsbwt_t *h, uint32_t T, uint32_t format);
 /* format (RSBWT_KTAB_FORMAT_PLAIN / _GROUPED), bytes in HBM and -- grouped -- the T-mers left to the search; any may be NULL */
 int rsbwt_ktab_info(const rsbwt_t *h, uint32_t *format, uint64_t *bytes, uint64_t *untabulated);
-/* Test hook (RSBWT_ENABLE_TEST_HOOKS): n bytes of the resident index (region 0: the lines, 1: an owned k-mer table)
- * copied out, the reading twin of rsbwt_debug_poke. */
+/* Test hook (RSBWT_ENABLE_TEST_HOOKS): n bytes of the resident index (region 0: the lines, 1: an owned k-mer table,
+ * 2: the select sample table, 5 * select stride words of 8 bytes -- RSBWT_ERANGE until it has been built: at open with
+ * RSBWT_OPEN_READS, else by rsbwt_prepare_extraction or a first extraction) copied out, the reading twin of
+ * rsbwt_debug_poke. */
 int rsbwt_debug_peek(rsbwt_t *h, int region, uint64_t offset, void *bytes, size_t n);
 /* Test hook (RSBWT_ENABLE_TEST_HOOKS=1): the '$' count of rsbwt_read_copies on {lower, upper} pairs given by hand,
  * u64[Q][2]: copies[q] = Occ('$', upper) - Occ('$', lower - 1) with Occ(., -1) = 0 and ending[q] = upper - lower + 1 (may
@@ -752,6 +754,21 @@ int rsbwt_layout_selftest_host(const uint8_t *runs, uint64_t num_runs, uint32_t 
  * hint, rows a hint settles (the others it bounds)}; *first_bad as above. */
 int rsbwt_layout_selftest_psi_host(const uint8_t *runs, uint64_t num_runs, uint32_t window_span, uint64_t *stats4,
                                    uint64_t *first_bad);
+
+/* Test hook (host only, answers no query): the lines the two hooks above certify, handed out, so that a GPU test can
+ * hold the device builder's lines and select sample table to them byte for byte.  `runs` is laid out by the very
+ * passes of rsbwt_layout_selftest_host -- or, with RSBWT_LAYOUT_HINTS, of rsbwt_layout_selftest_psi_host, whose sample
+ * table and psi hints are then built too, the hints written into the lines.  window_span as above (bit 31: the
+ * RSBWT_OPEN_READS layout).  out_lines: lines * 128 bytes, cap_bytes of room (NULL: the count pass only); out_sel: the
+ * sample table, stats10[7] words, cap_sel_words of room (NULL, or without the flag: not copied); group_stats4: {far
+ * lines, chunk windows, far windows, spilled symbols} per group of 16 windows, cap_groups groups of room (NULL: not
+ * wanted).  stats10 = the stats6 above, then {groups, words of the sample table, sample words written, lines with a
+ * hint} (the last two 0 unless built).  RSBWT_ERANGE: a buffer is too small (stats10 is filled all the same);
+ * RSBWT_EFORMAT: a symbol code above 4. */
+#define RSBWT_LAYOUT_HINTS 1u
+int rsbwt_layout_lines_host(const uint8_t *runs, uint64_t num_runs, uint32_t window_span, uint32_t flags,
+                            uint32_t *out_lines, uint64_t cap_bytes, uint64_t *out_sel, uint64_t cap_sel_words,
+                            uint64_t *group_stats4, uint64_t cap_groups, uint64_t *stats10);
 
 /* Test hook (host only, answers no query): the grouped k-mer table's record code (rsbwt_attach_ktab_format) -- `groups`
  * x 4 sibling intervals in, the 4 entries each 12-byte record gives back out as {lower:40 | width:24} words, width

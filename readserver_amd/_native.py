@@ -217,6 +217,7 @@ SIGNATURES = {
     "rsbwt_set_last_search_counters": (C.c_int, [_vp, _u64p]),
     "rsbwt_layout_selftest_host": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _u64p, _u64p]),
     "rsbwt_layout_selftest_psi_host": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _u64p, _u64p]),
+    "rsbwt_layout_lines_host": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),
     "rsbwt_ktab_group_selftest_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
     "rsbwt_debug_fast_window": (C.c_int, [_vp, C.c_size_t, C.c_uint32, _vp, _vp, C.c_int]),
     "rsbwt_debug_poke": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, C.c_size_t]),

@@ -542,18 +542,23 @@ int rsbwt_debug_poke(rsbwt_t *h, int region, uint64_t offset, const void *bytes,
 }
 
 // Test hook, the reading twin of rsbwt_debug_poke: n bytes of the index in HBM (region 0: the lines, 1: the k-mer
-// table) copied to `bytes` -- so that a test can hold "nothing a search reads is written after the handle was handed
+// table, 2: the select sample table) copied to `bytes` -- so that a test can hold "nothing a search reads is written after the handle was handed
 // out" to the bytes themselves.  Answers no query.
 int rsbwt_debug_peek(rsbwt_t *h, int region, uint64_t offset, void *bytes, size_t n) {
     if (!h || (!bytes && n)) return fail(RSBWT_EINVAL, "null argument");
     if (getenv("RSBWT_ENABLE_TEST_HOOKS") == nullptr) return fail(RSBWT_EINVAL, "rsbwt_debug_peek is a test hook: set RSBWT_ENABLE_TEST_HOOKS=1");
+    // (region 2, the select sample table: there once x_ready says so -- built at open, by rsbwt_prepare_extraction or by
+    // a first extraction)
+    const bool sampled = region == 2 && h->x_ready.load(std::memory_order_acquire) && h->d_sel;
+    if (region == 2 && !sampled) return fail(RSBWT_ERANGE, "the select sample table has not been built");
     const uint64_t size = region == 0 ? h->view.nlines * (uint64_t)LINE_BYTES
-                          : region == 1 && h->view.ktab && h->ktab_owned ? ktab_bytes(h->view.ktab_fmt, h->view.ktab_depth) : 0ull;
+                          : region == 1 && h->view.ktab && h->ktab_owned ? ktab_bytes(h->view.ktab_fmt, h->view.ktab_depth)
+                          : sampled ? 5ull * select_sample_stride(h->view) * sizeof(uint64_t) : 0ull;
     if (offset > size || n > size - offset) return fail(RSBWT_ERANGE, "peek outside the region (%llu bytes)", (unsigned long long)size);
     if (n == 0) return RSBWT_OK;
     int rc = use_device(h->device);
     if (rc != RSBWT_OK) return rc;
-    const char *base = region == 0 ? (const char *)h->view.lines : (const char *)h->view.ktab;
+    const char *base = region == 0 ? (const char *)h->view.lines : region == 1 ? (const char *)h->view.ktab : (const char *)h->d_sel;
     const hipError_t e = hipMemcpy(bytes, base + offset, n, hipMemcpyDeviceToHost);
     return e == hipSuccess ? RSBWT_OK : fail_hip(e, "rsbwt_debug_peek");
 }

@@ -17,6 +17,143 @@ using namespace rsb;
 // (bit 31 of window_span, both hooks: the RSBWT_OPEN_READS layout -- room for a psi hint in every window line)
 static constexpr uint32_t SELFTEST_ROOM = 1u << 31;
 
+// ---- the build passes: one piece of code for the two selftests and for rsbwt_layout_lines_host, so that the lines the
+// hook hands out are the lines whose every position the selftests check
+
+// what a run stream holds: symbols per code; RSBWT_EFORMAT for a code above 4 (a zero-length byte's code counts too, as
+// in the GPU builder's tile totals)
+static int scan_runs(const uint8_t *runs, uint64_t num_runs, uint64_t total[5]) {
+    for (int c = 0; c < 5; ++c) total[c] = 0;
+    for (uint64_t r = 0; r < num_runs; ++r) {
+        if ((runs[r] >> 5) > 4) return RSBWT_EFORMAT;
+        total[runs[r] >> 5] += runs[r] & 31u;
+    }
+    return RSBWT_OK;
+}
+
+struct host_layout {
+    span_params sp;
+    bool room;
+    uint64_t n, nwin, ngroups, first_far, nlines;
+    std::vector<uint64_t> far_base;  // far lines before each group (ngroups + 1)
+    std::vector<group_stats> per_group;
+    group_stats tot;
+};
+
+// pass 1: the span (0 = 90 pieces per window at the mean run length), then far lines and statistics per group, one
+// reader over the whole stream
+static void count_pass(const uint8_t *runs, uint64_t num_runs, uint64_t n, uint32_t window_span, bool room, host_layout &lay) {
+    uint32_t S = window_span;
+    if (!S) S = (uint32_t)(90.0 * (double)n / (double)num_runs + 0.5);
+    lay.sp = make_span(S);
+    lay.room = room;
+    lay.n = n;
+    lay.nwin = (n + lay.sp.S - 1) / lay.sp.S;
+    lay.ngroups = (lay.nwin + GROUP - 1) / GROUP;
+    lay.far_base.assign(lay.ngroups + 1, 0);
+    lay.per_group.resize(lay.ngroups);
+    lay.tot = {0, 0, 0, 0};
+    const uint64_t zero[4] = {0, 0, 0, 0};
+    run_reader rd;
+    rd.start(runs, num_runs, 0, zero);
+    for (uint64_t g = 0; g < lay.ngroups; ++g) {
+        const group_stats st = build_group<false>(lay.sp, n, lay.nwin, g, rd, nullptr, 0, room);
+        lay.per_group[g] = st;
+        lay.far_base[g + 1] = lay.far_base[g] + st.far_lines;
+        lay.tot.far_lines += st.far_lines;
+        lay.tot.chunk_windows += st.chunk_windows;
+        lay.tot.far_windows += st.far_windows;
+        lay.tot.spilled_symbols += st.spilled_symbols;
+    }
+    lay.first_far = lay.ngroups * (GROUP + 1);
+    lay.nlines = lay.first_far + lay.far_base[lay.ngroups];
+}
+
+// pass 2 of rsbwt_layout_selftest_host: every group from a reader re-seated at its first symbol (as the GPU threads
+// are).  `lines`: nlines * LINE_DWORDS zeroed dwords.
+static void write_pass_reseated(const uint8_t *runs, uint64_t num_runs, const host_layout &lay, uint32_t *lines) {
+    uint64_t cnt[4] = {0, 0, 0, 0};
+    uint64_t r = 0, at = 0;
+    for (uint64_t g = 0; g < lay.ngroups; ++g) {
+        const uint64_t gstart = g * GROUP * (uint64_t)lay.sp.S;
+        // runs wholly before the group's first symbol
+        while (r < num_runs && at + (runs[r] & 31u) <= gstart) {
+            const uint32_t sy = runs[r] >> 5;
+            if (sy >= 1 && sy <= 4) cnt[sy - 1] += runs[r] & 31u;
+            at += runs[r] & 31u;
+            ++r;
+        }
+        run_reader rd;
+        rd.start(runs, num_runs, r, cnt);
+        rd.skip_symbols(gstart - at);
+        build_group<true>(lay.sp, lay.n, lay.nwin, g, rd, lines, lay.first_far + lay.far_base[g], lay.room);
+    }
+}
+
+// pass 2 of rsbwt_layout_selftest_psi_host: one reader over the whole stream
+static void write_pass_sequential(const uint8_t *runs, uint64_t num_runs, const host_layout &lay, uint32_t *lines) {
+    const uint64_t zero[4] = {0, 0, 0, 0};
+    run_reader rd;
+    rd.start(runs, num_runs, 0, zero);
+    for (uint64_t g = 0; g < lay.ngroups; ++g)
+        build_group<true>(lay.sp, lay.n, lay.nwin, g, rd, lines, lay.first_far + lay.far_base[g], lay.room);
+}
+
+static shard_view host_view(const host_layout &lay, const uint32_t *lines, const uint64_t total[5]) {
+    shard_view v;
+    memset(&v, 0, sizeof v);
+    v.lines = lines;
+    v.n = lay.n;
+    v.nwin = lay.nwin;
+    v.nlines = lay.nlines;
+    v.first_far = lay.first_far;
+    v.sp = lay.sp;
+    v.sel_shift = lay.room ? SEL_SHIFT_SPARSE : SEL_SHIFT_DENSE;
+    v.hint_room = lay.room ? 1u : 0u;
+    for (int c = 0; c < 5; ++c) v.total[c] = total[c];
+    for (int c = 1; c < 5; ++c) v.C[c] = v.C[c - 1] + v.total[c - 1];
+    return v;
+}
+
+static void put_stats6(const host_layout &lay, uint64_t *stats6) {
+    stats6[0] = lay.sp.S;
+    stats6[1] = lay.nlines;
+    stats6[2] = lay.tot.far_lines;
+    stats6[3] = lay.tot.chunk_windows;
+    stats6[4] = lay.tot.far_windows;
+    stats6[5] = lay.tot.spilled_symbols;
+}
+
+// the select sample table (5 * select_stride(v) zeroed words) as select_sample_kernel fills it; the words written
+static uint64_t build_samples(const shard_view &v, uint64_t *sel) {
+    const uint64_t stride = select_stride(v);
+    uint64_t words = 0;
+    for (uint64_t w = 0; w < v.nwin; ++w)
+        for (uint32_t c = 0; c <= 4; ++c)
+            window_samples(v, w, c, [&](uint64_t m, uint64_t word) {
+                sel[c * stride + m] = word;
+                ++words;
+            });
+    return words;
+}
+
+// the psi hints, written into the lines as psi_hint_kernel writes them; the lines that got one
+static uint64_t write_hints(const shard_view &v, const uint64_t *sel, uint32_t *lines) {
+    const uint64_t stride = select_stride(v);
+    uint64_t hint_lines = 0;
+    for (uint64_t w = 0; w < v.nwin; ++w) {
+        uint32_t w0, kk;
+        if (!window_psi_hint(v, sel, stride, w, &w0, &kk)) continue;
+        uint32_t *Ln = lines + line_of_window(w) * LINE_DWORDS;
+        const uint32_t hd = hint_dword(parse_line(Ln).kind);
+        Ln[hd] = w0;
+        Ln[hd + 1u] = kk;
+        Ln[1] |= 1u << (8u + HINT_META0_BIT);
+        ++hint_lines;
+    }
+    return hint_lines;
+}
+
 extern "C" int rsbwt_layout_selftest_host(const uint8_t *runs, uint64_t num_runs, uint32_t window_span,
                                           uint64_t *stats6, uint64_t *first_bad) {
     if (!runs && num_runs) return RSBWT_EINVAL;
@@ -31,67 +168,15 @@ extern "C" int rsbwt_layout_selftest_host(const uint8_t *runs, uint64_t num_runs
     const uint64_t n = bwt.size();
     if (first_bad) *first_bad = ~0ull;
     if (n == 0) return RSBWT_OK;
-    uint32_t S = window_span;
-    if (!S) S = (uint32_t)(90.0 * (double)n / (double)num_runs + 0.5);
-    const span_params sp = make_span(S);
-    const uint64_t nwin = (n + sp.S - 1) / sp.S, ngroups = (nwin + GROUP - 1) / GROUP;
-    // pass 1: far lines per group
-    std::vector<uint64_t> far_base(ngroups + 1, 0);
-    group_stats tot = {0, 0, 0, 0};
-    {
-        const uint64_t zero[4] = {0, 0, 0, 0};
-        run_reader rd;
-        rd.start(runs, num_runs, 0, zero);
-        for (uint64_t g = 0; g < ngroups; ++g) {
-            const group_stats st = build_group<false>(sp, n, nwin, g, rd, nullptr, 0, room);
-            far_base[g + 1] = far_base[g] + st.far_lines;
-            tot.far_lines += st.far_lines;
-            tot.chunk_windows += st.chunk_windows;
-            tot.far_windows += st.far_windows;
-            tot.spilled_symbols += st.spilled_symbols;
-        }
-    }
-    const uint64_t first_far = ngroups * (GROUP + 1), nlines = first_far + far_base[ngroups];
-    std::vector<uint32_t> lines(nlines * LINE_DWORDS, 0);
-    // pass 2: every group from a reader re-seated at its first symbol (as the GPU threads are)
-    {
-        uint64_t cnt[4] = {0, 0, 0, 0};
-        uint64_t r = 0, at = 0;
-        for (uint64_t g = 0; g < ngroups; ++g) {
-            const uint64_t gstart = g * GROUP * (uint64_t)sp.S;
-            // runs wholly before the group's first symbol
-            while (r < num_runs && at + (runs[r] & 31u) <= gstart) {
-                const uint32_t sy = runs[r] >> 5;
-                if (sy >= 1 && sy <= 4) cnt[sy - 1] += runs[r] & 31u;
-                at += runs[r] & 31u;
-                ++r;
-            }
-            run_reader rd;
-            rd.start(runs, num_runs, r, cnt);
-            rd.skip_symbols(gstart - at);
-            build_group<true>(sp, n, nwin, g, rd, lines.data(), first_far + far_base[g], room);
-        }
-    }
-    shard_view v;
-    memset(&v, 0, sizeof v);
-    v.lines = lines.data();
-    v.n = n;
-    v.nwin = nwin;
-    v.nlines = nlines;
-    v.first_far = first_far;
-    v.sp = sp;
-    v.sel_shift = room ? SEL_SHIFT_SPARSE : SEL_SHIFT_DENSE;
-    v.hint_room = room ? 1u : 0u;
-    for (uint64_t p = 0; p < n; ++p) v.total[bwt[p]]++;
-    for (int c = 1; c < 5; ++c) v.C[c] = v.C[c - 1] + v.total[c - 1];
-    if (stats6) {
-        stats6[0] = sp.S;
-        stats6[1] = nlines;
-        stats6[2] = tot.far_lines;
-        stats6[3] = tot.chunk_windows;
-        stats6[4] = tot.far_windows;
-        stats6[5] = tot.spilled_symbols;
-    }
+    host_layout lay;
+    count_pass(runs, num_runs, n, window_span, room, lay);
+    std::vector<uint32_t> lines(lay.nlines * LINE_DWORDS, 0);
+    write_pass_reseated(runs, num_runs, lay, lines.data());
+    uint64_t total[5] = {0, 0, 0, 0, 0};
+    for (uint64_t p = 0; p < n; ++p) total[bwt[p]]++;
+    const shard_view v = host_view(lay, lines.data(), total);
+    const uint64_t nwin = lay.nwin;
+    if (stats6) put_stats6(lay, stats6);
     // every position: Occ of all five symbols, the symbol itself, and select of that occurrence
     uint64_t occ[5] = {0, 0, 0, 0, 0};
     for (uint64_t p = 0; p < n; ++p) {
@@ -132,50 +217,23 @@ extern "C" int rsbwt_layout_selftest_psi_host(const uint8_t *runs, uint64_t num_
     if (first_bad) *first_bad = ~0ull;
     if (stats4) stats4[0] = stats4[1] = stats4[2] = stats4[3] = 0;
     if (n == 0) return RSBWT_OK;
-    uint32_t S = window_span;
-    if (!S) S = (uint32_t)(90.0 * (double)n / (double)num_runs + 0.5);
-    const span_params sp = make_span(S);
-    const uint64_t nwin = (n + sp.S - 1) / sp.S, ngroups = (nwin + GROUP - 1) / GROUP;
-    std::vector<uint64_t> far_base(ngroups + 1, 0);
-    {
-        const uint64_t zero[4] = {0, 0, 0, 0};
-        run_reader rd;
-        rd.start(runs, num_runs, 0, zero);
-        for (uint64_t g = 0; g < ngroups; ++g) far_base[g + 1] = far_base[g] + build_group<false>(sp, n, nwin, g, rd, nullptr, 0, room).far_lines;
-    }
-    const uint64_t first_far = ngroups * (GROUP + 1), nlines = first_far + far_base[ngroups];
-    std::vector<uint32_t> lines(nlines * LINE_DWORDS, 0);
-    {
-        const uint64_t zero[4] = {0, 0, 0, 0};
-        run_reader rd;
-        rd.start(runs, num_runs, 0, zero);
-        for (uint64_t g = 0; g < ngroups; ++g) build_group<true>(sp, n, nwin, g, rd, lines.data(), first_far + far_base[g], room);
-    }
-    shard_view v;
-    memset(&v, 0, sizeof v);
-    v.lines = lines.data();
-    v.n = n;
-    v.nwin = nwin;
-    v.nlines = nlines;
-    v.first_far = first_far;
-    v.sp = sp;
-    v.sel_shift = room ? SEL_SHIFT_SPARSE : SEL_SHIFT_DENSE;
-    v.hint_room = room ? 1u : 0u;
-    for (uint64_t p = 0; p < n; ++p) v.total[bwt[p]]++;
-    for (int c = 1; c < 5; ++c) v.C[c] = v.C[c - 1] + v.total[c - 1];
+    host_layout lay;
+    count_pass(runs, num_runs, n, window_span, room, lay);
+    std::vector<uint32_t> lines(lay.nlines * LINE_DWORDS, 0);
+    write_pass_sequential(runs, num_runs, lay, lines.data());
+    uint64_t total[5] = {0, 0, 0, 0, 0};
+    for (uint64_t p = 0; p < n; ++p) total[bwt[p]]++;
+    const shard_view v = host_view(lay, lines.data(), total);
+    const span_params sp = lay.sp;
+    const uint64_t nwin = lay.nwin;
     // positions of the occurrences of every symbol (the naive select)
     std::vector<uint64_t> where[5];
     for (uint64_t p = 0; p < n; ++p) where[bwt[p]].push_back(p);
     // ---- samples
     const uint64_t stride = select_stride(v);
     std::vector<uint64_t> sel(5 * stride, 0);
-    uint64_t words = 0, inexact = 0;
-    for (uint64_t w = 0; w < nwin; ++w)
-        for (uint32_t c = 0; c <= 4; ++c)
-            window_samples(v, w, c, [&](uint64_t m, uint64_t word) {
-                sel[c * stride + m] = word;
-                ++words;
-            });
+    const uint64_t words = build_samples(v, sel.data());
+    uint64_t inexact = 0;
     for (uint32_t c = 0; c <= 4; ++c)
         for (uint64_t bc = 1; bc <= v.total[c]; ++bc) {
             bool exact;
@@ -189,17 +247,8 @@ extern "C" int rsbwt_layout_selftest_psi_host(const uint8_t *runs, uint64_t num_
             }
         }
     // ---- hints, written into the lines as the kernel writes them
-    uint64_t hint_lines = 0, by_hint = 0;
-    for (uint64_t w = 0; w < nwin; ++w) {
-        uint32_t w0, kk;
-        if (!window_psi_hint(v, sel.data(), stride, w, &w0, &kk)) continue;
-        uint32_t *Ln = lines.data() + line_of_window(w) * LINE_DWORDS;
-        const uint32_t hd = hint_dword(parse_line(Ln).kind);
-        Ln[hd] = w0;
-        Ln[hd + 1u] = kk;
-        Ln[1] |= 1u << (8u + HINT_META0_BIT);
-        ++hint_lines;
-    }
+    const uint64_t hint_lines = write_hints(v, sel.data(), lines.data());
+    uint64_t by_hint = 0;
     const uint32_t hs = hint_shift(sp.S);
     for (uint64_t i = 0; i < n; ++i) {  // row i: psi(i) = select_f(i - C[f] + 1), f = F(i)
         uint32_t f = 0;
@@ -239,6 +288,61 @@ extern "C" int rsbwt_layout_selftest_psi_host(const uint8_t *runs, uint64_t num_
             return RSBWT_EFORMAT;
         }
     }
+    return RSBWT_OK;
+}
+
+// TEST HOOK, host only (answers no query): the lines the two selftests above certify, handed out -- so that a GPU test
+// can hold the device builder's lines, and the select sample table, to them byte for byte.  The stream is laid out by
+// the selftests' own passes (RSBWT_LAYOUT_HINTS clear: rsbwt_layout_selftest_host's, every group from a re-seated
+// reader; set: rsbwt_layout_selftest_psi_host's, then its sample table and its hints written into the lines).
+// window_span as for the selftests (bit 31: the RSBWT_OPEN_READS layout; 0: 90 pieces per window).
+//   out_lines     nlines * 128 bytes (cap_bytes of room); NULL = the count pass only: statistics, nothing built
+//   out_sel       with RSBWT_LAYOUT_HINTS, 5 * select_stride words (cap_sel_words of room); may be NULL
+//   group_stats   4 numbers per group {far lines, chunk windows, far windows, spilled symbols} (cap_groups of room);
+//                 may be NULL
+//   stats10       {S, lines, far lines, chunk windows, far windows, spilled symbols, groups, words of the sample table,
+//                 sample words written, lines with a hint} (the last two 0 unless built)
+// RSBWT_ERANGE when a buffer is too small (stats10 is filled all the same: call once without buffers to size them).
+extern "C" int rsbwt_layout_lines_host(const uint8_t *runs, uint64_t num_runs, uint32_t window_span, uint32_t flags,
+                                       uint32_t *out_lines, uint64_t cap_bytes, uint64_t *out_sel, uint64_t cap_sel_words,
+                                       uint64_t *group_stats4, uint64_t cap_groups, uint64_t *stats10) {
+    if ((!runs && num_runs) || !stats10 || (flags & ~RSBWT_LAYOUT_HINTS)) return RSBWT_EINVAL;
+    const bool room = (window_span & SELFTEST_ROOM) != 0u, hints = (flags & RSBWT_LAYOUT_HINTS) != 0u;
+    window_span &= ~SELFTEST_ROOM;
+    for (int i = 0; i < 10; ++i) stats10[i] = 0;
+    uint64_t total[5];
+    const int rc = scan_runs(runs, num_runs, total);
+    if (rc != RSBWT_OK) return rc;
+    const uint64_t n = total[0] + total[1] + total[2] + total[3] + total[4];
+    if (n == 0) return RSBWT_OK;
+    host_layout lay;
+    count_pass(runs, num_runs, n, window_span, room, lay);
+    shard_view v = host_view(lay, out_lines, total);
+    const uint64_t sel_words = 5 * select_stride(v);
+    put_stats6(lay, stats10);
+    stats10[6] = lay.ngroups;
+    stats10[7] = sel_words;
+    if (group_stats4) {
+        if (cap_groups < lay.ngroups) return RSBWT_ERANGE;
+        for (uint64_t g = 0; g < lay.ngroups; ++g) {
+            group_stats4[4 * g] = lay.per_group[g].far_lines;
+            group_stats4[4 * g + 1] = lay.per_group[g].chunk_windows;
+            group_stats4[4 * g + 2] = lay.per_group[g].far_windows;
+            group_stats4[4 * g + 3] = lay.per_group[g].spilled_symbols;
+        }
+    }
+    if (!out_lines) return RSBWT_OK;
+    if (cap_bytes / LINE_BYTES < lay.nlines || (hints && out_sel && cap_sel_words < sel_words)) return RSBWT_ERANGE;
+    memset(out_lines, 0, lay.nlines * (uint64_t)LINE_BYTES);
+    if (!hints) {
+        write_pass_reseated(runs, num_runs, lay, out_lines);
+        return RSBWT_OK;
+    }
+    write_pass_sequential(runs, num_runs, lay, out_lines);
+    std::vector<uint64_t> sel(sel_words, 0);
+    stats10[8] = build_samples(v, sel.data());
+    stats10[9] = write_hints(v, sel.data(), out_lines);
+    if (out_sel) memcpy(out_sel, sel.data(), sel_words * sizeof(uint64_t));
     return RSBWT_OK;
 }
 

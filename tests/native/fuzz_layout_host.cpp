@@ -15,6 +15,9 @@ extern "C" int rsbwt_layout_selftest_host(const uint8_t *runs, uint64_t num_runs
                                           uint64_t *stats6, uint64_t *first_bad);
 extern "C" int rsbwt_layout_selftest_psi_host(const uint8_t *runs, uint64_t num_runs, uint32_t window_span,
                                               uint64_t *stats4, uint64_t *first_bad);
+extern "C" int rsbwt_layout_lines_host(const uint8_t *runs, uint64_t num_runs, uint32_t window_span, uint32_t flags,
+                                       uint32_t *out_lines, uint64_t cap_bytes, uint64_t *out_sel, uint64_t cap_sel_words,
+                                       uint64_t *group_stats4, uint64_t cap_groups, uint64_t *stats10);
 extern "C" int rsbwt_ktab_group_selftest_host(const uint64_t *lower, const uint64_t *upper, size_t groups, uint64_t *entries);
 
 static uint64_t s = 0xD1B54A32D192ED03ull;
@@ -58,6 +61,28 @@ int main(int argc, char **argv) {
         }
         hint_lines += st4[2];
         hinted_rows += st4[3];
+        // the hook that hands those lines out (rsbwt_layout_lines_host), into buffers of exactly the sizes it names: the
+        // count pass alone, then both writers; its statistics are the selftests'
+        for (uint32_t flags = 0; flags <= RSBWT_LAYOUT_HINTS; ++flags) {
+            uint64_t cs[10], fs[10];
+            int rc3 = rsbwt_layout_lines_host(runs.data(), R, span, flags, nullptr, 0, nullptr, 0, nullptr, 0, cs);
+            std::vector<uint32_t> lines(cs[1] * 32);
+            std::vector<uint64_t> sel(flags ? cs[7] : 0), gs(cs[6] * 4);
+            if (rc3 == RSBWT_OK)
+                rc3 = rsbwt_layout_lines_host(runs.data(), R, span, flags, lines.data(), lines.size() * 4, sel.data(), sel.size(), gs.data(),
+                                              cs[6], fs);
+            bool same = rc3 == RSBWT_OK;
+            for (int i = 0; i < 8 && same; ++i) same = cs[i] == fs[i] && (i >= 6 || fs[i] == st[i]);
+            uint64_t sum[4] = {0, 0, 0, 0};
+            for (size_t i = 0; i < gs.size(); ++i) sum[i % 4] += gs[i];
+            same = same && sum[0] == st[2] && sum[1] == st[3] && sum[2] == st[4] && sum[3] == st[5];
+            if (flags) same = same && fs[8] == st4[0] && fs[9] == st4[2];
+            if (!same) {
+                fprintf(stderr, "iteration %d (lines hook, flags %u): shape %d, %llu runs, span %u: rc %d or statistics differ\n", it, flags,
+                        shape, (unsigned long long)R, span, rc3);
+                return 1;
+            }
+        }
     }
     printf("%d run streams laid out and checked at every position; %llu lines with a psi hint answered %llu rows\n", iters,
            (unsigned long long)hint_lines, (unsigned long long)hinted_rows);

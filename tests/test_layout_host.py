@@ -7,6 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import layout_reference as LR
+
 
 def _runs(style, R, rng, L):
     if style == "synth":
@@ -23,12 +25,15 @@ def _runs(style, R, rng, L):
     return (rng.integers(0, 5, R).astype(np.uint8) << 5) | rng.integers(1, 32, R).astype(np.uint8)
 
 
-@pytest.mark.parametrize("style,R,span", [("synth", 60000, 0), ("synth", 60000, 256), ("synth", 60000, 1536),
-                                          ("synth", 60000, 2944), ("dense", 30000, 0), ("dense", 30000, 2944),
-                                          ("dense", 20000, 300), ("long", 30000, 0), ("long", 30000, 256),
-                                          ("mixed", 60000, 0), ("mixed", 60000, 768), ("rand", 40000, 0),
-                                          ("rand", 1, 0), ("rand", 2, 0), ("rand", 97, 0), ("rand", 17, 5),
-                                          ("rand", 3000, 2), ("rand", 3000, 3)])
+LAYOUT_MATRIX = [("synth", 60000, 0), ("synth", 60000, 256), ("synth", 60000, 1536),
+                 ("synth", 60000, 2944), ("dense", 30000, 0), ("dense", 30000, 2944),
+                 ("dense", 20000, 300), ("long", 30000, 0), ("long", 30000, 256),
+                 ("mixed", 60000, 0), ("mixed", 60000, 768), ("rand", 40000, 0),
+                 ("rand", 1, 0), ("rand", 2, 0), ("rand", 97, 0), ("rand", 17, 5),
+                 ("rand", 3000, 2), ("rand", 3000, 3)]
+
+
+@pytest.mark.parametrize("style,R,span", LAYOUT_MATRIX)
 @pytest.mark.parametrize("room", [False, True])
 def test_layout_is_exact_at_every_position(rsb, style, R, span, room):
     """room: the RSBWT_OPEN_READS layout -- every window line keeps its last 8 piece bytes for a psi hint."""
@@ -60,10 +65,58 @@ def test_layout_rejects_symbols_above_four(rsb):
     assert L.rsbwt_layout_selftest_host(runs.ctypes.data, 2, 0, None, None) == -3
 
 
+def _want_span(runs, span, room):
+    if room and span == 0:
+        n = int((runs & 31).astype(np.int64).sum())
+        return max(2, min(2944, int(82.0 * n / runs.size + 0.5)))
+    return span
+
+
+@pytest.mark.parametrize("style,R,span", LAYOUT_MATRIX)
+@pytest.mark.parametrize("room", [False, True])
+def test_lines_hook_hands_out_what_the_selftest_certifies(rsb, style, R, span, room):
+    """rsbwt_layout_lines_host (the lines the GPU builder's bytes are held to: tests/test_gpu_builder_bytes.py) runs the
+    selftest's own passes: its totals are the selftest's stats6, its per-group numbers sum to them, the count pass alone
+    says what the full call says, and the lines are all there -- what lies past the last line is not touched."""
+    L = rsb.lib()
+    runs = _runs(style, R, np.random.default_rng(R + span), L)
+    want = _want_span(runs, span, room)
+    st = (C.c_uint64 * 6)()
+    assert L.rsbwt_layout_selftest_host(runs.ctypes.data, R, want | (1 << 31 if room else 0), st, None) == 0
+    full = LR.host_layout(L, runs, want, room)
+    count = LR.host_layout(L, runs, want, room, lines=False)
+    assert [full[k] for k in LR.STATS[:6]] == list(st)
+    assert [count[k] for k in LR.STATS] == [full[k] for k in LR.STATS] and np.array_equal(count["group"], full["group"])
+    n = int((runs & 31).astype(np.int64).sum())
+    assert full["groups"] == ((n + full["S"] - 1) // full["S"] + 15) // 16 and full["sample_words"] == full["hint_lines"] == 0
+    assert full["group"].sum(axis=0).tolist() == list(st)[2:6]
+    assert full["dwords"].shape == (st[1], 32) and full["dwords"][0, 8:].any()  # (window 0 holds pieces)
+    # a buffer one line short is refused, and nothing is written past what was offered
+    guard = np.full((st[1] + 1, 32), 0xA5A5A5A5, np.uint32)
+    st10 = np.zeros(10, np.uint64)
+    arg = (runs.ctypes.data, R, want | (1 << 31 if room else 0), 0)
+    assert L.rsbwt_layout_lines_host(*arg, guard.ctypes.data, (st[1] - 1) * 128, None, 0, None, 0, st10.ctypes.data) == -7
+    assert (guard == 0xA5A5A5A5).all() and st10[:6].tolist() == list(st)
+    assert L.rsbwt_layout_lines_host(*arg, guard.ctypes.data, st[1] * 128, None, 0, None, 0, st10.ctypes.data) == 0
+    assert np.array_equal(guard[:-1], full["dwords"]) and (guard[-1] == 0xA5A5A5A5).all()
+
+
+def test_lines_hook_rejects_symbols_above_four_and_bad_arguments(rsb):
+    L = rsb.lib()
+    st10 = np.zeros(10, np.uint64)
+    for runs in (np.array([(1 << 5) | 3, (6 << 5) | 2], np.uint8), np.array([(1 << 5) | 3, (6 << 5) | 0, (2 << 5) | 1], np.uint8)):
+        assert LR.host_layout(L, runs, 0, False, rc_only=True) == -3  # (a zero-length byte's code counts, as on the GPU)
+    ok = np.array([(1 << 5) | 3], np.uint8)
+    assert L.rsbwt_layout_lines_host(ok.ctypes.data, 1, 0, 2, None, 0, None, 0, None, 0, st10.ctypes.data) == -1  # unknown flag
+    assert L.rsbwt_layout_lines_host(ok.ctypes.data, 1, 0, 0, None, 0, None, 0, None, 0, None) == -1
+    assert L.rsbwt_layout_lines_host(None, 0, 0, 0, None, 0, None, 0, None, 0, st10.ctypes.data) == 0 and not st10.any()
+
+
 def test_layout_code_under_address_and_ub_sanitizers(tmp_path):
     """tests/native/fuzz_layout_host.cpp: the layout builder and the scalar readers of line_format.h
     (the code the GPU kernels run) built for the CPU with -fsanitize=address,undefined, on 30 random run
-    streams of six shapes at spans 2..2,944, every position held to naive ranks; and the grouped k-mer table's record
+    streams of six shapes at spans 2..2,944, every position held to naive ranks -- and handed out by
+    rsbwt_layout_lines_host into buffers of exactly the sizes it names; and the grouped k-mer table's record
     code on 200,000 groups of four siblings, sound ones and arbitrary ones (a sibling that comes back with a width is
     exactly what went in)."""
     import os
@@ -85,10 +138,57 @@ def test_layout_code_under_address_and_ub_sanitizers(tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr[-3000:]
 
 
-@pytest.mark.parametrize("style,R,span", [("synth", 60000, 0), ("pop", 80000, 0), ("pop", 80000, 300), ("pop", 60000, 1024),
-                                          ("dense", 30000, 90), ("long", 30000, 0), ("mixed", 60000, 0), ("rand", 40000, 0),
-                                          ("desert", 60000, 0), ("rand", 1, 0), ("rand", 97, 5), ("rand", 3000, 2),
-                                          ("pop", 80000, 2000), ("dense", 30000, 2944)])
+PSI_MATRIX = [("synth", 60000, 0), ("pop", 80000, 0), ("pop", 80000, 300), ("pop", 60000, 1024),
+              ("dense", 30000, 90), ("long", 30000, 0), ("mixed", 60000, 0), ("rand", 40000, 0),
+              ("desert", 60000, 0), ("rand", 1, 0), ("rand", 97, 5), ("rand", 3000, 2),
+              ("pop", 80000, 2000), ("dense", 30000, 2944)]
+
+
+def _psi_runs(style, R, span, L):
+    rng = np.random.default_rng(R * 7 + span)
+    if style == "pop":
+        runs = np.empty(R, np.uint8)
+        assert L.rsbwt_synth_runs_host(runs.ctypes.data, R, 77 | (1 << 62)) == 0
+        return runs
+    if style == "desert":  # stretches without one symbol: sample blocks spread over many windows
+        sym = np.where((np.arange(R) // 7000) % 2 == 0, rng.integers(0, 5, R), rng.integers(0, 4, R))
+        return ((sym.astype(np.uint8)) << 5) | rng.integers(1, 9, R).astype(np.uint8)
+    return _runs(style, R, rng, L)
+
+
+@pytest.mark.parametrize("style,R,span", PSI_MATRIX)
+@pytest.mark.parametrize("room", [False, True])
+def test_lines_hook_with_hints_is_the_psi_selftests_layout(rsb, style, R, span, room):
+    """RSBWT_LAYOUT_HINTS: the sample table and the hinted lines the psi selftest certifies -- as many sample words, as
+    many lines with a hint -- and, hints apart, the lines of the call without the flag (the selftests' two writers, one
+    reader over the stream and a reader re-seated per group, lay out the same bytes)."""
+    L = rsb.lib()
+    runs = _psi_runs(style, R, span, L)
+    want = _want_span(runs, span, room)
+    st = (C.c_uint64 * 4)()
+    assert L.rsbwt_layout_selftest_psi_host(runs.ctypes.data, R, want | (1 << 31 if room else 0), st, None) == 0
+    full = LR.host_layout(L, runs, want, room, hints=True)
+    count = LR.host_layout(L, runs, want, room, hints=True, lines=False)
+    plain = LR.host_layout(L, runs, want, room)
+    assert (full["sample_words"], full["hint_lines"]) == (st[0], st[2])
+    assert [count[k] for k in LR.STATS[:8]] == [full[k] for k in LR.STATS[:8]] == [plain[k] for k in LR.STATS[:8]]
+    assert np.array_equal(count["group"], full["group"]) and (count["sample_words"], count["hint_lines"]) == (0, 0)
+    assert full["sel"].size == full["sel_words"] and np.count_nonzero(full["sel"]) <= st[0]
+    # the hinted lines differ from the plain ones in the flag (bit 29 of dword 1) and the two hint dwords, nowhere else
+    a, b = full["dwords"], plain["dwords"]
+    differ = np.nonzero((a != b).any(axis=1))[0]
+    flagged = np.nonzero(((a[:, 1] ^ b[:, 1]) >> 29) & 1)[0] if not room else None
+    if room:  # (the flag is laid out with the line; a hint replaces HINT_NONE in its slot)
+        assert len(differ) == st[2] and (differ % 17 != 16).all() and differ.max(initial=0) < full["groups"] * 17
+    else:
+        assert np.array_equal(differ, flagged) and len(flagged) == st[2]
+    rest = a.copy()
+    rest[differ, 1] = b[differ, 1]
+    rest[differ, 29:32] = b[differ, 29:32]
+    assert np.array_equal(rest, b)
+
+
+@pytest.mark.parametrize("style,R,span", PSI_MATRIX)
 @pytest.mark.parametrize("room", [False, True])
 def test_select_samples_and_psi_hints_are_exact(rsb, style, R, span, room):
     """The select samples name the window of EVERY occurrence (or bound it from below where they say so, and the floor
@@ -97,15 +197,7 @@ def test_select_samples_and_psi_hints_are_exact(rsb, style, R, span, room):
     the naive BWT at every position -- host run of the code the GPU runs.  room: the RSBWT_OPEN_READS layout (a hint
     slot in every window line, one sample per 4,096 occurrences)."""
     L = rsb.lib()
-    rng = np.random.default_rng(R * 7 + span)
-    if style == "pop":
-        runs = np.empty(R, np.uint8)
-        assert L.rsbwt_synth_runs_host(runs.ctypes.data, R, 77 | (1 << 62)) == 0
-    elif style == "desert":  # stretches without one symbol: sample blocks spread over many windows
-        sym = np.where((np.arange(R) // 7000) % 2 == 0, rng.integers(0, 5, R), rng.integers(0, 4, R))
-        runs = ((sym.astype(np.uint8)) << 5) | rng.integers(1, 9, R).astype(np.uint8)
-    else:
-        runs = _runs(style, R, rng, L)
+    runs = _psi_runs(style, R, span, L)
     st = (C.c_uint64 * 4)()
     bad = C.c_uint64()
     n = int((runs & 31).astype(np.int64).sum())

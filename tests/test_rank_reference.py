@@ -5,6 +5,7 @@ sweeps held to what it relies on (how much of them lies past a line's own pieces
 import numpy as np
 import pytest
 
+import layout_reference as LR
 import rank_reference as R
 import test_kmer_fixtures as F
 
@@ -154,12 +155,9 @@ def golden_layout(rsb, runs, n, room):
     """the builder's choice of span (csrc/build_lines.hip): 88 pieces per window at the mean run length -- 88 * 88 / 96 with
     room for a psi hint -- shrunk by 5 % (1.25 %) while more than 2.5 % of the positions spill or more than 1.5 % of the
     windows need far lines; the statistics are rsbwt_layout_selftest_host's at each span tried"""
-    S = int((88.0 * 88 / 96 if room else 88.0) * (n / runs.size) + 0.5)
-    for attempt in range(17 if room else 5):
-        st = F.selftest(rsb, runs, S, room)
-        if st[5] * 40 <= n and st[4] * 200 <= ((n + S - 1) // S) * 3:
-            break
-        S = int(S * (0.9875 if room else 0.95))
+    # (the rule itself is tests/layout_reference.py's, shared with the GPU builder's byte tests; this BWT has far fewer
+    # than the 4,096 groups at which the builder first tries its spans on a sample)
+    st, _ = LR.choose_span(n, runs.size, room, lambda S: (F.selftest(rsb, runs, S, room), None))
     return st
 
 

@@ -862,6 +862,24 @@ int rsbwt_pack_kmers_dev(const void *d_kmers, size_t Q, uint32_t k, size_t strid
 
 namespace rsb {
 
+// One metered launch: under the meter's lock, with the meter's counters (a counting launch; zeroed first unless the
+// launch adds to the one before it) and the next pair of its event ring.  launch(work, ev0, ev1) enqueues; `what` names
+// it in the error.
+template <class F>
+static int metered_launch(search_meter &m, hipStream_t stream, bool zero_work, const char *what, F &&launch) {
+    std::lock_guard<std::mutex> lock(m.mu);
+    unsigned long long *work = m.counting ? m.d_work : nullptr;
+    if (work && zero_work) HIP_OK(hipMemsetAsync(work, 0, WORK_WORDS * sizeof(unsigned long long), stream));
+    const int slot = (int)(m.launches % search_meter::RING);
+    const hipError_t e = launch(work, m.ev_start[slot], m.ev_stop[slot]);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail_hip(e, what);
+    }
+    m.launches++;
+    return RSBWT_OK;
+}
+
 // One fused search launch over the shards whose device views are d_views[0..nshards) on the current
 // device, timed and counted through `m`.  k >= 1 (k == 0 is answered on the host by the callers that
 // allow it); k <= 65535 (the resume position of a traced search is a 16-bit field).
@@ -872,56 +890,29 @@ int search_launch(search_meter &m, const shard_view *d_views, uint32_t nshards, 
     if (Q && (!d_packed || !d_valid || !d_lower || (!counts_only && !pairs && !d_upper))) return fail(RSBWT_EINVAL, "null argument");
     if (k == 0) return fail(RSBWT_EINVAL, "k must be at least 1 for device-resident searches");
     if (k > 65535u) return fail(RSBWT_ERANGE, "k %u: at most 65535 symbols per k-mer", k);
-    std::lock_guard<std::mutex> lock(m.mu);
-    unsigned long long *work = nullptr;
-    if (m.counting) {
-        work = m.d_work;
-        HIP_OK(hipMemsetAsync(work, 0, WORK_WORDS * sizeof(unsigned long long), stream));
-    }
-    const int slot = (int)(m.launches % search_meter::RING);
-    hipError_t e = launch_search(m.scratch, d_views, nshards, d_packed, d_valid, Q, k, d_lower, d_upper, counts_only, work, num_cus,
-                                 stream, m.ev_start[slot], m.ev_stop[slot], extra);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail_hip(e, "search kernel launch");
-    }
-    m.launches++;
-    return RSBWT_OK;
+    return metered_launch(m, stream, true, "search kernel launch", [&](unsigned long long *work, hipEvent_t ev0, hipEvent_t ev1) {
+        return launch_search(m.scratch, d_views, nshards, d_packed, d_valid, Q, k, d_lower, d_upper, counts_only, work, num_cus, stream, ev0, ev1,
+                             extra);
+    });
 }
 
 int search_launch_walk(search_meter &m, const shard_view *d_views, uint32_t nshards, int num_cus, const void *d_packed,
                        const void *d_valid, size_t nkmers, uint32_t tn, void *d_worklists, void *d_counts, size_t wl_cap, uint32_t k,
                        void *d_sparse, void *d_hit_bits, hipStream_t stream) {
-    std::lock_guard<std::mutex> lock(m.mu);
-    unsigned long long *work = nullptr;
-    if (m.counting) {
-        work = m.d_work;
-        HIP_OK(hipMemsetAsync(work, 0, WORK_WORDS * sizeof(unsigned long long), stream));
-    }
-    const int slot = (int)(m.launches % search_meter::RING);
-    hipError_t e = launch_search_walk(m.scratch, d_views, nshards, d_packed, d_valid, nkmers, tn, d_worklists, d_counts, wl_cap, k, d_sparse,
-                                      d_hit_bits, work, num_cus, stream, m.ev_start[slot], m.ev_stop[slot]);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail_hip(e, "1-mismatch walk kernel launch");
-    }
-    m.launches++;
-    return RSBWT_OK;
+    return metered_launch(m, stream, true, "1-mismatch walk kernel launch", [&](unsigned long long *work, hipEvent_t ev0, hipEvent_t ev1) {
+        return launch_search_walk(m.scratch, d_views, nshards, d_packed, d_valid, nkmers, tn, d_worklists, d_counts, wl_cap, k, d_sparse,
+                                  d_hit_bits, work, num_cus, stream, ev0, ev1);
+    });
 }
 
+// (its counters accumulate onto the walk's: capi_internal.h)
 int search_launch_worklist(search_meter &m, const shard_view *d_views, uint32_t nshards, int num_cus, const void *d_packed,
                            const void *d_valid, size_t nkmers, uint32_t tn, const void *d_worklists, const void *d_counts, size_t wl_cap,
                            uint32_t k, void *d_sparse, void *d_hit_bits, hipStream_t stream, const void *d_pre) {
-    std::lock_guard<std::mutex> lock(m.mu);
-    const int slot = (int)(m.launches % search_meter::RING);
-    hipError_t e = launch_search_worklist(m.scratch, d_views, nshards, d_packed, d_valid, nkmers, tn, d_worklists, d_counts, wl_cap, k, d_sparse,
-                                          d_hit_bits, m.counting ? m.d_work : nullptr, num_cus, stream, m.ev_start[slot], m.ev_stop[slot], d_pre);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail_hip(e, "worklist search kernel launch");
-    }
-    m.launches++;
-    return RSBWT_OK;
+    return metered_launch(m, stream, false, "worklist search kernel launch", [&](unsigned long long *work, hipEvent_t ev0, hipEvent_t ev1) {
+        return launch_search_worklist(m.scratch, d_views, nshards, d_packed, d_valid, nkmers, tn, d_worklists, d_counts, wl_cap, k, d_sparse,
+                                      d_hit_bits, work, num_cus, stream, ev0, ev1, d_pre);
+    });
 }
 
 }  // namespace rsb

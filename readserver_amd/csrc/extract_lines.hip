@@ -749,6 +749,42 @@ move_prefix_kernel(uint8_t *__restrict__ out, uint32_t stride, const uint32_t *_
     }
 }
 
+// Workgroups: what is resident at once (4 per CU: 99 of 128 VGPRs, 32 KB of LDS each) and no more.  A walk kernel
+// ends in a tail as long as its longest walk (a few hundred passes, most lanes idle), so the more rows each lane
+// walks before that tail the better: the shards of a set are walked by ONE launch (a launch per shard, side by
+// side on streams of the set -- round 3 -- queued the shards' grids behind one another: every lane walked 8 rows
+// instead of 60 and a third of the lane-passes were idle).  RSBWT_EXTRACT_WGS_PER_CU overrides the 4 (A/B knob,
+// tools/README.md)
+static size_t extract_wgs_per_cu() {
+    static const size_t v = (size_t)knob_int("RSBWT_EXTRACT_WGS_PER_CU", 1, 20, RSB_WALK_MIN_WGS);
+    return v;
+}
+
+// The three launches of an extraction: the prefix walk, the move of every prefix to the front of its row buffer, the
+// postfix walk -- over `total` rows: n of each shard, or (RAGGED, n = 0) the shards' segments as seg cuts them.
+template <bool RAGGED, bool CW>
+static hipError_t launch_walks(scratch_cache &scratch, const shard_view *d_shards, uint32_t nshards, const uint64_t *rows, size_t n, size_t total,
+                               const uint64_t *seg, size_t seg_stride, uint8_t *out, uint32_t stride, uint32_t *plen, uint32_t *len, int num_cus,
+                               hipStream_t stream, unsigned long long *d_work) {
+    // (the shards' row counters a line group apart, as the search kernels' query pools are: kernels.h, POOL_STRIDE)
+    pool_lease mem(scratch, stream, 0, 2, nshards);
+    if (mem.error() != hipSuccess) return mem.error();
+    // grid: every shard starts with as many workgroups as any other; rows per draw from a shard's counter: every wave
+    // launched draws twice or more (launch_plan.h)
+    const size_t g = plan_grid(total, 64 * XWG_WAVES, resident_cap(num_cus, extract_wgs_per_cu()), nshards);
+    const uint32_t row_chunk = plan_draw(ROW_CHUNK, 1, g * XWG_WAVES, 2, total);
+    hipLaunchKernelGGL((extract_prefix_wave_kernel<CW, RAGGED>), dim3((unsigned)g), dim3(64 * XWG_WAVES), 0, stream, d_shards, nshards, rows, n, out,
+                       stride, plen, mem.pool(0, nshards), d_work, row_chunk, seg, seg_stride);
+    // (the row buffers of the shards lie back to back: one launch moves every prefix)
+    if ((stride & 15u) == 0u && ((uintptr_t)out & 15u) == 0u)
+        hipLaunchKernelGGL(move_prefix16_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, stream, out, stride, (const uint32_t *)plen, total);
+    else
+        hipLaunchKernelGGL(move_prefix_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, stream, out, stride, (const uint32_t *)plen, total);
+    hipLaunchKernelGGL((extract_postfix_wave_kernel<CW, RAGGED>), dim3((unsigned)g), dim3(64 * XWG_WAVES), 0, stream, d_shards, nshards, rows, n, out,
+                       stride, (const uint32_t *)plen, len, mem.pool(1, nshards), CW ? d_work + XW_WORDS : nullptr, row_chunk, seg, seg_stride);
+    return hipGetLastError();
+}
+
 hipError_t launch_extract_wave(scratch_cache &scratch, const shard_view *d_shards, uint32_t nshards, const void *d_rows,
                                size_t n, void *d_out, uint32_t stride, void *d_plen, void *d_len, int num_cus,
                                hipStream_t stream, unsigned long long *d_work) {
@@ -764,64 +800,9 @@ hipError_t launch_extract_wave(scratch_cache &scratch, const shard_view *d_shard
         }
         return hipSuccess;
     }
-    scratch_cache::lease mem;
-    // (the shards' row counters a line group apart, as the search kernels' query pools are: adjacent counters are one
-    // line of one L2 channel that every wave of a small launch, and of any launch's tail, hits with atomics)
-    const size_t pool_bytes = 2 * (size_t)nshards * POOL_STRIDE * sizeof(unsigned long long);
-    hipError_t e = scratch.take(pool_bytes, stream, &mem);
-    if (e != hipSuccess) return e;
-    unsigned long long *pool = (unsigned long long *)mem.p;
-    e = hipMemsetAsync(pool, 0, pool_bytes, stream);
-    if (e != hipSuccess) {
-        scratch.give(mem, stream);
-        return e;
-    }
-    const size_t total = n * (size_t)nshards;
-    size_t g = (total + 64 * XWG_WAVES - 1) / (64 * XWG_WAVES);
-    // Workgroups: what is resident at once (4 per CU: 99 of 128 VGPRs, 32 KB of LDS each) and no more.  A walk kernel
-    // ends in a tail as long as its longest walk (a few hundred passes, most lanes idle), so the more rows each lane
-    // walks before that tail the better: the shards of a set are walked by ONE launch (a launch per shard, side by
-    // side on streams of the set -- round 3 -- queued the shards' grids behind one another: every lane walked 8 rows
-    // instead of 60 and a third of the lane-passes were idle).  RSBWT_EXTRACT_WGS_PER_CU overrides the 4 (A/B knob,
-    // tools/README.md)
-    static const size_t wgs_per_cu = [] {
-        const char *e = getenv("RSBWT_EXTRACT_WGS_PER_CU");
-        const int v = e ? atoi(e) : 0;
-        return (size_t)(v > 0 && v <= 20 ? v : RSB_WALK_MIN_WGS);
-    }();
-    const size_t cap = (size_t)num_cus * wgs_per_cu;
-    if (g > cap) g = cap;
-    if (g >= nshards) g -= g % nshards;  // (every shard starts with as many workgroups as any other)
-    // rows per draw from a shard's counter: ROW_CHUNK for a launch that fills the chip, fewer for a small one so that
-    // every wave launched draws twice or more (until round 5 a call of a few hundred rows -- the rows of a service
-    // window's intervals -- gave all of them to the first wave that asked: 242 rows took four walks one after the other,
-    // 1.24 ms, tools/probe_setquery.py)
-    uint32_t row_chunk = ROW_CHUNK;
-    while (row_chunk > 1u && (size_t)row_chunk * g * XWG_WAVES * 2u > total) row_chunk >>= 1;
-    if (d_work)
-        hipLaunchKernelGGL(extract_prefix_wave_kernel<true>, dim3((unsigned)g), dim3(64 * XWG_WAVES), 0, stream, d_shards, nshards,
-                           (const uint64_t *)d_rows, n, (uint8_t *)d_out, stride, (uint32_t *)d_plen, pool, d_work, row_chunk);
-    else
-        hipLaunchKernelGGL(extract_prefix_wave_kernel<false>, dim3((unsigned)g), dim3(64 * XWG_WAVES), 0, stream, d_shards, nshards,
-                           (const uint64_t *)d_rows, n, (uint8_t *)d_out, stride, (uint32_t *)d_plen, pool, d_work, row_chunk);
-    // (the row buffers of the shards lie back to back: one launch moves every prefix)
-    if ((stride & 15u) == 0u && ((uintptr_t)d_out & 15u) == 0u)
-        hipLaunchKernelGGL(move_prefix16_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, stream, (uint8_t *)d_out, stride,
-                           (const uint32_t *)d_plen, total);
-    else
-        hipLaunchKernelGGL(move_prefix_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, stream, (uint8_t *)d_out, stride,
-                           (const uint32_t *)d_plen, total);
-    if (d_work)
-        hipLaunchKernelGGL(extract_postfix_wave_kernel<true>, dim3((unsigned)g), dim3(64 * XWG_WAVES), 0, stream, d_shards, nshards,
-                           (const uint64_t *)d_rows, n, (uint8_t *)d_out, stride, (const uint32_t *)d_plen, (uint32_t *)d_len,
-                           pool + (size_t)nshards * POOL_STRIDE, d_work + XW_WORDS, row_chunk);
-    else
-        hipLaunchKernelGGL(extract_postfix_wave_kernel<false>, dim3((unsigned)g), dim3(64 * XWG_WAVES), 0, stream, d_shards, nshards,
-                           (const uint64_t *)d_rows, n, (uint8_t *)d_out, stride, (const uint32_t *)d_plen, (uint32_t *)d_len,
-                           pool + (size_t)nshards * POOL_STRIDE, d_work + XW_WORDS, row_chunk);
-    e = hipGetLastError();
-    scratch.give(mem, stream);
-    return e;
+    const auto walks = d_work ? launch_walks<false, true> : launch_walks<false, false>;
+    return walks(scratch, d_shards, nshards, (const uint64_t *)d_rows, n, n * (size_t)nshards, nullptr, 0, (uint8_t *)d_out, stride, (uint32_t *)d_plen,
+                 (uint32_t *)d_len, num_cus, stream, d_work);
 }
 
 // (the ragged form: the same three launches over `total` rows cut into the shards' segments)
@@ -830,38 +811,8 @@ hipError_t launch_extract_ragged(scratch_cache &scratch, const shard_view *d_sha
                                  hipStream_t stream) {
     if (total == 0 || nshards == 0) return hipSuccess;
     if (total >= (1ull << 31) || !d_seg) return hipErrorInvalidValue;  // (the walk kernels number a shard's rows in 32 bits)
-    scratch_cache::lease mem;
-    const size_t pool_bytes = 2 * (size_t)nshards * POOL_STRIDE * sizeof(unsigned long long);
-    hipError_t e = scratch.take(pool_bytes, stream, &mem);
-    if (e != hipSuccess) return e;
-    unsigned long long *pool = (unsigned long long *)mem.p;
-    e = hipMemsetAsync(pool, 0, pool_bytes, stream);
-    if (e != hipSuccess) {
-        scratch.give(mem, stream);
-        return e;
-    }
-    // (grid and rows per draw: launch_extract_wave's rules)
-    size_t g = (total + 64 * XWG_WAVES - 1) / (64 * XWG_WAVES);
-    const size_t cap = (size_t)num_cus * RSB_WALK_MIN_WGS;
-    if (g > cap) g = cap;
-    if (g >= nshards) g -= g % nshards;
-    uint32_t row_chunk = ROW_CHUNK;
-    while (row_chunk > 1u && (size_t)row_chunk * g * XWG_WAVES * 2u > total) row_chunk >>= 1;
-    hipLaunchKernelGGL((extract_prefix_wave_kernel<false, true>), dim3((unsigned)g), dim3(64 * XWG_WAVES), 0, stream, d_shards, nshards,
-                       (const uint64_t *)d_rows, (size_t)0, (uint8_t *)d_out, stride, (uint32_t *)d_plen, pool, (unsigned long long *)nullptr,
-                       row_chunk, (const uint64_t *)d_seg, seg_stride);
-    if ((stride & 15u) == 0u && ((uintptr_t)d_out & 15u) == 0u)
-        hipLaunchKernelGGL(move_prefix16_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, stream, (uint8_t *)d_out, stride,
-                           (const uint32_t *)d_plen, total);
-    else
-        hipLaunchKernelGGL(move_prefix_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, stream, (uint8_t *)d_out, stride,
-                           (const uint32_t *)d_plen, total);
-    hipLaunchKernelGGL((extract_postfix_wave_kernel<false, true>), dim3((unsigned)g), dim3(64 * XWG_WAVES), 0, stream, d_shards, nshards,
-                       (const uint64_t *)d_rows, (size_t)0, (uint8_t *)d_out, stride, (const uint32_t *)d_plen, (uint32_t *)d_len,
-                       pool + (size_t)nshards * POOL_STRIDE, (unsigned long long *)nullptr, row_chunk, (const uint64_t *)d_seg, seg_stride);
-    e = hipGetLastError();
-    scratch.give(mem, stream);
-    return e;
+    return launch_walks<true, false>(scratch, d_shards, nshards, (const uint64_t *)d_rows, 0, total, (const uint64_t *)d_seg, seg_stride,
+                                     (uint8_t *)d_out, stride, (uint32_t *)d_plen, (uint32_t *)d_len, num_cus, stream, nullptr);
 }
 
 }  // namespace rsb

@@ -1,5 +1,5 @@
-// kernels.h -- host-side launchers of the query kernels (kernels.hip, search_lines.hip) and of the
-// index builder (build_lines.hip).
+// kernels.h -- host-side launchers of every kernel of the library (the .hip files of this directory: each declaration
+// names its own) and the scratch they lease.
 #ifndef RSBWT_KERNELS_H
 #define RSBWT_KERNELS_H
 
@@ -9,6 +9,7 @@
 
 #include <mutex>
 
+#include "launch_plan.h"
 #include "line_format.h"
 
 namespace rsb {
@@ -43,13 +44,44 @@ class scratch_cache {
     std::mutex mu_;
 };
 
+// the search kernels' query pools (one counter per shard, drawn from by every wave of the launch) sit POOL_STRIDE u64
+// apart, as the worklists' lengths do (WL_COUNT_STRIDE): eight adjacent counters are one line of one L2 channel, and a
+// small batch -- 4,096 waves probing eight drained pools each -- then waits on that line longer than it searches (0.58
+// against 0.32 ms for 4e4 31-mers x 8 shards with a quarter of the waves).  The walkers' row counters likewise: every
+// wave of a small launch, and of any launch's tail, hits them with atomics.
+constexpr uint32_t POOL_STRIDE = 32;
+
+// The scratch of one persistent launch sequence on `stream`: front_bytes for the caller (a search's start records) and
+// behind them npools x nshards counters POOL_STRIDE apart, zeroed.  error() says whether both steps went through; the
+// lease goes back when this leaves scope -- after the sequence's last launch was enqueued, which is what give() asks.
+class pool_lease {
+  public:
+    pool_lease(scratch_cache &scratch, hipStream_t stream, size_t front_bytes, uint32_t npools, uint32_t nshards)
+        : scratch_(scratch), stream_(stream) {
+        const size_t pool_bytes = (size_t)npools * nshards * POOL_STRIDE * sizeof(unsigned long long);
+        err_ = scratch.take(front_bytes + pool_bytes, stream, &mem_);
+        if (err_ != hipSuccess) return;
+        pools_ = (unsigned long long *)((char *)mem_.p + front_bytes);
+        err_ = hipMemsetAsync(pools_, 0, pool_bytes, stream);
+    }
+    ~pool_lease() { scratch_.give(mem_, stream_); }  // (nothing taken: slot -1, nothing given)
+    pool_lease(const pool_lease &) = delete;
+    pool_lease &operator=(const pool_lease &) = delete;
+    hipError_t error() const { return err_; }
+    void *front() const { return mem_.p; }
+    unsigned long long *pool(uint32_t i, uint32_t nshards) const { return pools_ + (size_t)i * nshards * POOL_STRIDE; }
+
+  private:
+    scratch_cache &scratch_;
+    hipStream_t stream_;
+    scratch_cache::lease mem_;
+    unsigned long long *pools_ = nullptr;
+    hipError_t err_;
+};
+
 hipError_t launch_pack(const void *d_kmers, size_t Q, uint32_t k, size_t stride, void *d_packed,
                        void *d_valid, hipStream_t stream);
 
-// search_lines.hip: batched findInterval of Q packed k-mers in each of the nshards shards whose
-// views are the device array d_shards (all on the current device).  d_lower/d_upper: [nshards][Q]
-// (d_lower alone receives counts with counts_only).  ev0/ev1 (optional) are recorded on `stream`
-// immediately around the search kernel itself.
 // words of the hit map of Q searches (one bit per search, a whole number of 16-byte units: the maps of a launch's
 // shards lie back to back)
 __host__ __device__ inline size_t hit_map_words(size_t Q) { return ((Q + 127) / 128) * 2; }
@@ -86,6 +118,10 @@ hipError_t launch_pack_var(const void *d_text, const void *d_off, size_t Q, uint
                            hipStream_t stream);
 hipError_t launch_search_init_var(const shard_view *d_shards, uint32_t nshards, const void *d_packed, const void *d_valid,
                                   const void *d_len, size_t Q, uint32_t wpq, void *d_init, hipStream_t stream);
+// search_lines.hip: batched findInterval of Q packed k-mers in each of the nshards shards whose
+// views are the device array d_shards (all on the current device).  d_lower/d_upper: [nshards][Q]
+// (d_lower alone receives counts with counts_only).  ev0/ev1 (optional) are recorded on `stream`
+// immediately around the search kernel itself.
 hipError_t launch_search(scratch_cache &scratch, const shard_view *d_shards, uint32_t nshards, const void *d_packed,
                          const void *d_valid, size_t Q, uint32_t k, void *d_lower, void *d_upper, bool counts_only,
                          unsigned long long *d_work, int num_cus, hipStream_t stream, hipEvent_t ev0 = nullptr,
@@ -114,11 +150,6 @@ hipError_t launch_dollar_count(const shard_view *d_shards, uint32_t nshards, con
 // (the lists' lengths sit WL_COUNT_STRIDE u64 apart: appended to by every wave of the branch kernel, they must not share
 // a cache line -- eight counters in one line serialised the kernel at one atomic at a time: 10 ms instead of 3)
 constexpr uint32_t WL_COUNT_STRIDE = 32;
-// the search kernels' query pools (one counter per shard, drawn from by every wave of the launch) sit POOL_STRIDE u64
-// apart too: eight adjacent counters are one line of one L2 channel, and a small batch -- 4,096 waves probing eight
-// drained pools each -- then waits on that line longer than it searches (0.58 against 0.32 ms for 4e4 31-mers x 8 shards
-// with a quarter of the waves)
-constexpr uint32_t POOL_STRIDE = 32;
 hipError_t launch_mm1_worklists(const shard_view *d_shards, uint32_t nshards, const void *d_packed, const void *d_valid, size_t m,
                                 uint32_t k, uint32_t tn, const void *d_trace, const void *d_own, void *d_worklists, size_t wl_cap,
                                 void *d_counts, void *d_sparse, void *d_hit_bits, int num_cus, hipStream_t stream,

@@ -311,9 +311,7 @@ int kmer_ident_shard(rsbwt_t *h, const kr_segments &sg, const std::string &text,
     KR_HIP(hipMemcpyAsync(d_len, sg.chklen.data(), nseg * 4, hipMemcpyHostToDevice, st));
     if (!text.empty()) KR_HIP(hipMemcpyAsync(d_text, text.data(), text.size(), hipMemcpyHostToDevice, st));
     KR_HIP(hipMemsetAsync(d_misc, 0, a_misc, st));
-    size_t g = (size_t)((ncand + 64 * KR_WAVES - 1) / (64 * KR_WAVES));
-    const size_t cap = (size_t)h->num_cus * 4;
-    if (g > cap) g = cap;
+    const size_t g = plan_grid((size_t)ncand, 64 * KR_WAVES, resident_cap(h->num_cus, 4));
     hipLaunchKernelGGL(kr_ident_kernel, dim3((uint32_t)g), dim3(64 * KR_WAVES), 0, st, h->d_view, d_first, d_lo, d_pred, d_chk, d_len, nseg,
                        d_text, ncand, d_par, d_id, d_misc, d_misc + 8);
     KR_HIP(hipGetLastError());
@@ -478,11 +476,7 @@ int kmer_reads_batch(rsbwt_set_t *set, const std::vector<kmer_job> &jobs, size_t
     auto has_rows = [&](size_t g) { return tiles[g].s.size() < MAXL; };  // (|tile| >= max_read_length: sub-tiles only)
     // ---- jobs into passes: the ordinary ones together, every job with more than `wide` candidate rows on its own
     // (RSBWT_KMER_WIDE_ROWS overrides the 2^22: tests/test_gpu_kmer_match.py)
-    const uint64_t wide = [] {
-        const char *e = getenv("RSBWT_KMER_WIDE_ROWS");
-        const long long v = e ? atoll(e) : 0;
-        return v > 0 ? (uint64_t)v : (1ull << 22);
-    }();
+    const uint64_t wide = (uint64_t)knob_int("RSBWT_KMER_WIDE_ROWS", 1, LLONG_MAX, 1ll << 22);
     std::vector<std::vector<size_t>> passes(1);
     for (size_t j = 0; j < J; ++j) {
         uint64_t c = 0;

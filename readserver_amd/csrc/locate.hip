@@ -282,33 +282,17 @@ hipError_t launch_locate(scratch_cache &scratch, const shard_view *d_shards, uin
                          int num_cus, hipStream_t stream) {
     if (n == 0 || nshards == 0) return hipSuccess;
     if (!d_shard_of && nshards != 1) return hipErrorInvalidValue;
-    scratch_cache::lease mem;
-    const size_t pool_bytes = (size_t)nshards * POOL_STRIDE * sizeof(unsigned long long);
-    hipError_t e = scratch.take(pool_bytes, stream, &mem);
-    if (e != hipSuccess) return e;
-    unsigned long long *pool = (unsigned long long *)mem.p;
-    e = hipMemsetAsync(pool, 0, pool_bytes, stream);
-    if (e != hipSuccess) {
-        scratch.give(mem, stream);
-        return e;
-    }
-    // (grid: launch_extract_wave's rules -- what is resident at once and no more, every shard starting with as many
-    // workgroups as any other)
-    size_t g = (n + 64 * LC_WAVES - 1) / (64 * LC_WAVES);
-    const size_t cap = (size_t)num_cus * RSB_WALK_MIN_WGS;
-    if (g > cap) g = cap;
-    if (g >= nshards) g -= g % nshards;
-    if (g == 0) g = 1;
+    pool_lease mem(scratch, stream, 0, 1, nshards);
+    if (mem.error() != hipSuccess) return mem.error();
+    // (grid: the extraction's rules -- what is resident at once and no more, every shard starting with as many
+    // workgroups as any other; launch_plan.h)
+    const size_t g = plan_grid(n, 64 * LC_WAVES, resident_cap(num_cus, RSB_WALK_MIN_WGS), nshards, 1);
     // entries per draw: every wave that starts on a shard draws twice or more from its list, 64 entries at the least
-    const size_t waves_per_shard = std::max<size_t>(1, g * LC_WAVES / nshards);
-    uint32_t row_chunk = 256;
-    while (row_chunk > 64u && (size_t)row_chunk * waves_per_shard * 2u > n) row_chunk >>= 1;
+    const uint32_t row_chunk = plan_draw(256, 64, waves_per_shard(g, LC_WAVES, nshards), 2, n);
     hipLaunchKernelGGL(locate_wave_kernel, dim3((unsigned)g), dim3(64 * LC_WAVES), 0, stream, d_shards, nshards, (const uint32_t *)d_shard_of,
                        (const uint64_t *)d_rows, (uint64_t)n, max_steps ? max_steps : LC_DEFAULT_STEPS, (uint64_t *)d_read_row,
-                       (uint64_t *)d_ordinal, (uint32_t *)d_offset, pool, d_work2, row_chunk);
-    e = hipGetLastError();
-    scratch.give(mem, stream);
-    return e;
+                       (uint64_t *)d_ordinal, (uint32_t *)d_offset, mem.pool(0, nshards), d_work2, row_chunk);
+    return hipGetLastError();
 }
 
 namespace {

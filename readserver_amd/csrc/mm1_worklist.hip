@@ -276,10 +276,7 @@ hipError_t launch_mm1_worklists(const shard_view *d_shards, uint32_t nshards, co
     const size_t no = m * nshards;
     hipLaunchKernelGGL(wl_own_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, stream, (const ulonglong2 *)d_own,
                        (const uint8_t *)d_valid, nshards, m, k, (ulonglong2 *)d_sparse, (unsigned long long *)d_hit_bits, mv);
-    const size_t items = m * (size_t)tn;
-    size_t g = (items + 64 * WG_WAVES - 1) / (64 * WG_WAVES);
-    const size_t cap = (size_t)num_cus * RSB_MIN_WGS_PER_CU;
-    if (g > cap) g = cap;
+    const size_t g = plan_grid(m * (size_t)tn, 64 * WG_WAVES, resident_cap(num_cus, RSB_MIN_WGS_PER_CU));
     hipLaunchKernelGGL(wl_branch_kernel, dim3((unsigned)g), dim3(64 * WG_WAVES), 0, stream, d_shards, nshards, (const uint64_t *)d_packed,
                        (const uint8_t *)d_valid, m, k, tn, (const ulonglong2 *)d_trace, (ulonglong2 *)d_worklists, wl_cap,
                        (unsigned long long *)d_counts, (ulonglong2 *)d_sparse, (unsigned long long *)d_hit_bits, mv, d_branch_work);

@@ -22,6 +22,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "kernels.h"
 #include "line_format.h"
 #include "rank_device.h"
@@ -698,26 +700,48 @@ namespace rsb {
 static int search_kernel_choice() {
     static const int choice = [] {
         const char *e = getenv("RSBWT_SEARCH_KERNEL");
-        if (e && !strcmp(e, "pair")) return 0;
-        if (e && !strcmp(e, "solo")) return 1;
-        return 2;
+        if (e && !strcmp(e, "pair")) return SEARCH_PAIR;
+        if (e && !strcmp(e, "solo")) return SEARCH_SOLO;
+        return SEARCH_AUTO;
     }();
     return choice;
 }
+
+// Workgroups per CU: LDS admits 5 (20 waves), but 4 are as fast (the request path, not the
+// number of lookups in flight, is what saturates) and leave 32 KB of LDS and wave slots per CU
+// to kernels that run beside the search -- RCCL's, when the previous batch's intervals are
+// gathered at N > 1.  RSBWT_WAVE_WGS_PER_CU overrides.
+static size_t wave_wgs_per_cu() {
+    static const size_t v = (size_t)knob_int("RSBWT_WAVE_WGS_PER_CU", 1, INT_MAX, RSB_MIN_WGS_PER_CU);
+    return v;
+}
+
+// what a search launch may occupy: the resident workgroups less RSBWT_SEARCH_SPARE_WGS (launch_plan.h)
+static size_t search_cap(int num_cus, size_t wgs_per_cu) {
+    static const size_t spare = (size_t)knob_int("RSBWT_SEARCH_SPARE_WGS", 1, LLONG_MAX, 0);
+    return resident_cap(num_cus, wgs_per_cu, spare);
+}
+
+// a runtime bool as a template argument of what f launches: f(std::true_type) or f(std::false_type)
+template <class F>
+static void with_flag(bool b, F &&f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+#define FLAG(x) decltype(x)::value
 
 template <bool CW, bool CO>
 static void launch_solo(int grid, hipStream_t stream, const shard_view *shards, uint32_t nshards, const uint64_t *pk,
                         const ulonglong2 *init, const uint8_t *valid, unsigned long long *ctr, size_t Q, uint32_t k, uint32_t wpq,
                         uint64_t *lo, uint64_t *up, unsigned long long *work, ulonglong2 *trace, uint32_t trace_n,
                         uint32_t pairs, bool fused) {
-    uint32_t qchunk = 1024;
-    while (qchunk > 64u && (size_t)qchunk * (size_t)grid * WG_WAVES * 4u > Q * nshards) qchunk >>= 1;
+    const uint32_t qchunk = plan_draw(1024, 64, (size_t)grid * WG_WAVES, 4, Q * nshards);
     // results staged in LDS and stored a whole 1 KB group at a time (search_solo.h, STAGED RESULTS): 8 KB of dynamic
     // LDS per workgroup on top of the 32 KB of line slots -- four workgroups then fill a CU's 160 KB.
     // RSBWT_NO_STAGED_RESULTS: A/B knob (tools/README.md); also what leaves LDS to kernels running beside the search.
-    static const bool no_staged = getenv("RSBWT_NO_STAGED_RESULTS") != nullptr;
+    static const bool no_staged = knob_set("RSBWT_NO_STAGED_RESULTS");
     const bool staged = !CO && pairs != 2u && !no_staged;
-    static const bool count_unstaged = getenv("RSBWT_COUNT_UNSTAGED") != nullptr;  // probe knob (tools/README.md)
+    static const bool count_unstaged = knob_set("RSBWT_COUNT_UNSTAGED");  // probe knob (tools/README.md)
     const uint32_t pa = pairs | (staged ? SOLO_STAGED_RESULTS : 0u) | (CW && count_unstaged ? SOLO_COUNT_UNSTAGED : 0u);
     const size_t dyn = staged ? SOLO_RESULTS_LDS : 0u;  // (WG_WAVES x RES_WAVE_LDS: search_solo.h)
     if (fused)  // (one shard, k <= 32, a k-mer table, no trace: the kernel makes its own start records)
@@ -736,11 +760,7 @@ static void launch_k(int grid, hipStream_t stream, const shard_view *shards, uin
                      const ulonglong2 *init, unsigned long long *ctr, size_t Q, uint32_t k, uint32_t wpq,
                      uint64_t *lo, uint64_t *up, unsigned long long *work, ulonglong2 *trace, uint32_t trace_n,
                      uint32_t pairs) {
-    // queries per draw from the pool: at least ~4 draws per wave, so that a batch of a few
-    // thousand queries (a service micro-batch, the k-mers of a 1-mismatch slice) still occupies
-    // every wave launched instead of the first few
-    uint32_t qchunk = 1024;
-    while (qchunk > 32u && (size_t)qchunk * (size_t)grid * WG_WAVES * 4u > Q * nshards) qchunk >>= 1;
+    const uint32_t qchunk = plan_draw(1024, 32, (size_t)grid * WG_WAVES, 4, Q * nshards);
     if (wpq > 1)
         hipLaunchKernelGGL((search_lines_kernel<CW, CO, true, 0>), dim3(grid), dim3(64 * WG_WAVES), 0, stream, shards, nshards,
                            pk, init, ctr, Q, k, wpq, lo, up, work, trace, trace_n, qchunk, pairs);
@@ -751,8 +771,8 @@ static void launch_k(int grid, hipStream_t stream, const shard_view *shards, uin
 
 static void launch_init(const shard_view *d_shards, uint32_t nshards, const uint64_t *pk, const uint8_t *vd, size_t Q, uint32_t k,
                         uint32_t wpq, ulonglong2 *init, hipStream_t stream) {
-    static const bool untiled = getenv("RSBWT_INIT_UNTILED") != nullptr;  // A/B knob (tools/README.md)
-    static const bool one_per_thread = getenv("RSBWT_INIT_ONE_PER_THREAD") != nullptr;  // A/B knob (tools/README.md)
+    static const bool untiled = knob_set("RSBWT_INIT_UNTILED");  // A/B knob (tools/README.md)
+    static const bool one_per_thread = knob_set("RSBWT_INIT_ONE_PER_THREAD");  // A/B knob (tools/README.md)
     if (nshards >= 2u && nshards <= 256u && !untiled && wpq == 1u && !one_per_thread) {
         const uint32_t V = 256u / nshards;
         hipLaunchKernelGGL(search_init_tiled4_kernel, dim3((unsigned)((Q + (size_t)V * INIT_U - 1) / ((size_t)V * INIT_U))), dim3(256), 0, stream,
@@ -798,109 +818,57 @@ hipError_t launch_search(scratch_cache &scratch, const shard_view *d_shards, uin
     ulonglong2 *trace = extra ? (ulonglong2 *)extra->d_trace_out : nullptr;
     const uint32_t trace_n = extra ? extra->trace_n : 0u;
     const uint32_t wpq = (k + 31u) / 32u ? (k + 31u) / 32u : 1u;
-    // one lane per search (search_solo.h) where intervals are narrow for most of a search: shards whose
-    // k-mer tables are deep (extra->narrow: what is left of a hit are steps inside one window); behind
-    // a shallow table the first steps are wide, where pairs take one pass and a lone lane two
-    // (and only when the batch fills every lane of the launch: below that nothing is saturated and the
-    // pairs answer sooner -- a lone request of the service loop takes half the passes).
-    // Until round 5 several shards per launch stayed on lane pairs ("at the request ceiling already"): the
-    // launch is bound by the instructions a SIMD issues, not by requests (+ 12.6 % VALU = + 5.7 %
-    // time, the same build), a pair spends a whole lane on `upper` where 97 % of the steps find it in the line
-    // `lower - 1` staged, and the lone lanes run the headline's 8 x 20 GB shards in 19.05 ms against 20.04
-    const bool table_build = extra && extra->table_build;
-    const int choice = search_kernel_choice();
-    size_t g = 0;
-    // Workgroups per CU: LDS admits 5 (20 waves), but 4 are as fast (the request path, not the
-    // number of lookups in flight, is what saturates) and leave 32 KB of LDS and wave slots per CU
-    // to kernels that run beside the search -- RCCL's, when the previous batch's intervals are
-    // gathered at N > 1.  RSBWT_WAVE_WGS_PER_CU overrides.
-    static const int wgs_per_cu = [] {
-        const char *e = getenv("RSBWT_WAVE_WGS_PER_CU");
-        const int v = e ? atoi(e) : 0;
-        return v > 0 ? v : RSB_MIN_WGS_PER_CU;
-    }();
-    // RSBWT_SEARCH_SPARE_WGS = n: n workgroups fewer than the chip holds.  A search launch is persistent (its workgroups
-    // stay until the batch is done) and fills every CU's registers (4 waves x 128 VGPRs per SIMD) and LDS: a kernel
-    // that should run BESIDE it -- RCCL's, gathering the previous batch at N > 1 -- finds room only on CUs a workgroup
-    // short.  bench.py sets it for its N > 1 ranks (32: a workgroup slot on 32 CUs for the collective's channels).
-    static const size_t spare_wgs = [] {
-        const char *e = getenv("RSBWT_SEARCH_SPARE_WGS");
-        const long v = e ? atol(e) : 0;
-        return (size_t)(v > 0 ? v : 0);
-    }();
-    const size_t cap_all = (size_t)num_cus * (size_t)wgs_per_cu;
-    const size_t cap = cap_all > 2 * spare_wgs ? cap_all - spare_wgs : cap_all;
-    // (the variants of a 1-mismatch search that resume from a trace start on their k-mer's narrow interval and live
-    // 2.4 steps: what bounds their launch is how fast searches are taken up, and a wave of lone lanes takes up 64 per
-    // pass where pairs take 32 -- any number of shards: 25.0 -> 23.5 ms per batch of 4e5 31-mers x 8 shards)
-    const bool resumed = extra && extra->d_trace_in;
-    const bool solo = !table_build && (choice == 1 || (choice == 2 && Q * nshards >= cap * WG_WAVES * 64u &&
-                                                       (resumed || (extra && extra->narrow))));
-    // 32 (pairs) or 64 (solo) searches per wave, 4 waves per workgroup
-    const size_t per_wg = (solo ? 64u : 32u) * WG_WAVES;
-    g = (Q * nshards + per_wg - 1) / per_wg;
-    if (g > cap) g = cap;
-    const int grid = (int)g;
+    const bool table_build = extra && extra->table_build, resumed = extra && extra->d_trace_in;
+    const size_t nrec = Q * nshards;
+    // lane pairs or lone lanes, and the grid (launch_plan.h): 32 (pairs) or 64 (solo) searches per wave, 4 waves per workgroup
+    const size_t cap = search_cap(num_cus, wave_wgs_per_cu());
+    const bool solo = plan_lone_lanes(search_kernel_choice(), table_build, nrec, cap, WG_WAVES, resumed, extra && extra->narrow);
+    const int grid = (int)plan_grid(nrec, (solo ? 64u : 32u) * WG_WAVES, cap);
     const uint64_t *pk = (const uint64_t *)d_packed;
     const uint8_t *vd = (const uint8_t *)d_valid;
     uint64_t *lo = (uint64_t *)d_lower, *up = hit_list ? (uint64_t *)extra->d_hit_bits : (uint64_t *)d_upper;
-    // start records of this batch + the shards' query counters: scratch of this launch sequence
-    // alone, so concurrent calls do not share state
-    const size_t nrec = Q * nshards;
     // a full batch on one shard behind a deep k-mer table (extra->narrow says there is one and k reaches it): the
     // one-lane kernel makes its own start records (search_solo.h, FUSED) -- no start-record launch, no records
-    static const bool no_fused_start = getenv("RSBWT_NO_FUSED_START") != nullptr;  // A/B knob (tools/README.md)
+    static const bool no_fused_start = knob_set("RSBWT_NO_FUSED_START");  // A/B knob (tools/README.md)
     const bool fused = solo && nshards == 1 && extra && extra->narrow && !extra->d_init && !resumed && !trace && wpq == 1 && !no_fused_start;
     const bool prepared = (extra && extra->d_init) || fused;  // the start records exist already / are not needed: only the counters are scratch
-    scratch_cache::lease mem;
-    hipError_t e = scratch.take((prepared ? 0 : nrec * sizeof(ulonglong2)) + nshards * POOL_STRIDE * sizeof(unsigned long long), stream, &mem);
-    if (e != hipSuccess) return e;
     if (counts_only) {  // counts: only the searches that find something store theirs
-        e = hipMemsetAsync(d_lower, 0, nrec * sizeof(uint64_t), stream);
-        if (e != hipSuccess) {
-            scratch.give(mem, stream);
-            return e;
-        }
+        const hipError_t e = hipMemsetAsync(d_lower, 0, nrec * sizeof(uint64_t), stream);
+        if (e != hipSuccess) return e;
     }
-    ulonglong2 *init = fused ? nullptr : prepared ? (ulonglong2 *)extra->d_init : (ulonglong2 *)mem.p;
-    unsigned long long *ctr = prepared ? (unsigned long long *)mem.p : (unsigned long long *)(init + nrec);
-    e = hipMemsetAsync(ctr, 0, nshards * POOL_STRIDE * sizeof(unsigned long long), stream);
-    if (e != hipSuccess) {
-        scratch.give(mem, stream);
-        return e;
-    }
+    // start records of this batch + the shards' query counters: scratch of this launch sequence
+    // alone, so concurrent calls do not share state
+    pool_lease mem(scratch, stream, prepared ? 0 : nrec * sizeof(ulonglong2), 1, nshards);
+    if (mem.error() != hipSuccess) return mem.error();
+    ulonglong2 *init = fused ? nullptr : prepared ? (ulonglong2 *)extra->d_init : (ulonglong2 *)mem.front();
+    unsigned long long *ctr = mem.pool(0, nshards);
     const unsigned ig = (unsigned)((nrec + 255) / 256);
     if (prepared) {
         // nothing to compute
-    } else if (extra && extra->d_trace_in)
+    } else if (resumed)
         hipLaunchKernelGGL(search_init_1mm_kernel, dim3(ig), dim3(256), 0, stream, d_shards, nshards, pk, vd, Q, k, wpq,
                            extra->variants, (const ulonglong2 *)extra->d_trace_in, trace_n, init);
     else
         launch_init(d_shards, nshards, pk, vd, Q, k, wpq, init, stream);
     if (ev0) (void)hipEventRecord(ev0, stream);
-    if (extra && extra->table_build && !d_work && !counts_only && wpq == 1) {
-        uint32_t qchunk = 1024;
-        while (qchunk > 32u && (size_t)qchunk * (size_t)grid * WG_WAVES * 4u > Q * nshards) qchunk >>= 1;
+    if (table_build && !d_work && !counts_only && wpq == 1) {
+        const uint32_t qchunk = plan_draw(1024, 32, (size_t)grid * WG_WAVES, 4, nrec);
         hipLaunchKernelGGL((search_lines_kernel<false, false, false, 1>), dim3(grid), dim3(64 * WG_WAVES), 0, stream, d_shards,
                            nshards, pk, init, ctr, Q, k, wpq, lo, up, d_work, trace, trace_n, qchunk, 0u);
-    } else if (solo) {
-        if (d_work) {
-            if (counts_only) launch_solo<true, true>(grid, stream, d_shards, nshards, pk, init, vd, ctr, Q, k, wpq, lo, up, d_work, trace, trace_n, pairs, fused);
-            else launch_solo<true, false>(grid, stream, d_shards, nshards, pk, init, vd, ctr, Q, k, wpq, lo, up, d_work, trace, trace_n, pairs, fused);
-        } else {
-            if (counts_only) launch_solo<false, true>(grid, stream, d_shards, nshards, pk, init, vd, ctr, Q, k, wpq, lo, up, d_work, trace, trace_n, pairs, fused);
-            else launch_solo<false, false>(grid, stream, d_shards, nshards, pk, init, vd, ctr, Q, k, wpq, lo, up, d_work, trace, trace_n, pairs, fused);
-        }
-    } else if (d_work) {
-        if (counts_only) launch_k<true, true>(grid, stream, d_shards, nshards, pk, init, ctr, Q, k, wpq, lo, up, d_work, trace, trace_n, pairs);
-        else launch_k<true, false>(grid, stream, d_shards, nshards, pk, init, ctr, Q, k, wpq, lo, up, d_work, trace, trace_n, pairs);
     } else {
-        if (counts_only) launch_k<false, true>(grid, stream, d_shards, nshards, pk, init, ctr, Q, k, wpq, lo, up, d_work, trace, trace_n, pairs);
-        else launch_k<false, false>(grid, stream, d_shards, nshards, pk, init, ctr, Q, k, wpq, lo, up, d_work, trace, trace_n, pairs);
+        with_flag(d_work != nullptr, [&](auto cw) {
+            with_flag(counts_only, [&](auto co) {
+                if (solo)
+                    launch_solo<FLAG(cw), FLAG(co)>(grid, stream, d_shards, nshards, pk, init, vd, ctr, Q, k, wpq, lo, up, d_work, trace,
+                                                    trace_n, pairs, fused);
+                else
+                    launch_k<FLAG(cw), FLAG(co)>(grid, stream, d_shards, nshards, pk, init, ctr, Q, k, wpq, lo, up, d_work, trace, trace_n,
+                                                 pairs);
+            });
+        });
     }
-    e = hipGetLastError();
+    const hipError_t e = hipGetLastError();
     if (ev1) (void)hipEventRecord(ev1, stream);
-    scratch.give(mem, stream);
     return e;
 }
 
@@ -912,59 +880,27 @@ hipError_t launch_search_worklist(scratch_cache &scratch, const shard_view *d_sh
                                   hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const void *d_pre) {
     if (nshards == 0 || m == 0) return hipSuccess;
     if (k > 32u || tn == 0 || tn >= k) return hipErrorInvalidValue;
-    static const int wgs_per_cu = [] {
-        const char *e = getenv("RSBWT_WAVE_WGS_PER_CU");
-        const int v = e ? atoi(e) : 0;
-        return v > 0 ? v : RSB_MIN_WGS_PER_CU;
-    }();
     const size_t implicit = m * 3u * (size_t)(k - tn), mv = m * (3u * (size_t)k + 1u);
-    size_t g = ((implicit + wl_cap) * nshards + 64u * WG_WAVES - 1) / (64u * WG_WAVES);
-    // RSBWT_SEARCH_SPARE_WGS = n: n workgroups fewer than the chip holds.  A search launch is persistent (its workgroups
-    // stay until the batch is done) and fills every CU's registers (4 waves x 128 VGPRs per SIMD) and LDS: a kernel
-    // that should run BESIDE it -- RCCL's, gathering the previous batch at N > 1 -- finds room only on CUs a workgroup
-    // short.  bench.py sets it for its N > 1 ranks (32: a workgroup slot on 32 CUs for the collective's channels).
-    static const size_t spare_wgs = [] {
-        const char *e = getenv("RSBWT_SEARCH_SPARE_WGS");
-        const long v = e ? atol(e) : 0;
-        return (size_t)(v > 0 ? v : 0);
-    }();
-    const size_t cap_all = (size_t)num_cus * (size_t)wgs_per_cu;
-    const size_t cap = cap_all > 2 * spare_wgs ? cap_all - spare_wgs : cap_all;
-    if (g > cap) g = cap;
-    scratch_cache::lease mem;
-    hipError_t e = scratch.take(nshards * POOL_STRIDE * sizeof(unsigned long long), stream, &mem);
-    if (e != hipSuccess) return e;
-    unsigned long long *ctr = (unsigned long long *)mem.p;
-    e = hipMemsetAsync(ctr, 0, nshards * POOL_STRIDE * sizeof(unsigned long long), stream);
-    if (e != hipSuccess) {
-        scratch.give(mem, stream);
-        return e;
-    }
+    const size_t g = plan_grid((implicit + wl_cap) * nshards, 64u * WG_WAVES, search_cap(num_cus, wave_wgs_per_cu()));
+    pool_lease mem(scratch, stream, 0, 1, nshards);
+    if (mem.error() != hipSuccess) return mem.error();
     if (ev0) (void)hipEventRecord(ev0, stream);
     // (the table entries of the implicit items read ahead for all shards: inside this launch's event pair, so that the
     // time the library reports for the worklist search includes it)
     if (d_pre) {
-        e = launch_wl_table_entries(d_shards, nshards, d_packed, m, k, tn, const_cast<void *>(d_pre), stream);
-        if (e != hipSuccess) {
-            scratch.give(mem, stream);
-            return e;
-        }
+        const hipError_t e = launch_wl_table_entries(d_shards, nshards, d_packed, m, k, tn, const_cast<void *>(d_pre), stream);
+        if (e != hipSuccess) return e;
     }
-    uint32_t qchunk = 1024;
-    while (qchunk > 64u && (size_t)qchunk * g * WG_WAVES * 4u > implicit * nshards) qchunk >>= 1;
-    if (d_work)
-        hipLaunchKernelGGL((search_solo_kernel<true, false, false, false, true>), dim3((unsigned)g), dim3(64 * WG_WAVES), 0, stream, d_shards,
-                           nshards, (const uint64_t *)d_packed, (const ulonglong2 *)d_worklists, (const uint8_t *)d_valid, ctr, mv, k, 1u,
-                           (uint64_t *)d_sparse, (uint64_t *)d_hit_bits, d_work, (ulonglong2 *)const_cast<void *>(d_pre), tn, qchunk, 2u,
+    // (the draw is sized by the implicit items: how many records were appended only the device knows)
+    const uint32_t qchunk = plan_draw(1024, 64, g * WG_WAVES, 4, implicit * nshards);
+    with_flag(d_work != nullptr, [&](auto cw) {
+        hipLaunchKernelGGL((search_solo_kernel<FLAG(cw), false, false, false, true>), dim3((unsigned)g), dim3(64 * WG_WAVES), 0, stream, d_shards,
+                           nshards, (const uint64_t *)d_packed, (const ulonglong2 *)d_worklists, (const uint8_t *)d_valid, mem.pool(0, nshards), mv,
+                           k, 1u, (uint64_t *)d_sparse, (uint64_t *)d_hit_bits, d_work, (ulonglong2 *)const_cast<void *>(d_pre), tn, qchunk, 2u,
                            (const unsigned long long *)d_counts, wl_cap, implicit);
-    else
-        hipLaunchKernelGGL((search_solo_kernel<false, false, false, false, true>), dim3((unsigned)g), dim3(64 * WG_WAVES), 0, stream, d_shards,
-                           nshards, (const uint64_t *)d_packed, (const ulonglong2 *)d_worklists, (const uint8_t *)d_valid, ctr, mv, k, 1u,
-                           (uint64_t *)d_sparse, (uint64_t *)d_hit_bits, d_work, (ulonglong2 *)const_cast<void *>(d_pre), tn, qchunk, 2u,
-                           (const unsigned long long *)d_counts, wl_cap, implicit);
-    e = hipGetLastError();
+    });
+    const hipError_t e = hipGetLastError();
     if (ev1) (void)hipEventRecord(ev1, stream);
-    scratch.give(mem, stream);
     return e;
 }
 
@@ -976,51 +912,23 @@ hipError_t launch_search_walk(scratch_cache &scratch, const shard_view *d_shards
                               hipEvent_t ev0, hipEvent_t ev1) {
     if (nshards == 0 || m == 0) return hipSuccess;
     if (k > 32u || tn == 0 || tn >= k) return hipErrorInvalidValue;
-    static const int wgs_per_cu = [] {
-        const char *e = getenv("RSBWT_WALK1MM_WGS_PER_CU");
-        const int v = e ? atoi(e) : 0;
-        return v > 0 && v <= RSB_WALK1MM_WGS_PER_CU ? v : RSB_WALK1MM_WGS_PER_CU;
-    }();
-    size_t g = (m * nshards + 64u * WG_WAVES - 1) / (64u * WG_WAVES);
-    // RSBWT_SEARCH_SPARE_WGS = n: n workgroups fewer than the chip holds.  A search launch is persistent (its workgroups
-    // stay until the batch is done) and fills every CU's registers (4 waves x 128 VGPRs per SIMD) and LDS: a kernel
-    // that should run BESIDE it -- RCCL's, gathering the previous batch at N > 1 -- finds room only on CUs a workgroup
-    // short.  bench.py sets it for its N > 1 ranks (32: a workgroup slot on 32 CUs for the collective's channels).
-    static const size_t spare_wgs = [] {
-        const char *e = getenv("RSBWT_SEARCH_SPARE_WGS");
-        const long v = e ? atol(e) : 0;
-        return (size_t)(v > 0 ? v : 0);
-    }();
-    const size_t cap_all = (size_t)num_cus * (size_t)wgs_per_cu;
-    const size_t cap = cap_all > 2 * spare_wgs ? cap_all - spare_wgs : cap_all;
-    if (g > cap) g = cap;
-    scratch_cache::lease mem;
-    hipError_t e = scratch.take(nshards * POOL_STRIDE * sizeof(unsigned long long), stream, &mem);
-    if (e != hipSuccess) return e;
-    unsigned long long *ctr = (unsigned long long *)mem.p;
-    e = hipMemsetAsync(ctr, 0, nshards * POOL_STRIDE * sizeof(unsigned long long), stream);
-    if (e != hipSuccess) {
-        scratch.give(mem, stream);
-        return e;
-    }
+    static const size_t wgs_per_cu = (size_t)knob_int("RSBWT_WALK1MM_WGS_PER_CU", 1, RSB_WALK1MM_WGS_PER_CU, RSB_WALK1MM_WGS_PER_CU);
+    const size_t g = plan_grid(m * nshards, 64u * WG_WAVES, search_cap(num_cus, wgs_per_cu));
+    pool_lease mem(scratch, stream, 0, 1, nshards);
+    if (mem.error() != hipSuccess) return mem.error();
     if (ev0) (void)hipEventRecord(ev0, stream);
-    uint32_t qchunk = 1024;
-    while (qchunk > 64u && (size_t)qchunk * g * WG_WAVES * 4u > m * nshards) qchunk >>= 1;
-    if (d_work)
-        hipLaunchKernelGGL((search_solo_kernel<true, false, false, true, false, true>), dim3((unsigned)g), dim3(64 * WG_WAVES), 0, stream,
-                           d_shards, nshards, (const uint64_t *)d_packed, (const ulonglong2 *)d_worklists, (const uint8_t *)d_valid, ctr, m, k, 1u,
-                           (uint64_t *)d_sparse, (uint64_t *)d_hit_bits, d_work, (ulonglong2 *)nullptr, tn, qchunk, 2u,
-                           (const unsigned long long *)d_counts, wl_cap, (size_t)0);
-    else
-        hipLaunchKernelGGL((search_solo_kernel<false, false, false, true, false, true>), dim3((unsigned)g), dim3(64 * WG_WAVES), 0, stream,
-                           d_shards, nshards, (const uint64_t *)d_packed, (const ulonglong2 *)d_worklists, (const uint8_t *)d_valid, ctr, m, k, 1u,
-                           (uint64_t *)d_sparse, (uint64_t *)d_hit_bits, d_work, (ulonglong2 *)nullptr, tn, qchunk, 2u,
-                           (const unsigned long long *)d_counts, wl_cap, (size_t)0);
-    e = hipGetLastError();
+    const uint32_t qchunk = plan_draw(1024, 64, g * WG_WAVES, 4, m * nshards);
+    with_flag(d_work != nullptr, [&](auto cw) {
+        hipLaunchKernelGGL((search_solo_kernel<FLAG(cw), false, false, true, false, true>), dim3((unsigned)g), dim3(64 * WG_WAVES), 0, stream,
+                           d_shards, nshards, (const uint64_t *)d_packed, (const ulonglong2 *)d_worklists, (const uint8_t *)d_valid,
+                           mem.pool(0, nshards), m, k, 1u, (uint64_t *)d_sparse, (uint64_t *)d_hit_bits, d_work, (ulonglong2 *)nullptr, tn, qchunk,
+                           2u, (const unsigned long long *)d_counts, wl_cap, (size_t)0);
+    });
+    const hipError_t e = hipGetLastError();
     if (ev1) (void)hipEventRecord(ev1, stream);
-    scratch.give(mem, stream);
     return e;
 }
+#undef FLAG
 
 // Entries per k-mer of a traced search = the positions left of the k-mer table's reach (0: the
 // 1-mismatch search has nothing to share: no table, or k within it)

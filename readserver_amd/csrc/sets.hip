@@ -802,11 +802,7 @@ int rsbwt_set_count_dev(rsbwt_set_t *s, const void *d_packed, const void *d_vali
 // (8 resident 20 GB shards, per batch: 4e4 31-mers 5.7 -> 4.3 ms, 1e5 9.4 -> 7.8, 4e5 30.7 -> 27.9:
 // profiles/r03_set_side_by_side.json).
 static size_t side_by_side_below() {
-    static const size_t v = [] {
-        const char *e = getenv("RSBWT_SET_1MM_SIDE_LOG2");  // A/B knob (tools/README.md)
-        const int b = e ? atoi(e) : 0;
-        return (size_t)1 << (b >= 10 && b <= 40 ? b : 26);
-    }();
+    static const size_t v = (size_t)1 << knob_int("RSBWT_SET_1MM_SIDE_LOG2", 10, 40, 26);  // A/B knob (tools/README.md)
     return v;
 }
 #define SIDE_BY_SIDE_BELOW side_by_side_below()
@@ -823,10 +819,7 @@ static size_t side_by_side_below() {
 // per 4e5 31-mers x 8 shards, 1.74 -> 1.69 at 4e4; round 4 measured the same idea 2 % SLOWER -- the search kernel it
 // relieved was then bound by instruction issue, not by requests).  RSBWT_SET_1MM_TABLE_PREPASS=0: A/B knob (tools/README.md)
 static bool table_prepass() {
-    static const bool on = [] {
-        const char *e = getenv("RSBWT_SET_1MM_TABLE_PREPASS");
-        return e ? atoi(e) != 0 : RSB_1MM_TABLE_PREPASS_DEFAULT;
-    }();
+    static const bool on = knob_int("RSBWT_SET_1MM_TABLE_PREPASS", INT_MIN, INT_MAX, RSB_1MM_TABLE_PREPASS_DEFAULT) != 0;
     return on;
 }
 struct fused_1mm_layout {
@@ -839,7 +832,7 @@ struct fused_1mm_layout {
     size_t pre;  // the table-part variants' entries read ahead for all shards (RSBWT_SET_1MM_TABLE_PREPASS): u64 [S][m * 3 (k - tn)], or 0
 };
 static bool fused_1mm_applies(const rsbwt_set_t *s, size_t m, uint32_t k, fused_1mm_layout *L, bool dense = false) {
-    static const bool off = getenv("RSBWT_SET_1MM_UNFUSED") != nullptr;  // A/B knob (tools/README.md)
+    static const bool off = knob_set("RSBWT_SET_1MM_UNFUSED");  // A/B knob (tools/README.md)
     const size_t S = s->shards.size(), mv = m * (3 * (size_t)k + 1);
     if (off || S < 2 || S > 1024 || s->groups.size() != 1 || mv >= SIDE_BY_SIDE_BELOW || k > 32767u) return false;  // (S: a grid row per shard)
     const uint32_t tn = trace_entries(s->shards[0]->view, k);
@@ -850,8 +843,8 @@ static bool fused_1mm_applies(const rsbwt_set_t *s, size_t m, uint32_t k, fused_
     L->sparse = al(S * mv * 16);
     L->bits = al(S * hit_map_words(mv) * 8);
     L->blocks = al(S * compact_hits_block_words(mv) * 8);
-    static const bool no_worklist = getenv("RSBWT_SET_1MM_NO_WORKLIST") != nullptr;  // A/B knob (tools/README.md): round 3's launches
-    static const bool no_walk = getenv("RSBWT_SET_1MM_NO_WALK") != nullptr;          // A/B knob: the traced launch + the branch kernel
+    static const bool no_worklist = knob_set("RSBWT_SET_1MM_NO_WORKLIST");  // A/B knob (tools/README.md): round 3's launches
+    static const bool no_walk = knob_set("RSBWT_SET_1MM_NO_WALK");          // A/B knob: the traced launch + the branch kernel
     L->worklist = !no_worklist && tn > 0 && tn < k && k <= 32u && m * (size_t)tn < 0xFFFFFFFFull;
     // the trace ([S][m][tn] intervals) and the k-mers' own intervals are what the TRACED launch leaves: the default
     // worklist path walks the k-mers instead (search_solo.h, WALK) and touches neither (0.87 GB of scratch at 4e5
@@ -1081,7 +1074,7 @@ static int rsbwt_set_extract_body(rsbwt_set_t *s, const uint32_t *shard_of, cons
     const size_t S = s->shards.size();
     for (size_t i = 0; i < n; ++i)
         if (shard_of[i] >= S) return fail(RSBWT_EINVAL, "row %zu names shard %u of %zu", i, shard_of[i], S);
-    static const bool turns_only = getenv("RSBWT_SET_EXTRACT_TURNS") != nullptr;  // A/B knob (tools/README.md): a launch sequence per shard
+    static const bool turns_only = knob_set("RSBWT_SET_EXTRACT_TURNS");  // A/B knob (tools/README.md): a launch sequence per shard
     return for_each_group(s, [&](size_t gi) -> int {
         dev_group *g = s->groups[gi];
         const group_share sh = share_of_group(s, g, shard_of, rows, n);
@@ -1376,8 +1369,8 @@ int query_capped_body(rsbwt_set_t *s, const char *text, const uint64_t *off, siz
     for (rsbwt_t *h : s->shards)
         if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
     const size_t S = s->shards.size();
-    static const bool turns_only = getenv("RSBWT_SET_EXTRACT_TURNS") != nullptr;        // A/B knobs (tools/README.md)
-    static const bool host_rows = getenv("RSBWT_SET_QUERY_HOST_ROWS") != nullptr;
+    static const bool turns_only = knob_set("RSBWT_SET_EXTRACT_TURNS");        // A/B knobs (tools/README.md)
+    static const bool host_rows = knob_set("RSBWT_SET_QUERY_HOST_ROWS");
     if (s->groups.size() == 1 && S <= 1024 && !turns_only && !host_rows) {
         const int rc = query_capped_device(s, text, off, Q, max_rows, first, read_shard, reads, read_stride, read_len, cap_reads, nreads, matches);
         if (rc != CAPPED_TAKE_HOST) return rc;
@@ -1972,7 +1965,7 @@ size_t rsbwt_set_hits_1mm_scratch_bytes(const rsbwt_set_t *s, size_t m, uint32_t
 // 1: rsbwt_set_hits_1mm_dev of m k-mers runs as the fused launches (for a caller that prices them: bench.py)
 int rsbwt_set_hits_1mm_is_fused(const rsbwt_set_t *s, size_t m, uint32_t k) {
     fused_1mm_layout L;
-    static const bool turns_only = getenv("RSBWT_SET_1MM_TURNS") != nullptr;
+    static const bool turns_only = knob_set("RSBWT_SET_1MM_TURNS");
     return s && m && k && !turns_only && fused_1mm_applies(s, m, k, &L) ? 1 : 0;
 }
 
@@ -1991,7 +1984,7 @@ static int set_hits_1mm_fused(rsbwt_set_t *s, dev_group *g, const fused_1mm_layo
         // (d_pre: the table entries of the variants inside the tables' reach, read ahead for all shards by the worklist
         // launch's first kernel: mm1_worklist.hip, wl_table_entries_kernel)
         uint8_t *d_wl = d_blocks + L.blocks, *d_counts = d_wl + L.wl, *d_pre = L.pre ? d_counts + L.counts : nullptr;
-        static const bool no_walk = getenv("RSBWT_SET_1MM_NO_WALK") != nullptr;  // A/B knob (tools/README.md): the traced launch + the branch kernel
+        static const bool no_walk = knob_set("RSBWT_SET_1MM_NO_WALK");  // A/B knob (tools/README.md): the traced launch + the branch kernel
         if (!no_walk) {
             // ONE walk of the k-mers: their own searches, and at every position left of the tables' reach the step of the
             // three substitutions off the same fetch -- the survivors appended to the worklists (search_solo.h, WALK)
@@ -2030,7 +2023,7 @@ int rsbwt_set_hits_1mm_dev(rsbwt_set_t *s, const void *d_packed, const void *d_v
     }
     if (!d_packed || !d_valid || !d_scratch) return fail(RSBWT_EINVAL, "null argument");
     if (k == 0) return fail(RSBWT_EINVAL, "k must be at least 1");
-    static const bool turns_only = getenv("RSBWT_SET_1MM_TURNS") != nullptr;  // A/B knob (tools/README.md)
+    static const bool turns_only = knob_set("RSBWT_SET_1MM_TURNS");  // A/B knob (tools/README.md)
     const bool side = !turns_only && S > 1 && m * (3 * (size_t)k + 1) < SIDE_BY_SIDE_BELOW;
     const size_t one = hits_1mm_scratch_one(s, m, k);
     uint8_t *d_var = (uint8_t *)d_scratch, *d_slots = d_var + ((variants_bytes(m, k) + 255) & ~(size_t)255);
@@ -2085,7 +2078,7 @@ int rsbwt_set_extract_dev(rsbwt_set_t *s, const void *d_rows, size_t n, void *d_
     if (!d_rows || !d_out || !d_len || !d_prefix_len) return fail(RSBWT_EINVAL, "null argument");
     if (stride == 0) return fail(RSBWT_EINVAL, "stride must be positive");
     const size_t S = s->shards.size();
-    static const bool turns_only = getenv("RSBWT_SET_EXTRACT_TURNS") != nullptr;  // A/B knob (tools/README.md): a launch sequence per shard
+    static const bool turns_only = knob_set("RSBWT_SET_EXTRACT_TURNS");  // A/B knob (tools/README.md): a launch sequence per shard
     if (turns_only || n > (1ull << 31)) {
         for (size_t i = 0; i < S; ++i) {
             rc = rsbwt_extract_dev(s->shards[i], (const uint8_t *)d_rows + i * n * 8, n, (uint8_t *)d_out + i * n * (size_t)stride,

@@ -584,6 +584,52 @@ int rsbwt_set_gt_reads(rsbwt_set_t *s, const char *text, const uint64_t *off, si
 int rsbwt_set_gt_count(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, int32_t k, int32_t skip,
                        uint64_t M, uint64_t *counts);
 void rsbwt_set_gt_last_work(uint64_t *work6);
+/* Matching statistics: for every END position of a batch of queries and every shard, the longest string ending there
+ * that the shard still supports, and its interval -- "how much of this sequence do the reads support, and where does the
+ * support break".  Queries arrive as in the _var calls: text, off[Q + 1], N = off[Q] - off[0] positions; position t in
+ * [0, N) belongs to query q with off[q] <= off[0] + t < off[q+1], and its end is e = off[0] + t - off[q] + 1.  W_p(x) is
+ * the number of rows of findInterval(x) in shard p by this header's rule for an interval (lower <= upper && upper <
+ * bwlen ? upper - lower + 1 : 0), and 0 for a string that holds a symbol outside ACGT.  m = max(min_rows, 1); cap =
+ * max_len, 0 = no cap.
+ *   len[p*N + t]            the largest l in [0, min(e, cap)] such that x = the l symbols ending at position t is all
+ *                           ACGT and W_p(x) >= m
+ *   lower / upper[p*N + t]  findInterval(x) in shard p; (1, 0) where l = 0
+ *   SMEM                    position t is a super-maximal exact match of its shard iff len > 0 and either the query ends
+ *                           at t or len[t+1] <= len[t].  The starts t - len[t] never decrease along a query, so a match
+ *                           lies inside another exactly when the next position's match has the same start; a match that
+ *                           stops at cap counts as maximal under the cap.
+ * W cannot grow when a string grows to the left: Occ(c, upper) - Occ(c, lower - 1) <= upper - lower + 1 for any run
+ * stream, a valid BWT or not.  So the largest l is where the first LF step fails; the search never looks past it, and
+ * the definition holds on synthetic run streams too.  The search starts from the shard's k-mer table where the match is
+ * at least that deep and from initInterval elsewhere: same answers with any table or none.
+ *   rsbwt_set_match_lengths      len u32[S][N]; lower / upper u64[S][N] may be NULL, both or neither
+ *   rsbwt_match_lengths          one handle = a set of one
+ *   rsbwt_set_match_lengths_dev  a set on ONE device; d_text, d_off (u64[Q + 1], d_off[0] = 0, d_off[Q] = N) and the
+ *                                outputs in HBM: d_len u32[S][N], d_pairs {lower, upper}[S][N] (16 bytes each; may be
+ *                                NULL); enqueues on `stream`, synchronises nothing
+ *   rsbwt_set_smems              the SMEMs of query q in shard p are out[first[q*S+p] .. first[q*S+p+1]) (first has Q*S + 1
+ *                                entries), ascending end: the match is text[off[q]+start .. off[q]+end).  cap = 0 sizes
+ *                                the buffer (RSBWT_ERANGE, *nsmems set).  Only the SMEMs' records leave the device.
+ * Q = 0 or N = 0 succeeds and touches no output array (rsbwt_set_smems sets *nsmems = 0 and zeroes first[]).  A query longer
+ * than 2^31 - 1 symbols is RSBWT_EINVAL, 2^31 positions or more in one call RSBWT_ERANGE.  No call needs RSBWT_OPEN_READS
+ * or a k-mer table; they build nothing and write nothing a search reads, and are re-entrant like the other set calls.
+ * rsbwt_set_match_last_work: the calling thread's last host-buffer call: {items = positions x shards, LF steps, lane-passes
+ * that fetched a line, starts from a k-mer table entry, restarts from initInterval after a table entry was refused,
+ * SMEMs}. */
+typedef struct rsbwt_smem {
+    uint64_t query;
+    uint32_t shard, start, end, reserved; /* the match is query[start:end) */
+    uint64_t lower, upper;                /* its interval in that shard */
+} rsbwt_smem;
+int rsbwt_set_match_lengths(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t max_len, uint64_t min_rows,
+                            uint32_t *len, uint64_t *lower, uint64_t *upper);
+int rsbwt_set_match_lengths_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, size_t N, uint32_t max_len,
+                                uint64_t min_rows, void *d_len, void *d_pairs, void *stream);
+int rsbwt_set_smems(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t max_len, uint64_t min_rows,
+                    uint64_t *first, rsbwt_smem *out, size_t cap, size_t *nsmems);
+int rsbwt_match_lengths(rsbwt_t *h, const char *text, const uint64_t *off, size_t Q, uint32_t max_len, uint64_t min_rows,
+                        uint32_t *len, uint64_t *lower, uint64_t *upper);
+void rsbwt_set_match_last_work(uint64_t *work6);
 /* Device-resident forms, for a set on ONE device (one process per GPU: bench.py --mode 1mm|extract).
  * d_hits [num_shards][cap_per_shard] x 32-byte records (rsbwt_hits_1mm_dev's), d_totals u64[num_shards];
  * d_rows [num_shards][n] (row numbers are per shard), d_out [num_shards][n][stride], d_len / d_prefix_len [num_shards][n]. */

@@ -186,6 +186,19 @@ class GpuBWT:
         check(lib().rsbwt_locate(self.handle, _ptr(r), r.size, max_steps, _ptr(rr), _ptr(od), _ptr(of)))
         return rr, od, of
 
+    def match_lengths(self, queries, max_len=0, min_rows=1, intervals=False):
+        """Matching statistics of this shard (rsbwt_match_lengths): len, a uint32 array over the positions of the queries
+        laid back to back -- the longest string ending at each position that occurs in at least max(min_rows, 1) rows, at
+        most max_len symbols long (0 = no cap); intervals=True: (len, lower, upper) with findInterval of that string,
+        (1, 0) where len is 0.  ShardSet.match_last_work() tells the work."""
+        text, off = ShardSet._var_text(queries)
+        N = int(off[-1])
+        ln = np.zeros(N, np.uint32)
+        lo, up = (np.zeros(N, np.uint64), np.zeros(N, np.uint64)) if intervals else (None, None)
+        check(lib().rsbwt_match_lengths(self.handle, _ptr(text), _ptr(off), len(queries), max_len, min_rows, _ptr(ln),
+                                        _ptr(lo) if intervals else None, _ptr(up) if intervals else None))
+        return (ln, lo, up) if intervals else ln
+
     @property
     def exactmatch_by_search(self):
         """True: query_exactmatch on this shard answers by backward search from the terminator rows
@@ -242,6 +255,8 @@ def find_intervals_1mm(pBWT, kmers):
 
 HIT_1MM = np.dtype([("lower", "<u8"), ("upper", "<u8"), ("query", "<u4"), ("pos", "<i2"), ("base", "S1"),
                     ("reserved", "u1")])  # = rsbwt_hit_1mm
+SMEM = np.dtype([("query", "<u8"), ("shard", "<u4"), ("start", "<u4"), ("end", "<u4"), ("reserved", "<u4"), ("lower", "<u8"),
+                 ("upper", "<u8")])  # = rsbwt_smem
 GT_LEG = np.dtype([("query", "<u8"), ("tile", "<u4"), ("leg", "<u4"), ("shard", "<u4"), ("a", "<u4"), ("b", "<u4"), ("reserved", "<u4"),
                    ("lower", "<u8"), ("upper", "<u8")])  # = rsbwt_gt_leg
 
@@ -602,6 +617,47 @@ class ShardSet:
         w = np.zeros(6, np.uint64)
         lib().rsbwt_set_gt_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
         return dict(zip(("legs", "no_answer", "narrow_steps", "candidates", "kept", "extracted"), (int(x) for x in w)))
+
+    # -- matching statistics (csrc/match_stats.hip): rsbwt_set_match_lengths / rsbwt_set_smems
+    def match_lengths(self, queries, max_len=0, min_rows=1, intervals=False):
+        """len of shape (shards, N), N the positions of the queries laid back to back: per shard the longest string ending
+        at each position that occurs in at least max(min_rows, 1) rows, at most max_len symbols long (0 = no cap);
+        intervals=True: (len, lower, upper) with findInterval of that string, (1, 0) where len is 0
+        (rsbwt_set_match_lengths)"""
+        text, off = self._var_text(queries)
+        S, N = len(self.shards), int(off[-1])
+        ln = np.zeros((S, N), np.uint32)
+        lo, up = (np.zeros((S, N), np.uint64), np.zeros((S, N), np.uint64)) if intervals else (None, None)
+        check(lib().rsbwt_set_match_lengths(self._s, _ptr(text), _ptr(off), len(queries), max_len, min_rows, _ptr(ln),
+                                            _ptr(lo) if intervals else None, _ptr(up) if intervals else None))
+        return (ln, lo, up) if intervals else ln
+
+    def smems(self, queries, max_len=0, min_rows=1, raw=False):
+        """[query][shard] -> the super-maximal exact matches as (start, end, lower, upper), ascending end: query[start:end)
+        is a longest match that no neighbouring position's match contains, [lower, upper] its interval in that shard;
+        raw=True: (SMEM array ordered by (query, shard, end), first) as rsbwt_set_smems writes them"""
+        text, off = self._var_text(queries)
+        Q, S = len(queries), len(self.shards)
+        first = np.zeros(Q * S + 1, np.uint64)
+        n = C.c_size_t()
+        rc = lib().rsbwt_set_smems(self._s, _ptr(text), _ptr(off), Q, max_len, min_rows, _ptr(first), None, 0, C.byref(n))
+        if rc not in (0, -7):
+            check(rc)
+        total = n.value
+        out = np.zeros(max(total, 1), SMEM)
+        if total:
+            check(lib().rsbwt_set_smems(self._s, _ptr(text), _ptr(off), Q, max_len, min_rows, _ptr(first), _ptr(out), total, C.byref(n)))
+        if raw:
+            return out[:total], first
+        return [[[(int(r["start"]), int(r["end"]), int(r["lower"]), int(r["upper"]))
+                  for r in out[int(first[q * S + p]):int(first[q * S + p + 1])]] for p in range(S)] for q in range(Q)]
+
+    @staticmethod
+    def match_last_work():
+        """{items, lf_steps, passes, table_starts, restarts, smems} of this thread's last matching-statistics call"""
+        w = np.zeros(6, np.uint64)
+        lib().rsbwt_set_match_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return dict(zip(("items", "lf_steps", "passes", "table_starts", "restarts", "smems"), (int(x) for x in w)))
 
     # -- BASELINE configs[3] / configs[4] over the set: per-shard results side by side, the way the front-end
     # concatenates its partitions' replies (src/service/server.cpp:199-261)

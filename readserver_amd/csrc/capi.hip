@@ -15,6 +15,7 @@
 #include "../../include/rsbwt.h"
 #include "bpi2.h"
 #include "bwt_file.h"
+#include "capi_guard.h"
 #include "capi_internal.h"
 #include "kernels.h"
 #include "line_format.h"
@@ -1916,6 +1917,44 @@ int rsbwt_last_search_ktab_lookups(rsbwt_t *h, uint64_t *lookups) {
     if ((rc = meter_work(*h, w, WORK_WORDS)) != RSBWT_OK) return rc;
     *lookups = w[3];
     return RSBWT_OK;
+}
+
+// ---- matching statistics (match_stats.hip): one handle = a set of one ------------------------
+
+int rsbwt_match_lengths(rsbwt_t *h, const char *text, const uint64_t *off, size_t Q, uint32_t max_len, uint64_t min_rows, uint32_t *len,
+                        uint64_t *lower, uint64_t *upper) {
+    return guarded("rsbwt_match_lengths", [&]() -> int {
+        match_set_last_work(nullptr);
+        if (!h && rsbwt_device_count() == 0) return fail(RSBWT_ENODEV, "no HIP device is visible: the popBWT engine has no CPU fallback");
+        if (!h) return fail(RSBWT_EINVAL, "null handle");
+        if ((lower == nullptr) != (upper == nullptr)) return fail(RSBWT_EINVAL, "lower and upper: both or neither");
+        std::vector<uint64_t> rel;
+        size_t N = 0;
+        int rc = match_check_batch(text, off, Q, &rel, &N);
+        if (rc) return rc;
+        if (N == 0) return RSBWT_OK;
+        if (!len) return fail(RSBWT_EINVAL, "null argument");
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index");
+        if ((rc = use_device(h->device)) != RSBWT_OK) return rc;
+        call_ctx *c = h->pool.acquire();
+        if (!c) return fail(RSBWT_EHIP, "cannot create a HIP stream");
+        struct release_t {
+            rsbwt_t *h;
+            call_ctx *c;
+            ~release_t() { h->pool.release(c); }
+        } release{h, c};
+        std::vector<uint64_t> pairs(lower ? 2 * N : 0);
+        uint64_t work6[6] = {N, 0, 0, 0, 0, 0};
+        rc = match_host_views(h->scratch, c->st[0], h->d_view, 1, text + off[0], rel.data(), Q, N, max_len, min_rows, len,
+                              lower ? pairs.data() : nullptr, nullptr, work6 + 1);
+        if (rc) return rc;
+        for (size_t t = 0; lower && t < N; ++t) {
+            lower[t] = pairs[2 * t];
+            upper[t] = pairs[2 * t + 1];
+        }
+        match_set_last_work(work6);
+        return RSBWT_OK;
+    });
 }
 
 // ---- synthetic data ---------------------------------------------------------------------------

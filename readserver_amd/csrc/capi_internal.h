@@ -118,6 +118,16 @@ int locate_host_views(scratch_cache &scratch, call_ctx &c, const shard_view *d_v
                       const uint64_t *rows, size_t n, uint32_t max_steps, uint64_t *read_row, uint64_t *ordinal, uint32_t *offset,
                       uint64_t *work2);
 void locate_set_last_work(uint64_t walked, uint64_t steps);
+// match_stats.hip: what the host-buffer matching-statistics calls share (capi.hip: one handle; sets.hip: a set).
+//   match_check_batch  off[] ascending, no query over 2^31 - 1 symbols, under 2^31 positions: rel = offsets from off[0], *N
+//   match_host_views   one device's share on `st` (synchronised before it returns): len u32[S][N], pairs {lower, upper}[S][N],
+//                      smems (shard = d_views' number, unordered), each optional; work4 += the launch's counters
+//   match_set / get_last_work: what rsbwt_set_match_last_work reports for the calling thread
+int match_check_batch(const char *text, const uint64_t *off, size_t Q, std::vector<uint64_t> *rel, size_t *N);
+int match_host_views(scratch_cache &scratch, hipStream_t st, const shard_view *d_views, uint32_t S, const char *t0, const uint64_t *rel, size_t Q,
+                     size_t N, uint32_t cap, uint64_t m, uint32_t *len, uint64_t *pairs, std::vector<rsbwt_smem> *smems, uint64_t *work4);
+void match_set_last_work(const uint64_t work6[6]);
+void match_get_last_work(uint64_t work6[6]);
 // 1-mismatch hit list of one shard from variants expanded once for the whole batch (sets.hip: every shard of a set
 // searches the same variants)
 size_t variants_bytes(size_t m, uint32_t k);

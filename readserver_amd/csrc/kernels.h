@@ -284,6 +284,24 @@ hipError_t launch_gt_narrow(const shard_view *d_shards, uint32_t nshards, const 
                             unsigned long long *d_work, hipStream_t stream);
 hipError_t launch_gt_filter(const gt_batch &bt, const void *d_legs, const void *d_first, const void *d_shard_of, const void *d_offset,
                             const void *d_read_row, uint64_t total, void *d_kept_rows, unsigned long long *d_counters, hipStream_t stream);
+// match_stats.hip: matching statistics (include/rsbwt.h: the definition).  A batch is its queries' text back to back and
+// where each starts: position t < N = off[Q] belongs to the query with off[q] <= t < off[q + 1] (off[0] = 0), all in HBM.
+struct match_batch {
+    const char *text;
+    const uint64_t *off;  // [Q + 1]
+    size_t Q, N;
+    uint32_t cap;  // max_len; 0 = none
+    uint64_t m;    // rows a match must hold, >= 1
+};
+//   launch_match_stats: one lane per (position, shard): d_len u32[nshards][N], d_pairs {lower, upper}[nshards][N] (optional);
+//     d_work (optional, zeroed by the caller) [0..3] += LF steps, lane-passes that fetched a line, starts from the k-mer
+//     table, restarts from initInterval after a table entry was refused
+//   launch_match_smems: the SMEMs of those answers, compacted: d_smems rsbwt_smem[cap_records] (shard = the launch's
+//     number) receives one record per SMEM, *d_counter (zeroed by the caller) of them in all, in no particular order
+hipError_t launch_match_stats(const shard_view *d_shards, uint32_t nshards, const match_batch &bt, void *d_len, void *d_pairs,
+                              unsigned long long *d_work, hipStream_t stream);
+hipError_t launch_match_smems(uint32_t nshards, const match_batch &bt, const void *d_len, const void *d_pairs, void *d_smems, uint64_t cap_records,
+                              unsigned long long *d_counter, hipStream_t stream);
 // (SEL_SHIFT, sample_window, window_samples, window_psi_hint: line_format.h -- shared with the host-side layout test)
 // query / query_exactmatch (query.cpp:87-120) over extracted reads
 hipError_t launch_match_reads(const void *d_reads, const void *d_len, size_t n, uint32_t stride, const void *d_owner,

@@ -1944,6 +1944,143 @@ void rsbwt_set_gt_last_work(uint64_t *work6) {
     if (work6) memcpy(work6, gt_last_work, sizeof gt_last_work);
 }
 
+// ---- matching statistics (match_stats.hip): the longest supported match at every end position, in every shard ----
+namespace {
+// Each device group runs its shards' rows of the (position, shard) grid; answers are per (position, shard), so the host
+// only puts group gi's row j at row idx[j].  len / lower / upper [S][N] and smems (ordered by (query, shard, end)) are
+// each optional.
+int match_call(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t max_len, uint64_t min_rows, uint32_t *len, uint64_t *lower,
+               uint64_t *upper, std::vector<rsbwt_smem> *smems) {
+    match_set_last_work(nullptr);
+    // (no set can be had on a box without a GPU: the call says so instead of blaming the argument)
+    if (!s && rsbwt_device_count() == 0) return fail(RSBWT_ENODEV, "no HIP device is visible: the popBWT engine has no CPU fallback");
+    if (!s) return fail(RSBWT_EINVAL, "null set");
+    if ((lower == nullptr) != (upper == nullptr)) return fail(RSBWT_EINVAL, "lower and upper: both or neither");
+    std::vector<uint64_t> rel;
+    size_t N = 0;
+    int rc = match_check_batch(text, off, Q, &rel, &N);
+    if (rc) return rc;
+    if (N == 0) return RSBWT_OK;
+    if (!len && !smems) return fail(RSBWT_EINVAL, "null argument");
+    const size_t S = s->shards.size();
+    for (rsbwt_t *h : s->shards)
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
+    if (S > 65535) return fail(RSBWT_EINVAL, "%zu shards: at most 65535", S);
+    struct group_out {
+        std::vector<uint32_t> len;
+        std::vector<uint64_t> pairs;
+        std::vector<rsbwt_smem> smems;
+        uint64_t work[4] = {0, 0, 0, 0};
+    };
+    std::vector<group_out> outs(s->groups.size());
+    rc = for_each_group(s, [&](size_t gi) -> int {
+        dev_group *g = s->groups[gi];
+        group_call gc(g);
+        if (gc.rc) return gc.rc;
+        group_out &o = outs[gi];
+        const size_t Sg = g->idx.size();
+        // (a group whose shards sit next to each other in the set answers straight into the caller's rows)
+        const bool straight = g->idx.back() - g->idx.front() + 1 == Sg;
+        uint32_t *glen = nullptr;
+        if (len) {
+            if (straight) glen = len + g->idx.front() * N;
+            else {
+                o.len.resize(Sg * N);
+                glen = o.len.data();
+            }
+        }
+        if (lower) o.pairs.resize(2 * Sg * N);
+        return match_host_views(g->scratch, gc.st, g->d_views, (uint32_t)Sg, text + off[0], rel.data(), Q, N, max_len, min_rows, glen,
+                                lower ? o.pairs.data() : nullptr, smems ? &o.smems : nullptr, o.work);
+    });
+    if (rc) return rc;
+    uint64_t work6[6] = {(uint64_t)S * N, 0, 0, 0, 0, 0};
+    for (size_t gi = 0; gi < outs.size(); ++gi) {
+        const dev_group *g = s->groups[gi];
+        const group_out &o = outs[gi];
+        for (size_t j = 0; j < g->idx.size(); ++j) {
+            const size_t p = g->idx[j];
+            if (len && !o.len.empty()) memcpy(len + p * N, o.len.data() + j * N, N * 4);
+            if (lower)
+                for (size_t t = 0; t < N; ++t) {
+                    lower[p * N + t] = o.pairs[2 * (j * N + t)];
+                    upper[p * N + t] = o.pairs[2 * (j * N + t) + 1];
+                }
+        }
+        for (int i = 0; i < 4; ++i) work6[1 + i] += o.work[i];
+        if (smems)
+            for (rsbwt_smem r : o.smems) {
+                r.shard = (uint32_t)g->idx[r.shard];
+                smems->push_back(r);
+            }
+    }
+    if (smems) {
+        std::sort(smems->begin(), smems->end(), [](const rsbwt_smem &x, const rsbwt_smem &y) {
+            return x.query != y.query ? x.query < y.query : x.shard != y.shard ? x.shard < y.shard : x.end < y.end;
+        });
+        work6[5] = smems->size();
+    }
+    match_set_last_work(work6);
+    return RSBWT_OK;
+}
+}  // namespace
+
+int rsbwt_set_match_lengths(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t max_len, uint64_t min_rows, uint32_t *len,
+                            uint64_t *lower, uint64_t *upper) {
+    return guarded("rsbwt_set_match_lengths", [&]() -> int {
+        return match_call(s, text, off, Q, max_len, min_rows, len, lower, upper, nullptr);
+    });
+}
+
+int rsbwt_set_smems(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t max_len, uint64_t min_rows, uint64_t *first,
+                    rsbwt_smem *out, size_t cap, size_t *nsmems) {
+    return guarded("rsbwt_set_smems", [&]() -> int {
+        if (!nsmems || (!first && Q)) return fail(RSBWT_EINVAL, "null argument");
+        *nsmems = 0;
+        std::vector<rsbwt_smem> recs;
+        const int rc = match_call(s, text, off, Q, max_len, min_rows, nullptr, nullptr, nullptr, &recs);
+        if (rc) return rc;
+        const size_t S = s->shards.size();
+        if (first) {
+            for (size_t c = 0; c <= Q * S; ++c) first[c] = 0;
+            for (const rsbwt_smem &r : recs) first[(size_t)r.query * S + r.shard + 1] += 1;
+            for (size_t c = 0; c < Q * S; ++c) first[c + 1] += first[c];
+        }
+        *nsmems = recs.size();
+        if (recs.size() > cap) return fail(RSBWT_ERANGE, "%zu SMEMs, room for %zu", recs.size(), cap);
+        if (recs.empty()) return RSBWT_OK;
+        if (!out) return fail(RSBWT_EINVAL, "null argument");
+        memcpy(out, recs.data(), recs.size() * sizeof(rsbwt_smem));
+        return RSBWT_OK;
+    });
+}
+
+int rsbwt_set_match_lengths_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, size_t N, uint32_t max_len, uint64_t min_rows,
+                                void *d_len, void *d_pairs, void *stream) {
+    dev_group *g = nullptr;
+    const int rc = one_device_group(s, &g);
+    if (rc) return rc;
+    if (Q == 0 || N == 0) return RSBWT_OK;
+    if (!d_text || !d_off || !d_len) return fail(RSBWT_EINVAL, "null argument");
+    if (N >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu positions in one call: at most 2^31 - 1", N);
+    for (rsbwt_t *h : s->shards)
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
+    if (s->shards.size() > 65535) return fail(RSBWT_EINVAL, "%zu shards: at most 65535", s->shards.size());
+    match_batch bt;
+    bt.text = (const char *)d_text;
+    bt.off = (const uint64_t *)d_off;
+    bt.Q = Q;
+    bt.N = N;
+    bt.cap = max_len;
+    bt.m = min_rows ? min_rows : 1;
+    const hipError_t e = launch_match_stats(g->d_views, (uint32_t)g->idx.size(), bt, d_len, d_pairs, nullptr, (hipStream_t)stream);
+    return e == hipSuccess ? RSBWT_OK : fail_hip(e, "matching-statistics kernel launch");
+}
+
+void rsbwt_set_match_last_work(uint64_t *work6) {
+    if (work6) match_get_last_work(work6);
+}
+
 static size_t hits_1mm_scratch_one(const rsbwt_set_t *s, size_t m, uint32_t k) {
     size_t need = 0;
     for (rsbwt_t *h : s->shards) need = std::max(need, rsbwt_hits_1mm_scratch_bytes(h, m, k));

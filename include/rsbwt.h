@@ -630,6 +630,66 @@ int rsbwt_set_smems(rsbwt_set_t *s, const char *text, const uint64_t *off, size_
 int rsbwt_match_lengths(rsbwt_t *h, const char *text, const uint64_t *off, size_t Q, uint32_t max_len, uint64_t min_rows,
                         uint32_t *len, uint64_t *lower, uint64_t *upper);
 void rsbwt_set_match_last_work(uint64_t *work6);
+/* Overlaps: the reads that BEGIN with a suffix of a query -- "which reads continue this sequence past its end", the
+ * suffix-prefix overlaps an assembler walks.  Queries arrive as in the _var calls: text, off[Q + 1], N = off[Q] - off[0]
+ * positions; position t in [0, N) belongs to query q as in rsbwt_set_match_lengths (off[q] <= off[0] + t < off[q+1]) and
+ * names the suffix of its query that starts there: x = text[off[0]+t .. off[q+1]), of length l = off[q+1] - off[0] - t.
+ * limit = max_overlap, 0 = no limit.  For shard p:
+ *   count[p*N + t]    Occ('$', upper) - Occ('$', lower - 1) over (lower, upper) = findInterval(x), Occ(., -1) = 0, when
+ *                     l >= max(min_overlap, 1), l <= limit (if one is set), x is all ACGT and the interval is proper by
+ *                     this header's rule (lower <= upper && upper < bwlen); 0 in every other case.  In a multi-string
+ *                     BWT a row of the interval holds '$' exactly when a read begins with x there, so this is the
+ *                     number of reads of the shard that begin with x.
+ *   ordinal[p*N + t]  Occ('$', lower - 1) where count > 0, else 0.  The reads are the ordinals [ordinal, ordinal + count),
+ *                     the dense numbers rsbwt_locate reports: for each such o the row getOccAt('$', o + 1) lies in the
+ *                     interval, has offset 0 and extracts as that read.
+ * A read equal to x counts (it begins with x).  A shard without '$' rows gives 0 everywhere.  The definition goes through
+ * Occ, so it holds on synthetic run streams too.  One backward search of a query from its right end passes through the
+ * interval of every suffix, and the '$' ranks are taken at the positions the next LF step ranks its own symbol at: the
+ * profile of a query costs one search.  The search ends at the first improper interval, at the limit or at a symbol
+ * outside ACGT; it starts from the shard's k-mer table of depth T only when T >= 2, min_overlap >= T and
+ * min(query length, limit) >= T, so no depth that could be reported is skipped: same answers with any table or none.
+ *   rsbwt_set_overlaps         count u64[S][N]; ordinal u64[S][N] may be NULL
+ *   rsbwt_overlaps             one handle = a set of one
+ *   rsbwt_set_overlaps_dev     a set on ONE device; d_text, d_off (u64[Q + 1], d_off[0] = 0, d_off[Q] = N) and the output
+ *                              in HBM: d_pairs {ordinal, count}[S][N] (16 bytes each, every entry written); enqueues on
+ *                              `stream`, synchronises nothing
+ *   rsbwt_set_overlap_records  the entries with count > 0 as records: those of query q in shard p are out[first[q*S+p] ..
+ *                              first[q*S+p+1]) (first has Q*S + 1 entries), ascending start -- the longest overlap first.
+ *                              cap = 0 sizes the buffer (RSBWT_ERANGE, *nrecords set).  Only the records leave the device.
+ *   rsbwt_set_overlap_reads    the reads themselves: those of (q, p) are entries first[q*S+p] .. first[q*S+p+1) of reads
+ *                              (read_stride bytes each), read_len, overlap (the length of the LONGEST suffix of the query
+ *                              the read begins with) and ordinal.  A read is reported once per (query, shard) -- a
+ *                              periodic query makes one read begin with several suffixes -- ordered by overlap descending,
+ *                              then ordinal ascending.  matches[q*S+p] (may be NULL) = the number of distinct reads; a
+ *                              (query, shard) with more than max_reads of them (0 = no limit) reports none and empties
+ *                              nobody else (rsbwt_set_query_var_capped's rule).  cap_reads = 0 sizes the buffers
+ *                              (RSBWT_ERANGE, *nreads set).  Every shard must be opened with RSBWT_OPEN_READS, else
+ *                              RSBWT_EINVAL; no other call here needs that.
+ * Q = 0 or N = 0 succeeds and touches no output array (the sizing calls set their count to 0 and zero first[]).  A query
+ * longer than 2^31 - 1 symbols is RSBWT_EINVAL, 2^31 positions or more in one call RSBWT_ERANGE, no device RSBWT_ENODEV.
+ * The calls build nothing and write nothing a search reads, and are re-entrant like the other set calls.
+ * rsbwt_set_overlap_last_work: the calling thread's last host-buffer call: {items = queries x shards, LF steps,
+ * lane-passes that fetched a line, starts from a k-mer table entry, lane-passes fetched for '$' alone, entries with
+ * count > 0}. */
+typedef struct rsbwt_overlap {
+    uint64_t query;
+    uint32_t shard, start, length, reserved; /* the suffix is query[start : start+length) */
+    uint64_t ordinal, count;                 /* reads [ordinal, ordinal + count) of that shard begin with it */
+    uint64_t lower, upper;                   /* its interval */
+} rsbwt_overlap;                             /* 56 bytes */
+int rsbwt_set_overlaps(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t min_overlap, uint32_t max_overlap,
+                       uint64_t *count, uint64_t *ordinal);
+int rsbwt_overlaps(rsbwt_t *h, const char *text, const uint64_t *off, size_t Q, uint32_t min_overlap, uint32_t max_overlap, uint64_t *count,
+                   uint64_t *ordinal);
+int rsbwt_set_overlaps_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, size_t N, uint32_t min_overlap,
+                           uint32_t max_overlap, void *d_pairs, void *stream);
+int rsbwt_set_overlap_records(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t min_overlap, uint32_t max_overlap,
+                              uint64_t *first, rsbwt_overlap *out, size_t cap, size_t *nrecords);
+int rsbwt_set_overlap_reads(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t min_overlap, uint32_t max_overlap,
+                            uint64_t max_reads, uint64_t *first, char *reads, uint32_t read_stride, uint32_t *read_len, uint32_t *overlap,
+                            uint64_t *ordinal, size_t cap_reads, size_t *nreads, uint64_t *matches);
+void rsbwt_set_overlap_last_work(uint64_t *work6);
 /* Device-resident forms, for a set on ONE device (one process per GPU: bench.py --mode 1mm|extract).
  * d_hits [num_shards][cap_per_shard] x 32-byte records (rsbwt_hits_1mm_dev's), d_totals u64[num_shards];
  * d_rows [num_shards][n] (row numbers are per shard), d_out [num_shards][n][stride], d_len / d_prefix_len [num_shards][n]. */

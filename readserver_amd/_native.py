@@ -201,6 +201,13 @@ SIGNATURES = {
     "rsbwt_set_smems": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, C.c_uint64, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rsbwt_match_lengths": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, C.c_uint64, _vp, _vp, _vp]),
     "rsbwt_set_match_last_work": (None, [_u64p]),
+    "rsbwt_set_overlaps": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "rsbwt_overlaps": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "rsbwt_set_overlaps_dev": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "rsbwt_set_overlap_records": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, C.c_uint32, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rsbwt_set_overlap_reads": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, _vp, _vp, _vp,
+                                          C.c_size_t, C.POINTER(C.c_size_t), _vp]),
+    "rsbwt_set_overlap_last_work": (None, [_u64p]),
     "rsbwt_service_kmer_requests": (C.c_uint64, [_vp]),
     "rsbwt_proto_encode_kmer_reply": (C.c_size_t, [_vp, C.c_size_t, C.c_int, C.c_char_p, C.c_size_t, C.c_int,
                                                    C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t]),

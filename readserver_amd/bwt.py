@@ -199,6 +199,20 @@ class GpuBWT:
                                         _ptr(lo) if intervals else None, _ptr(up) if intervals else None))
         return (ln, lo, up) if intervals else ln
 
+    def overlaps(self, queries, min_overlap, max_overlap=0, ordinals=False):
+        """The reads of this shard that begin with a suffix of a query (rsbwt_overlaps): count, a uint64 array over the
+        positions of the queries laid back to back -- position t names the suffix of its query that starts there, count[t]
+        the reads beginning with it when it has min_overlap symbols or more (and at most max_overlap, 0 = no limit), else
+        0; ordinals=True: (count, ordinal), the reads being the rsbwt_locate ordinals [ordinal, ordinal + count).
+        ShardSet.overlap_last_work() tells the work."""
+        text, off = ShardSet._var_text(queries)
+        N = int(off[-1])
+        cnt = np.zeros(N, np.uint64)
+        od = np.zeros(N, np.uint64) if ordinals else None
+        check(lib().rsbwt_overlaps(self.handle, _ptr(text), _ptr(off), len(queries), min_overlap, max_overlap, _ptr(cnt),
+                                   _ptr(od) if ordinals else None))
+        return (cnt, od) if ordinals else cnt
+
     @property
     def exactmatch_by_search(self):
         """True: query_exactmatch on this shard answers by backward search from the terminator rows
@@ -257,6 +271,8 @@ HIT_1MM = np.dtype([("lower", "<u8"), ("upper", "<u8"), ("query", "<u4"), ("pos"
                     ("reserved", "u1")])  # = rsbwt_hit_1mm
 SMEM = np.dtype([("query", "<u8"), ("shard", "<u4"), ("start", "<u4"), ("end", "<u4"), ("reserved", "<u4"), ("lower", "<u8"),
                  ("upper", "<u8")])  # = rsbwt_smem
+OVERLAP = np.dtype([("query", "<u8"), ("shard", "<u4"), ("start", "<u4"), ("length", "<u4"), ("reserved", "<u4"), ("ordinal", "<u8"),
+                    ("count", "<u8"), ("lower", "<u8"), ("upper", "<u8")])  # = rsbwt_overlap
 GT_LEG = np.dtype([("query", "<u8"), ("tile", "<u4"), ("leg", "<u4"), ("shard", "<u4"), ("a", "<u4"), ("b", "<u4"), ("reserved", "<u4"),
                    ("lower", "<u8"), ("upper", "<u8")])  # = rsbwt_gt_leg
 
@@ -658,6 +674,81 @@ class ShardSet:
         w = np.zeros(6, np.uint64)
         lib().rsbwt_set_match_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
         return dict(zip(("items", "lf_steps", "passes", "table_starts", "restarts", "smems"), (int(x) for x in w)))
+
+    # -- overlaps (csrc/overlaps.hip): rsbwt_set_overlaps / rsbwt_set_overlap_records / rsbwt_set_overlap_reads
+    def overlaps(self, queries, min_overlap, max_overlap=0, ordinals=False):
+        """count of shape (shards, N), N the positions of the queries laid back to back: position t names the suffix of its
+        query that starts there, count[p, t] the reads of shard p that begin with it when it has min_overlap symbols or
+        more (and at most max_overlap, 0 = no limit), else 0; ordinals=True: (count, ordinal), the reads being the
+        rsbwt_locate ordinals [ordinal, ordinal + count) of that shard (rsbwt_set_overlaps)"""
+        text, off = self._var_text(queries)
+        S, N = len(self.shards), int(off[-1])
+        cnt = np.zeros((S, N), np.uint64)
+        od = np.zeros((S, N), np.uint64) if ordinals else None
+        check(lib().rsbwt_set_overlaps(self._s, _ptr(text), _ptr(off), len(queries), min_overlap, max_overlap, _ptr(cnt),
+                                       _ptr(od) if ordinals else None))
+        return (cnt, od) if ordinals else cnt
+
+    def overlap_records(self, queries, min_overlap, max_overlap=0, raw=False):
+        """[query][shard] -> the suffixes some read begins with as (start, length, ordinal, count, lower, upper), ascending
+        start (the longest overlap first): query[start:start+length] opens the reads [ordinal, ordinal + count) of that
+        shard, [lower, upper] is its interval; raw=True: (OVERLAP array ordered by (query, shard, start), first) as
+        rsbwt_set_overlap_records writes them"""
+        text, off = self._var_text(queries)
+        Q, S = len(queries), len(self.shards)
+        first = np.zeros(Q * S + 1, np.uint64)
+        n = C.c_size_t()
+        rc = lib().rsbwt_set_overlap_records(self._s, _ptr(text), _ptr(off), Q, min_overlap, max_overlap, _ptr(first), None, 0, C.byref(n))
+        if rc not in (0, -7):
+            check(rc)
+        total = n.value
+        out = np.zeros(max(total, 1), OVERLAP)
+        if total:
+            check(lib().rsbwt_set_overlap_records(self._s, _ptr(text), _ptr(off), Q, min_overlap, max_overlap, _ptr(first), _ptr(out), total,
+                                                  C.byref(n)))
+        if raw:
+            return out[:total], first
+        return [[[tuple(int(r[f]) for f in ("start", "length", "ordinal", "count", "lower", "upper"))
+                  for r in out[int(first[q * S + p]):int(first[q * S + p + 1])]] for p in range(S)] for q in range(Q)]
+
+    def overlap_reads(self, queries, min_overlap, max_overlap=0, max_reads=0, read_stride=256, raw=False):
+        """(reads, matches): reads[q][shard] = [(overlap, ordinal, read)] of the reads of that shard that begin with a
+        suffix of query q of min_overlap symbols or more, each once at its longest overlap, overlap descending then ordinal
+        ascending -- none for a (query, shard) with more than max_reads of them (0 = no limit); matches of shape (Q,
+        shards) = that number of distinct reads, over the limit or not; raw=True: (first, read strings, overlap, ordinal,
+        matches) as rsbwt_set_overlap_reads writes them.  Every shard must be opened for reads."""
+        text, off = self._var_text(queries)
+        Q, S = len(queries), len(self.shards)
+        first = np.zeros(Q * S + 1, np.uint64)
+        matches = np.zeros(max(Q * S, 1), np.uint64)
+        n = C.c_size_t()
+        rc = lib().rsbwt_set_overlap_reads(self._s, _ptr(text), _ptr(off), Q, min_overlap, max_overlap, max_reads, _ptr(first), None,
+                                           read_stride, None, None, None, 0, C.byref(n), _ptr(matches))
+        if rc not in (0, -7):
+            check(rc)
+        total = n.value
+        reads = np.zeros((max(total, 1), read_stride), np.uint8)
+        ln = np.zeros(max(total, 1), np.uint32)
+        ov = np.zeros(max(total, 1), np.uint32)
+        od = np.zeros(max(total, 1), np.uint64)
+        if total:
+            check(lib().rsbwt_set_overlap_reads(self._s, _ptr(text), _ptr(off), Q, min_overlap, max_overlap, max_reads, _ptr(first),
+                                                _ptr(reads), read_stride, _ptr(ln), _ptr(ov), _ptr(od), total, C.byref(n), _ptr(matches)))
+            if (ln[:total] == 0xFFFFFFFF).any():
+                raise RsbwtError(-1, "a read does not fit read_stride")
+        strs = [reads[r, :ln[r]].tobytes().decode() for r in range(total)]
+        m = matches[:Q * S].reshape(Q, S).copy()
+        if raw:
+            return first, strs, ov[:total], od[:total], m
+        return [[[(int(ov[r]), int(od[r]), strs[r]) for r in range(int(first[q * S + p]), int(first[q * S + p + 1]))]
+                 for p in range(S)] for q in range(Q)], m
+
+    @staticmethod
+    def overlap_last_work():
+        """{items, lf_steps, passes, table_starts, dollar_only_passes, entries} of this thread's last overlap call"""
+        w = np.zeros(6, np.uint64)
+        lib().rsbwt_set_overlap_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return dict(zip(("items", "lf_steps", "passes", "table_starts", "dollar_only_passes", "entries"), (int(x) for x in w)))
 
     # -- BASELINE configs[3] / configs[4] over the set: per-shard results side by side, the way the front-end
     # concatenates its partitions' replies (src/service/server.cpp:199-261)

@@ -1957,6 +1957,43 @@ int rsbwt_match_lengths(rsbwt_t *h, const char *text, const uint64_t *off, size_
     });
 }
 
+// ---- overlaps (overlaps.hip): one handle = a set of one ---------------------------------------
+
+int rsbwt_overlaps(rsbwt_t *h, const char *text, const uint64_t *off, size_t Q, uint32_t min_overlap, uint32_t max_overlap, uint64_t *count,
+                   uint64_t *ordinal) {
+    return guarded("rsbwt_overlaps", [&]() -> int {
+        overlap_set_last_work(nullptr);
+        if (!h && rsbwt_device_count() == 0) return fail(RSBWT_ENODEV, "no HIP device is visible: the popBWT engine has no CPU fallback");
+        if (!h) return fail(RSBWT_EINVAL, "null handle");
+        std::vector<uint64_t> rel;
+        size_t N = 0;
+        int rc = match_check_batch(text, off, Q, &rel, &N);
+        if (rc) return rc;
+        if (N == 0) return RSBWT_OK;
+        if (!count) return fail(RSBWT_EINVAL, "null argument");
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index");
+        if ((rc = use_device(h->device)) != RSBWT_OK) return rc;
+        call_ctx *c = h->pool.acquire();
+        if (!c) return fail(RSBWT_EHIP, "cannot create a HIP stream");
+        struct release_t {
+            rsbwt_t *h;
+            call_ctx *c;
+            ~release_t() { h->pool.release(c); }
+        } release{h, c};
+        std::vector<uint64_t> pairs(2 * N);
+        uint64_t work6[6] = {Q, 0, 0, 0, 0, 0};
+        rc = overlap_host_views(h->scratch, c->st[0], h->d_view, 1, text + off[0], rel.data(), Q, N, min_overlap, max_overlap, pairs.data(), nullptr,
+                                work6 + 1);
+        if (rc) return rc;
+        for (size_t t = 0; t < N; ++t) {
+            if (ordinal) ordinal[t] = pairs[2 * t];
+            count[t] = pairs[2 * t + 1];
+        }
+        overlap_set_last_work(work6);
+        return RSBWT_OK;
+    });
+}
+
 // ---- synthetic data ---------------------------------------------------------------------------
 
 int rsbwt_synth_runs_dev(void *d_runs, uint64_t num_runs, uint64_t seed, int device, void *stream) {

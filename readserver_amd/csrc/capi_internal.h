@@ -128,6 +128,16 @@ int match_host_views(scratch_cache &scratch, hipStream_t st, const shard_view *d
                      size_t N, uint32_t cap, uint64_t m, uint32_t *len, uint64_t *pairs, std::vector<rsbwt_smem> *smems, uint64_t *work4);
 void match_set_last_work(const uint64_t work6[6]);
 void match_get_last_work(uint64_t work6[6]);
+// overlaps.hip: what the host-buffer overlap calls share (capi.hip: one handle; sets.hip: a set); batches are checked by
+// match_check_batch.
+//   overlap_host_views  one device's share on `st` (synchronised before it returns): pairs {ordinal, count}[S][N] and recs
+//                       (the entries with count > 0; shard = d_views' number, unordered), each optional; work5 += the
+//                       launch's counters
+//   overlap_set / get_last_work: what rsbwt_set_overlap_last_work reports for the calling thread
+int overlap_host_views(scratch_cache &scratch, hipStream_t st, const shard_view *d_views, uint32_t S, const char *t0, const uint64_t *rel, size_t Q,
+                       size_t N, uint32_t min_overlap, uint32_t max_overlap, uint64_t *pairs, std::vector<rsbwt_overlap> *recs, uint64_t *work5);
+void overlap_set_last_work(const uint64_t work6[6]);
+void overlap_get_last_work(uint64_t work6[6]);
 // 1-mismatch hit list of one shard from variants expanded once for the whole batch (sets.hip: every shard of a set
 // searches the same variants)
 size_t variants_bytes(size_t m, uint32_t k);

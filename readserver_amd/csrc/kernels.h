@@ -302,6 +302,25 @@ hipError_t launch_match_stats(const shard_view *d_shards, uint32_t nshards, cons
                               unsigned long long *d_work, hipStream_t stream);
 hipError_t launch_match_smems(uint32_t nshards, const match_batch &bt, const void *d_len, const void *d_pairs, void *d_smems, uint64_t cap_records,
                               unsigned long long *d_counter, hipStream_t stream);
+// overlaps.hip: the reads that begin with a suffix of a query (include/rsbwt.h: the definition).  A batch is laid out as
+// a match_batch's; position t names the suffix of its query that starts there.
+struct overlap_batch {
+    const char *text;
+    const uint64_t *off;  // [Q + 1]
+    size_t Q, N;
+    uint32_t min_overlap;  // >= 1
+    uint32_t max_overlap;  // 0 = none
+};
+//   launch_overlaps: one lane per (query, shard): d_pairs {ordinal, count}[nshards][N] is zeroed on `stream` and the
+//     entries with count > 0 written; d_ivals {lower, upper}[nshards][N] (optional) is written at those entries ONLY;
+//     d_work (optional, zeroed by the caller) [0..4] += LF steps, lane-passes that fetched a line, starts from the k-mer
+//     table, lane-passes fetched for '$' alone, entries with count > 0
+//   launch_overlap_records: those entries compacted: d_out rsbwt_overlap[cap_records] (shard = the launch's number),
+//     *d_counter (zeroed by the caller) of them in all, in no particular order
+hipError_t launch_overlaps(const shard_view *d_shards, uint32_t nshards, const overlap_batch &bt, void *d_pairs, void *d_ivals,
+                           unsigned long long *d_work, hipStream_t stream);
+hipError_t launch_overlap_records(uint32_t nshards, const overlap_batch &bt, const void *d_pairs, const void *d_ivals, void *d_out,
+                                  uint64_t cap_records, unsigned long long *d_counter, hipStream_t stream);
 // (SEL_SHIFT, sample_window, window_samples, window_psi_hint: line_format.h -- shared with the host-side layout test)
 // query / query_exactmatch (query.cpp:87-120) over extracted reads
 hipError_t launch_match_reads(const void *d_reads, const void *d_len, size_t n, uint32_t stride, const void *d_owner,

@@ -2081,6 +2081,233 @@ void rsbwt_set_match_last_work(uint64_t *work6) {
     if (work6) match_get_last_work(work6);
 }
 
+// ---- overlaps (overlaps.hip): the reads that begin with a suffix of a query, in every shard ----
+namespace {
+// Each device group walks its shards' rows of the (query, shard) grid; answers are per (position, shard), so the host
+// only puts group gi's row j at row idx[j].  count / ordinal [S][N] and recs (ordered by (query, shard, start)) are each
+// optional.
+int overlap_call(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t min_overlap, uint32_t max_overlap, uint64_t *count,
+                 uint64_t *ordinal, std::vector<rsbwt_overlap> *recs) {
+    overlap_set_last_work(nullptr);
+    // (no set can be had on a box without a GPU: the call says so instead of blaming the argument)
+    if (!s && rsbwt_device_count() == 0) return fail(RSBWT_ENODEV, "no HIP device is visible: the popBWT engine has no CPU fallback");
+    if (!s) return fail(RSBWT_EINVAL, "null set");
+    std::vector<uint64_t> rel;
+    size_t N = 0;
+    int rc = match_check_batch(text, off, Q, &rel, &N);
+    if (rc) return rc;
+    if (N == 0) return RSBWT_OK;
+    if (!count && !recs) return fail(RSBWT_EINVAL, "null argument");
+    const size_t S = s->shards.size();
+    for (rsbwt_t *h : s->shards)
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
+    if (S > 65535) return fail(RSBWT_EINVAL, "%zu shards: at most 65535", S);
+    struct group_out {
+        std::vector<uint64_t> pairs;
+        std::vector<rsbwt_overlap> recs;
+        uint64_t work[5] = {0, 0, 0, 0, 0};
+    };
+    std::vector<group_out> outs(s->groups.size());
+    rc = for_each_group(s, [&](size_t gi) -> int {
+        dev_group *g = s->groups[gi];
+        group_call gc(g);
+        if (gc.rc) return gc.rc;
+        group_out &o = outs[gi];
+        const size_t Sg = g->idx.size();
+        if (count) o.pairs.resize(2 * Sg * N);
+        return overlap_host_views(g->scratch, gc.st, g->d_views, (uint32_t)Sg, text + off[0], rel.data(), Q, N, min_overlap, max_overlap,
+                                  count ? o.pairs.data() : nullptr, recs ? &o.recs : nullptr, o.work);
+    });
+    if (rc) return rc;
+    uint64_t work6[6] = {(uint64_t)S * Q, 0, 0, 0, 0, 0};
+    for (size_t gi = 0; gi < outs.size(); ++gi) {
+        const dev_group *g = s->groups[gi];
+        const group_out &o = outs[gi];
+        for (size_t j = 0; count && j < g->idx.size(); ++j) {
+            const size_t p = g->idx[j];
+            for (size_t t = 0; t < N; ++t) {
+                if (ordinal) ordinal[p * N + t] = o.pairs[2 * (j * N + t)];
+                count[p * N + t] = o.pairs[2 * (j * N + t) + 1];
+            }
+        }
+        for (int i = 0; i < 5; ++i) work6[1 + i] += o.work[i];
+        if (recs)
+            for (rsbwt_overlap r : o.recs) {
+                r.shard = (uint32_t)g->idx[r.shard];
+                recs->push_back(r);
+            }
+    }
+    if (recs)
+        std::sort(recs->begin(), recs->end(), [](const rsbwt_overlap &x, const rsbwt_overlap &y) {
+            return x.query != y.query ? x.query < y.query : x.shard != y.shard ? x.shard < y.shard : x.start < y.start;
+        });
+    overlap_set_last_work(work6);
+    return RSBWT_OK;
+}
+
+// first[] of records ordered by (query, shard): cell c = q * S + p holds records first[c] .. first[c + 1]
+void overlap_first(const std::vector<rsbwt_overlap> &recs, size_t cells, size_t S, uint64_t *first) {
+    for (size_t c = 0; c <= cells; ++c) first[c] = 0;
+    for (const rsbwt_overlap &r : recs) first[(size_t)r.query * S + r.shard + 1] += 1;
+    for (size_t c = 0; c < cells; ++c) first[c + 1] += first[c];
+}
+}  // namespace
+
+int rsbwt_set_overlaps(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t min_overlap, uint32_t max_overlap,
+                       uint64_t *count, uint64_t *ordinal) {
+    return guarded("rsbwt_set_overlaps", [&]() -> int {
+        if (s && Q && !count) return fail(RSBWT_EINVAL, "null argument");  // (ordinal alone is not a form of the call)
+        return overlap_call(s, text, off, Q, min_overlap, max_overlap, count, ordinal, nullptr);
+    });
+}
+
+int rsbwt_set_overlap_records(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t min_overlap, uint32_t max_overlap,
+                              uint64_t *first, rsbwt_overlap *out, size_t cap, size_t *nrecords) {
+    return guarded("rsbwt_set_overlap_records", [&]() -> int {
+        if (!nrecords || (!first && Q)) return fail(RSBWT_EINVAL, "null argument");
+        *nrecords = 0;
+        std::vector<rsbwt_overlap> recs;
+        const int rc = overlap_call(s, text, off, Q, min_overlap, max_overlap, nullptr, nullptr, &recs);
+        if (rc) return rc;
+        if (first) overlap_first(recs, Q * s->shards.size(), s->shards.size(), first);
+        *nrecords = recs.size();
+        if (recs.size() > cap) return fail(RSBWT_ERANGE, "%zu overlap records, room for %zu", recs.size(), cap);
+        if (recs.empty()) return RSBWT_OK;
+        if (!out) return fail(RSBWT_EINVAL, "null argument");
+        memcpy(out, recs.data(), recs.size() * sizeof(rsbwt_overlap));
+        return RSBWT_OK;
+    });
+}
+
+// The reads call is a composition of what exists: the records; per (query, shard) the union of their ordinal ranges taken
+// from the longest overlap down, so that a read is reported once, at its longest; the ordinals to rows by getOccAt('$',
+// o + 1), a launch per shard; the set extraction.
+int rsbwt_set_overlap_reads(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t min_overlap, uint32_t max_overlap,
+                            uint64_t max_reads, uint64_t *first, char *reads, uint32_t read_stride, uint32_t *read_len, uint32_t *overlap,
+                            uint64_t *ordinal, size_t cap_reads, size_t *nreads, uint64_t *matches) {
+    return guarded("rsbwt_set_overlap_reads", [&]() -> int {
+        if (!nreads || (!first && Q)) return fail(RSBWT_EINVAL, "null argument");
+        *nreads = 0;
+        if (s)
+            for (rsbwt_t *h : s->shards)
+                if (!rsbwt_opened_for_reads(h)) return fail(RSBWT_EINVAL, "overlap reads need shards opened with RSBWT_OPEN_READS");
+        if (s && Q && read_stride == 0) return fail(RSBWT_EINVAL, "read_stride must be positive");
+        std::vector<rsbwt_overlap> recs;
+        const int rc = overlap_call(s, text, off, Q, min_overlap, max_overlap, nullptr, nullptr, &recs);
+        if (rc) return rc;
+        const size_t S = s->shards.size(), cells = Q * S;
+        if (first)
+            for (size_t c = 0; c <= cells; ++c) first[c] = 0;
+        for (size_t c = 0; matches && c < cells; ++c) matches[c] = 0;
+        // the records of a cell arrive longest suffix first; what a shorter suffix's range adds are the ordinals no
+        // longer one has covered (a range lies inside a later one exactly when the shorter suffix is a prefix of the
+        // longer: a periodic query)
+        struct piece {
+            uint64_t a, b;  // ordinals [a, b)
+            uint32_t overlap;
+        };
+        std::vector<piece> pieces;
+        std::vector<size_t> piece_first(cells + 1, 0);
+        uint64_t total = 0;
+        for (size_t i = 0; i < recs.size();) {
+            const size_t cell = (size_t)recs[i].query * S + recs[i].shard;
+            std::vector<std::pair<uint64_t, uint64_t>> covered;  // disjoint, ascending
+            const size_t p0 = pieces.size();
+            uint64_t distinct = 0;
+            for (; i < recs.size() && (size_t)recs[i].query * S + recs[i].shard == cell; ++i) {
+                const uint64_t a = recs[i].ordinal, b = a + recs[i].count;
+                uint64_t at = a;
+                std::vector<std::pair<uint64_t, uint64_t>> next;
+                size_t k = 0;
+                for (; k < covered.size() && covered[k].second <= a; ++k) next.push_back(covered[k]);
+                uint64_t lo = a, hi = b;
+                for (; k < covered.size() && covered[k].first < b; ++k) {
+                    if (covered[k].first > at) pieces.push_back(piece{at, covered[k].first, recs[i].length});
+                    at = std::max(at, covered[k].second);
+                    lo = std::min(lo, covered[k].first);
+                    hi = std::max(hi, covered[k].second);
+                }
+                if (at < b) pieces.push_back(piece{at, b, recs[i].length});
+                next.emplace_back(lo, hi);
+                for (; k < covered.size(); ++k) next.push_back(covered[k]);
+                covered.swap(next);
+            }
+            for (size_t k = p0; k < pieces.size(); ++k) distinct += pieces[k].b - pieces[k].a;
+            if (matches) matches[cell] = distinct;
+            if (max_reads && distinct > max_reads) pieces.resize(p0);  // over the limit: none, and nobody else's are touched
+            else total += distinct;
+            piece_first[cell + 1] = pieces.size();
+        }
+        for (size_t c = 0; c < cells; ++c) piece_first[c + 1] = std::max(piece_first[c + 1], piece_first[c]);
+        if (first) {
+            uint64_t run = 0;
+            for (size_t c = 0; c < cells; ++c) {
+                first[c] = run;
+                for (size_t k = piece_first[c]; k < piece_first[c + 1]; ++k) run += pieces[k].b - pieces[k].a;
+            }
+            first[cells] = run;
+        }
+        *nreads = (size_t)total;
+        if (total > cap_reads) return fail(RSBWT_ERANGE, "%llu reads over the set, room for %zu", (unsigned long long)total, cap_reads);
+        if (total == 0) return RSBWT_OK;
+        if (!reads || !read_len) return fail(RSBWT_EINVAL, "null argument");
+        // the ordinals in the caller's order, then per shard their rows: getOccAt('$', o + 1)
+        std::vector<uint32_t> shard_of((size_t)total);
+        std::vector<uint64_t> ords((size_t)total), rows((size_t)total);
+        size_t r = 0;
+        for (size_t c = 0; c < cells; ++c)
+            for (size_t k = piece_first[c]; k < piece_first[c + 1]; ++k)
+                for (uint64_t o = pieces[k].a; o < pieces[k].b; ++o, ++r) {
+                    shard_of[r] = (uint32_t)(c % S);
+                    ords[r] = o;
+                    if (overlap) overlap[r] = pieces[k].overlap;
+                    if (ordinal) ordinal[r] = o;
+                }
+        for (size_t p = 0; p < S; ++p) {
+            std::vector<size_t> where;
+            std::vector<uint64_t> bc;
+            for (size_t t = 0; t < (size_t)total; ++t)
+                if (shard_of[t] == p) {
+                    where.push_back(t);
+                    bc.push_back(ords[t] + 1);
+                }
+            if (where.empty()) continue;
+            const std::vector<char> syms(where.size(), '$');
+            std::vector<uint64_t> got(where.size());
+            const int ro = rsbwt_occ_at_batch(s->shards[p], syms.data(), bc.data(), bc.size(), got.data());
+            if (ro) return ro;
+            for (size_t t = 0; t < where.size(); ++t) rows[where[t]] = got[t];
+        }
+        return rsbwt_set_extract_body(s, shard_of.data(), rows.data(), (size_t)total, reads, read_stride, read_len, nullptr);
+    });
+}
+
+int rsbwt_set_overlaps_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, size_t N, uint32_t min_overlap,
+                           uint32_t max_overlap, void *d_pairs, void *stream) {
+    dev_group *g = nullptr;
+    const int rc = one_device_group(s, &g);
+    if (rc) return rc;
+    if (Q == 0 || N == 0) return RSBWT_OK;
+    if (!d_text || !d_off || !d_pairs) return fail(RSBWT_EINVAL, "null argument");
+    if (N >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu positions in one call: at most 2^31 - 1", N);
+    for (rsbwt_t *h : s->shards)
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
+    if (s->shards.size() > 65535) return fail(RSBWT_EINVAL, "%zu shards: at most 65535", s->shards.size());
+    overlap_batch bt;
+    bt.text = (const char *)d_text;
+    bt.off = (const uint64_t *)d_off;
+    bt.Q = Q;
+    bt.N = N;
+    bt.min_overlap = min_overlap ? min_overlap : 1u;
+    bt.max_overlap = max_overlap;
+    const hipError_t e = launch_overlaps(g->d_views, (uint32_t)g->idx.size(), bt, d_pairs, nullptr, nullptr, (hipStream_t)stream);
+    return e == hipSuccess ? RSBWT_OK : fail_hip(e, "overlap kernel launch");
+}
+
+void rsbwt_set_overlap_last_work(uint64_t *work6) {
+    if (work6) overlap_get_last_work(work6);
+}
+
 static size_t hits_1mm_scratch_one(const rsbwt_set_t *s, size_t m, uint32_t k) {
     size_t need = 0;
     for (rsbwt_t *h : s->shards) need = std::max(need, rsbwt_hits_1mm_scratch_bytes(h, m, k));

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Randomised differential campaign on the GPU box (not part of the suite: it runs for as long as it is
 told to): random run streams x layouts (window span, k-mer table depth) x query lengths, the HIP path
-against the oracle -- intervals, counts, the 1-mismatch hit list against the dense matrices, getOccAt, read
-extraction row by row, and (two-shard sets) the set-level hit lists and query lists.  Test infrastructure: the oracle is the checker, as in tests/.
+against the oracle -- intervals, counts, the 1-mismatch hit list against the dense matrices, getOccAt, matching
+statistics and overlaps against the tests' restatements, read extraction row by row, and (two-shard sets) the set-level hit lists and query lists.  Test infrastructure: the oracle is the checker, as in tests/.
 Prints a progress line per configuration and one JSON line at the end; exit code 1 on any difference.
 usage: tools/fuzz_parity.py [seconds=300] [seed=1]"""
 import ctypes as C
@@ -16,7 +16,10 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import gt_reference  # noqa: E402
+import match_reference  # noqa: E402
 import oracle_binding  # noqa: E402
+import overlap_reference  # noqa: E402
 import readserver_amd as rsb  # noqa: E402
 
 SECONDS = float(sys.argv[1]) if len(sys.argv) > 1 else 300.0
@@ -268,6 +271,26 @@ while time.time() < t_end:
                     gi = g.occ_at_batch(ch, bcs)
                     assert all(int(gi[i]) == oix.occ_at(ch, int(bcs[i])) for i in range(0, 300, 7)), "getOccAt"
                     assert np.array_equal(g.occ_batch(ch, gi), bcs), "getOcc(getOccAt)"
+            # matching statistics and overlaps on a few hundred positions (csrc/match_stats.hip, csrc/overlaps.hip) against
+            # the restatements over the oracle the tests use: pieces of the spelled-out rows, random strings, an N, an
+            # empty query
+            sh = gt_reference.OracleShard(oix)
+            mq = []
+            for tx in texts[:6]:
+                if tx:
+                    a = int(rng.integers(0, len(tx)))
+                    mq.append(tx[a:a + int(rng.integers(1, 41))].decode())
+            mq += ["".join("ACGT"[c] for c in rng.integers(0, 4, int(rng.integers(1, 41)))) for _ in range(4)]
+            mq += ["", "ACGTNACGT"[:int(rng.integers(5, 10))]]
+            max_len, min_rows = int(rng.integers(0, 2)) * int(rng.integers(1, 20)), int([1, 1, 3, 20][int(rng.integers(0, 4))])
+            want = [match_reference.longest(sh, n, w, e, max_len, min_rows) for w in mq for e in range(1, len(w) + 1)]
+            ln, mlo, mup = g.match_lengths(mq, max_len, min_rows, intervals=True)
+            assert [(int(a), int(b), int(c)) for a, b, c in zip(ln, mlo, mup)] == want, f"match_lengths (max_len {max_len}, min_rows {min_rows})"
+            mo, xo = int(rng.integers(1, 14)), int(rng.integers(0, 2)) * int(rng.integers(1, 41))
+            side = overlap_reference.OracleSide(sh)
+            want = [x[:2] for w in mq for x in overlap_reference.profile(side, w, mo, xo)]
+            cnt, od = g.overlaps(mq, mo, xo, ordinals=True)
+            assert [(int(b), int(a)) for a, b in zip(cnt, od)] == want, f"overlaps (min_overlap {mo}, max_overlap {xo})"
             stride = 2048
             out = np.zeros((rows.size, stride), np.uint8)
             ln = np.empty(rows.size, np.uint32)

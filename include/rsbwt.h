@@ -690,6 +690,58 @@ int rsbwt_set_overlap_reads(rsbwt_set_t *s, const char *text, const uint64_t *of
                             uint64_t max_reads, uint64_t *first, char *reads, uint32_t read_stride, uint32_t *read_len, uint32_t *overlap,
                             uint64_t *ordinal, size_t cap_reads, size_t *nreads, uint64_t *matches);
 void rsbwt_set_overlap_last_work(uint64_t *work6);
+/* The per-read sample table: "which samples carry this read".  Replaces, for the return types All and Samples, the
+ * RocksDB lookups of the reference -- sdb->Get(read, &value) in QueryTask::run (src/service/service.cpp:1292-1348), KmerTask::run
+ * (:917-975) and DbTask::run (:816-845) -- by a table in HBM keyed by the read's ordinal: per shard off u64[num_strings + 1]
+ * and the value bytes back to back, the value of ordinal o = bytes[off[o] .. off[o+1]).  The table holds raw bytes; what a
+ * record is (size_of_sample, has_other_meta_data) only the Reply encoder below knows.  Each shard's table lives on that
+ * shard's device.  The FM index is the hash from read string to ordinal: (ordinal, copies) of a string come from the
+ * whole-read search of rsbwt_read_copies, ordinal = Occ('$', lower - 1) -- rsbwt_locate's and rsbwt_set_overlaps' number.
+ *   rsbwt_set_meta_build       pair i = read text[off[i] .. off[i+1]) with value values[voff[i] .. voff[i+1]).  In every shard
+ *                              every ordinal of [ordinal, ordinal + copies) takes the value (all copies of a string share one
+ *                              RocksDB key).  A string given twice: the pair with the higher index wins (batch.Put overwrites,
+ *                              src/util/load_data_into_rocksdb.cpp:50), whatever the order the GPU takes them in.  A string that
+ *                              is empty, holds a symbol outside ACGT, is longer than 65,535 symbols or matches no shard is
+ *                              counted and changes nothing; an ordinal no pair reaches has an empty value.  A second build
+ *                              replaces the table.  stats4 (may be NULL) = {pairs that matched at least one shard, pairs that
+ *                              matched none, ordinals given a value (an empty one included), value bytes stored}.
+ *   rsbwt_set_meta_load        the same from the file load_data_into_rocksdb reads: line 1 a read, line 2 its value up to the
+ *                              newline, repeated (:44); a last read without a value line is ignored, '\r' is a byte like any
+ *                              other, "the higher index wins" holds over the whole file.  RSBWT_EIO: unreadable.
+ *   rsbwt_set_meta_clear       frees the table.
+ *   rsbwt_set_meta_bytes       its bytes in HBM over all shards (0: none).
+ * BUILD, LOAD AND CLEAR MUST NOT RUN BESIDE A LOOKUP (or each other) ON THE SAME SET: they replace what the lookups read.
+ * The lookups are re-entrant like the other set calls, need neither RSBWT_OPEN_READS nor a k-mer table, and use no atomics:
+ *   rsbwt_set_read_ordinals_var   rsbwt_set_read_copies_var with one more output: ordinal / copies u64[S][Q] in the set's
+ *                                 shard order; ordinal = Occ('$', lower - 1) where copies > 0, else 0.  The same search.
+ *   rsbwt_set_meta_by_ordinal     item i = ordinal[i] of shard shard_of[i]; first has n + 1 entries, the value of item i is
+ *                                 bytes[first[i] .. first[i+1]), in the order asked; an ordinal may be asked any number of
+ *                                 times.  An ordinal >= num_strings or UINT64_MAX (locate's "not located"): empty.  A shard
+ *                                 index out of range: RSBWT_EINVAL; a set without a table: RSBWT_EINVAL ("no sample table").
+ *                                 cap too small (cap = 0 sizes the buffer): RSBWT_ERANGE with *nbytes and first[] set.
+ *   rsbwt_set_meta_by_ordinal_dev a set on ONE device; d_shard u32[n] / d_ordinal u64[n] as rsbwt_set_interval_rows_dev and
+ *                                 rsbwt_set_locate_dev write them; d_first u64[n + 1] is always written, d_bytes only when
+ *                                 d_first[n] <= cap; a shard index out of range gives an empty value.  Enqueues on `stream`,
+ *                                 synchronises nothing.
+ *   rsbwt_set_read_meta_var       strings in, values out: the value of query q in shard p is item q * S + p (first has
+ *                                 Q * S + 1 entries, the layout of the KmerMatch calls), taken at the read's FIRST ordinal,
+ *                                 empty where copies == 0; copies u64[S][Q] may be NULL.  On a one-device set search, sizing,
+ *                                 scan and copy stay on the device: first[] and the bytes come back.
+ *   rsbwt_set_meta_last_work      the calling thread's last lookup call: {items, items with a value, value bytes copied, LF
+ *                                 steps of the string searches (counted only while rsbwt_set_set_counting is on, else 0)}. */
+int rsbwt_set_meta_build(rsbwt_set_t *s, const char *text, const uint64_t *off, const uint8_t *values, const uint64_t *voff, size_t n,
+                         uint64_t *stats4);
+int rsbwt_set_meta_load(rsbwt_set_t *s, const char *path, uint64_t *stats4);
+int rsbwt_set_meta_clear(rsbwt_set_t *s);
+uint64_t rsbwt_set_meta_bytes(const rsbwt_set_t *s);
+int rsbwt_set_read_ordinals_var(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *ordinal, uint64_t *copies);
+int rsbwt_set_meta_by_ordinal(rsbwt_set_t *s, const uint32_t *shard_of, const uint64_t *ordinal, size_t n, uint64_t *first, uint8_t *bytes,
+                              size_t cap, size_t *nbytes);
+int rsbwt_set_meta_by_ordinal_dev(rsbwt_set_t *s, const void *d_shard, const void *d_ordinal, size_t n, void *d_first, void *d_bytes,
+                                  size_t cap, void *stream);
+int rsbwt_set_read_meta_var(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *first, uint8_t *bytes, size_t cap,
+                            size_t *nbytes, uint64_t *copies);
+void rsbwt_set_meta_last_work(uint64_t *work4);
 /* Device-resident forms, for a set on ONE device (one process per GPU: bench.py --mode 1mm|extract).
  * d_hits [num_shards][cap_per_shard] x 32-byte records (rsbwt_hits_1mm_dev's), d_totals u64[num_shards];
  * d_rows [num_shards][n] (row numbers are per shard), d_out [num_shards][n][stride], d_len / d_prefix_len [num_shards][n]. */
@@ -748,6 +800,26 @@ int rsbwt_proto_decode_request_ks(const uint8_t *msg, size_t len, int32_t *k, in
 /* The Reply a reference service sends for a request it finds nothing for: for Request type t and return type rt,
  * strand revcomp -- what rsbwt_service_set_unserved answers with (0 = bad arguments / no such reply). */
 size_t rsbwt_proto_encode_empty_reply(uint8_t *out, size_t cap, int t, int rt, const char *q, size_t qlen, int revcomp);
+
+/* Reply{rt = request_type, t = (ReplyType) return_type, q, a = ReplyAll{forward_matches | revcomp_matches = ResultAll{r, s*}*}}
+ * (readserver.proto:16-29,39-54): what QueryTask::run (src/service/service.cpp:1292-1348; request_type 2) and KmerTask::run
+ * (:917-975; request_type 3) send for the return types All (3) and Samples (4) -- the reference sets t = 4 for Samples and
+ * still fills `a` (:1263).  Read i carries the ReadInfo records spelled from its value values[i] (value_len[i] bytes; values
+ * NULL: none) exactly as :1332-1347 spell them: per record g = hash[value.substr(pos, size_of_sample)] -- `hash` is the text
+ * of the service's hash file, lines of `name \t code` (:1477-1488; the first line of a code wins, a code not in it gives
+ * g = "", as std::map::operator[] does) -- and, with has_other_meta_data, c = (int)(signed char)value[pos] - 33 and l likewise
+ * from the next byte (negative values are ten-byte varints), else c = l = 0; required fields are written even when 0.
+ * THE ONE DIVERGENCE: a value whose length is not a multiple of the record size is cut at its last whole record (the
+ * reference reads past the end of the string there).  Returns the bytes needed (written when out != NULL and they fit cap);
+ * 0 = bad arguments (size_of_sample 0 without meta data among them: a record of no bytes). */
+size_t rsbwt_proto_encode_all_reply(uint8_t *out, size_t cap, int request_type, int return_type, const char *q, size_t qlen, int revcomp,
+                                    const char *const *reads, const size_t *read_len, const uint8_t *const *values, const size_t *value_len,
+                                    size_t nreads, const char *hash, size_t hash_len, uint32_t size_of_sample, int has_other_meta_data);
+/* Host only: the pairs rsbwt_set_meta_load would build from the file at `path` (the parser alone).  sizes3 = {pairs, read
+ * bytes, value bytes} is always set; RSBWT_ERANGE when a buffer is too small or NULL (call once to size them), RSBWT_EIO when
+ * the file cannot be read.  off / voff receive pairs + 1 entries. */
+int rsbwt_meta_parse_file(const char *path, char *text, size_t text_cap, uint64_t *off, uint8_t *values, size_t values_cap, uint64_t *voff,
+                          size_t cap_pairs, size_t *sizes3);
 
 /* The service's configuration file: the libconfig subset the reference's service.cfg uses
  * (`key = "value";`, `key = [ "a", ... ];`, comments; demo/TEMPLATE.service.cfg).  Loading fails with
@@ -809,7 +881,8 @@ void rsbwt_service_set_other_handler(rsbwt_service_t *s, rsbwt_service_other_fn 
  * Tiles are visited in the order of the reference's container (std::unordered_set<std::string>, filled the same
  * way): the same order on the same C++ standard library.  A query holding a symbol outside ACGT matches nothing
  * (find_reads' short-query branch would search it as it stands; count_reads, the pre-flight, answers 0 for it).
- * The return type All needs the RocksDB shards: still the `other` handler's.  enable = 0: Reads requests go to the
+ * The return types All and Samples are answered once the set has a sample table (rsbwt_service_set_all), else they are the
+ * `other` handler's.  enable = 0: Reads requests go to the
  * `other` handler too, as before round 5. */
 void rsbwt_service_set_reads(rsbwt_service_t *s, int enable, uint32_t min_read_length, uint32_t max_read_length);
 /* service.cfg's `suffix` of every shard of the set (demo/TEMPLATE.service.cfg:16-17), n = rsbwt_set_size (0: none):
@@ -833,6 +906,17 @@ uint64_t rsbwt_service_capped_requests(const rsbwt_service_t *s); /* Reads reque
  * SiteMatch; service.cfg `unserved = "empty"`): 2 replies per partition on `push` carrying no matches, as the
  * reference sends for an empty result.  The first such request is logged once.  Default off. */
 void rsbwt_service_set_unserved(rsbwt_service_t *s, int empty);
+/* ExactMatch requests with return type All or Samples (`output=all`, what scripts/client.pl asks for by default), and KmerMatch
+ * ones when rsbwt_service_set_kmermatch is on: answered in the window -- the reads of the Reads paths, in their order and
+ * under their rules (tiles, suffix filter, min / max read length, max_match_reads: a strand over the limit gets empty lists),
+ * each read with its `s` from the set's sample table (rsbwt_set_read_meta_var over the reads of each Reply, in their own
+ * partition), one rsbwt_proto_encode_all_reply per partition and strand on `push`.  hashfile / size_of_sample /
+ * has_other_meta_data: service.cfg's keys (service.cpp:1410-1415,1425; hashfile NULL or "": every g is "").  service.cfg:
+ * `meta = "<pairs file>"`.  RSBWT_EINVAL: the set has no sample table, or a shard was not opened with RSBWT_OPEN_READS;
+ * RSBWT_EIO: the hash file cannot be read.  Default off: such requests go to the `other` handler / rsbwt_service_set_unserved
+ * as before.  Before rsbwt_service_run / _start. */
+int rsbwt_service_set_all(rsbwt_service_t *s, int enable, const char *hashfile, uint32_t size_of_sample, int has_other_meta_data);
+uint64_t rsbwt_service_all_requests(const rsbwt_service_t *s); /* All / Samples requests answered so far */
 /* The loop is a pipeline: the thread that runs it receives and cuts the windows, `workers` threads answer a whole
  * window each (decode, one batched search per query length, Reply bytes -- the set's entry points are re-entrant),
  * a sender thread sends the windows' Replies in window order, so replies still leave in arrival order.  Default 8,

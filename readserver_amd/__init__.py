@@ -27,4 +27,6 @@ from .bwt import (  # noqa: F401
     synth_popbwt,
     write_bpi2,
     check_bpi2,
+    encode_all_reply,
+    parse_meta_file,
 )

@@ -209,6 +209,21 @@ SIGNATURES = {
                                           C.c_size_t, C.POINTER(C.c_size_t), _vp]),
     "rsbwt_set_overlap_last_work": (None, [_u64p]),
     "rsbwt_service_kmer_requests": (C.c_uint64, [_vp]),
+    "rsbwt_set_meta_build": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "rsbwt_set_meta_load": (C.c_int, [_vp, C.c_char_p, _vp]),
+    "rsbwt_set_meta_clear": (C.c_int, [_vp]),
+    "rsbwt_set_meta_bytes": (C.c_uint64, [_vp]),
+    "rsbwt_set_read_ordinals_var": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "rsbwt_set_meta_by_ordinal": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rsbwt_set_meta_by_ordinal_dev": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    "rsbwt_set_read_meta_var": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t), _vp]),
+    "rsbwt_set_meta_last_work": (None, [_u64p]),
+    "rsbwt_proto_encode_all_reply": (C.c_size_t, [_vp, C.c_size_t, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_char_p),
+                                                  C.POINTER(C.c_size_t), C.POINTER(_vp), C.POINTER(C.c_size_t), C.c_size_t, C.c_char_p,
+                                                  C.c_size_t, C.c_uint32, C.c_int]),
+    "rsbwt_meta_parse_file": (C.c_int, [C.c_char_p, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rsbwt_service_set_all": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_uint32, C.c_int]),
+    "rsbwt_service_all_requests": (C.c_uint64, [_vp]),
     "rsbwt_proto_encode_kmer_reply": (C.c_size_t, [_vp, C.c_size_t, C.c_int, C.c_char_p, C.c_size_t, C.c_int,
                                                    C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_size_t]),
     "rsbwt_proto_encode_empty_reply": (C.c_size_t, [_vp, C.c_size_t, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.c_int]),

@@ -750,6 +750,99 @@ class ShardSet:
         lib().rsbwt_set_overlap_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
         return dict(zip(("items", "lf_steps", "passes", "table_starts", "dollar_only_passes", "entries"), (int(x) for x in w)))
 
+    # -- the per-read sample table (csrc/read_meta.hip): rsbwt_set_meta_* / rsbwt_set_read_meta_var
+    @staticmethod
+    def _var_bytes(values):
+        bs = [bytes(v) for v in values]
+        off = np.zeros(len(bs) + 1, np.uint64)
+        off[1:] = np.cumsum([len(b) for b in bs], dtype=np.uint64)
+        return np.frombuffer(b"".join(bs) + b"\0", np.uint8).copy(), off
+
+    def meta_build(self, reads, values):
+        """Builds the set's sample table from (read, value bytes) pairs; a read given twice keeps the later value.
+        Returns {matched, unmatched, ordinals, bytes} (rsbwt_set_meta_build).  Not beside a lookup on this set."""
+        if len(reads) != len(values):
+            raise ValueError("reads and values differ in length")
+        text, off = self._var_text(reads)
+        vals, voff = self._var_bytes(values)
+        st = np.zeros(4, np.uint64)
+        check(lib().rsbwt_set_meta_build(self._s, _ptr(text), _ptr(off), _ptr(vals), _ptr(voff), len(reads), _ptr(st)))
+        return dict(zip(("matched", "unmatched", "ordinals", "bytes"), (int(x) for x in st)))
+
+    def meta_load(self, path):
+        """The same from the file load_data_into_rocksdb reads: a read line, a value line, repeated (rsbwt_set_meta_load)"""
+        st = np.zeros(4, np.uint64)
+        check(lib().rsbwt_set_meta_load(self._s, str(path).encode(), _ptr(st)))
+        return dict(zip(("matched", "unmatched", "ordinals", "bytes"), (int(x) for x in st)))
+
+    def meta_clear(self):
+        check(lib().rsbwt_set_meta_clear(self._s))
+
+    def meta_bytes(self):
+        """bytes of the sample table in HBM over all shards (0: none)"""
+        return int(lib().rsbwt_set_meta_bytes(self._s))
+
+    def read_ordinals(self, queries):
+        """(ordinal, copies) of shape (shards, Q): per shard the first ordinal of the reads equal to each query (0 where
+        there is none) and how many there are (rsbwt_set_read_ordinals_var)"""
+        text, off = self._var_text(queries)
+        Q, S = len(queries), len(self.shards)
+        od = np.zeros((S, Q), np.uint64)
+        cp = np.zeros((S, Q), np.uint64)
+        check(lib().rsbwt_set_read_ordinals_var(self._s, _ptr(text), _ptr(off), Q, _ptr(od), _ptr(cp)))
+        return od, cp
+
+    def meta_by_ordinal(self, shard_of, ordinal, raw=False):
+        """the values of (shard, ordinal) items, in the order asked: a list of bytes; raw=True: (first, bytes array)
+        (rsbwt_set_meta_by_ordinal)"""
+        sh = np.ascontiguousarray(shard_of, dtype=np.uint32).ravel()
+        od = np.ascontiguousarray(ordinal, dtype=np.uint64).ravel()
+        if sh.size != od.size:
+            raise ValueError("shard_of and ordinal differ in length")
+        first = np.zeros(od.size + 1, np.uint64)
+        n = C.c_size_t()
+        rc = lib().rsbwt_set_meta_by_ordinal(self._s, _ptr(sh), _ptr(od), od.size, _ptr(first), None, 0, C.byref(n))
+        if rc not in (0, -7):
+            check(rc)
+        out = np.zeros(max(n.value, 1), np.uint8)
+        if n.value:
+            check(lib().rsbwt_set_meta_by_ordinal(self._s, _ptr(sh), _ptr(od), od.size, _ptr(first), _ptr(out), n.value, C.byref(n)))
+        if raw:
+            return first, out[:n.value]
+        return [out[int(first[i]):int(first[i + 1])].tobytes() for i in range(od.size)]
+
+    def meta_by_ordinal_dev(self, d_shard, d_ordinal, n, d_first, d_bytes, cap, stream=None):
+        """device pointers (ints) in, nothing synchronised (rsbwt_set_meta_by_ordinal_dev)"""
+        check(lib().rsbwt_set_meta_by_ordinal_dev(self._s, d_shard, d_ordinal, n, d_first, d_bytes, cap, stream))
+
+    def read_meta(self, queries, raw=False):
+        """strings in, values out: ([query][shard] -> bytes, copies of shape (shards, Q)); raw=True: (first, bytes array,
+        copies) with the value of query q in shard p at item q * S + p (rsbwt_set_read_meta_var)"""
+        text, off = self._var_text(queries)
+        Q, S = len(queries), len(self.shards)
+        first = np.zeros(Q * S + 1, np.uint64)
+        cp = np.zeros((S, max(Q, 1)), np.uint64)
+        n = C.c_size_t()
+        cap = 64 * Q * S + 256
+        out = np.zeros(cap, np.uint8)
+        rc = lib().rsbwt_set_read_meta_var(self._s, _ptr(text), _ptr(off), Q, _ptr(first), _ptr(out), cap, C.byref(n), _ptr(cp))
+        if rc == -7:
+            cap = n.value
+            out = np.zeros(max(cap, 1), np.uint8)
+            rc = lib().rsbwt_set_read_meta_var(self._s, _ptr(text), _ptr(off), Q, _ptr(first), _ptr(out), cap, C.byref(n), _ptr(cp))
+        check(rc)
+        cp = cp[:, :Q]
+        if raw:
+            return first, out[:n.value], cp
+        return [[out[int(first[q * S + p]):int(first[q * S + p + 1])].tobytes() for p in range(S)] for q in range(Q)], cp
+
+    @staticmethod
+    def meta_last_work():
+        """{items, valued, bytes, lf_steps} of this thread's last sample lookup (lf_steps: in counting mode only)"""
+        w = np.zeros(4, np.uint64)
+        lib().rsbwt_set_meta_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return dict(zip(("items", "valued", "bytes", "lf_steps"), (int(x) for x in w)))
+
     # -- BASELINE configs[3] / configs[4] over the set: per-shard results side by side, the way the front-end
     # concatenates its partitions' replies (src/service/server.cpp:199-261)
     def hits_1mm(self, kmers):
@@ -839,6 +932,46 @@ class ShardSet:
                 raise RsbwtError(-1, "a read does not fit read_stride")
         return [[(int(sh[r]), reads[r, :ln[r]].tobytes().decode()) for r in range(int(first[q]), int(first[q + 1]))]
                 for q in range(Q)]
+
+
+def encode_all_reply(request_type, return_type, q, revcomp, reads, values, hash_text=b"", size_of_sample=2, has_other_meta_data=True):
+    """Reply{rt, t = return type, q, a = ReplyAll{ResultAll{r, s*}*}} as the reference's QueryTask / KmerTask send it for All
+    and Samples: reads (str / bytes) with their sample-table values (bytes); hash_text = the hash file's text
+    (rsbwt_proto_encode_all_reply)"""
+    rs = [r if isinstance(r, (bytes, bytearray)) else str(r).encode() for r in reads]
+    vs = [bytes(v) for v in values]
+    if len(rs) != len(vs):
+        raise ValueError("reads and values differ in length")
+    qb = q if isinstance(q, (bytes, bytearray)) else str(q).encode()
+    hb = hash_text if isinstance(hash_text, (bytes, bytearray)) else str(hash_text).encode()
+    n = len(rs)
+    rp = (C.c_char_p * max(n, 1))(*rs)
+    rl = (C.c_size_t * max(n, 1))(*[len(r) for r in rs])
+    keep = [C.create_string_buffer(v, max(len(v), 1)) for v in vs]
+    vp = (C.c_void_p * max(n, 1))(*[C.addressof(b) for b in keep])
+    vl = (C.c_size_t * max(n, 1))(*[len(v) for v in vs])
+    args = (request_type, return_type, qb, len(qb), 1 if revcomp else 0, rp, rl, vp, vl, n, hb, len(hb), size_of_sample,
+            1 if has_other_meta_data else 0)
+    need = lib().rsbwt_proto_encode_all_reply(None, 0, *args)
+    if need == 0:
+        raise RsbwtError(-1, "bad arguments to rsbwt_proto_encode_all_reply")
+    out = np.zeros(need, np.uint8)
+    lib().rsbwt_proto_encode_all_reply(_ptr(out), need, *args)
+    return out.tobytes()
+
+
+def parse_meta_file(path):
+    """(reads, values): the pairs rsbwt_set_meta_load builds from a file, as lists of bytes (host only: rsbwt_meta_parse_file)"""
+    sz = (C.c_size_t * 3)()
+    rc = lib().rsbwt_meta_parse_file(str(path).encode(), None, 0, None, None, 0, None, 0, sz)
+    if rc not in (0, -7):
+        check(rc)
+    n, tb, vb = sz[0], sz[1], sz[2]
+    text, vals = np.zeros(max(tb, 1), np.uint8), np.zeros(max(vb, 1), np.uint8)
+    off, voff = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+    check(lib().rsbwt_meta_parse_file(str(path).encode(), _ptr(text), tb, _ptr(off), _ptr(vals), vb, _ptr(voff), n, sz))
+    return ([text[int(off[i]):int(off[i + 1])].tobytes() for i in range(n)],
+            [vals[int(voff[i]):int(voff[i + 1])].tobytes() for i in range(n)])
 
 
 def write_bpi2(bwt_path, bpi2_path=None):

@@ -1203,7 +1203,7 @@ namespace rsb {
 
 int read_copies_launch(search_meter &m, const shard_view *d_views, uint32_t nshards, int num_cus, const void *d_packed,
                        const void *d_valid, const void *d_len, size_t Q, uint32_t k, void *d_scratch, void *d_copies, void *d_ending,
-                       hipStream_t stream) {
+                       hipStream_t stream, void *d_ordinal) {
     if (Q == 0 || nshards == 0) return RSBWT_OK;
     uint8_t *d_rec = (uint8_t *)d_scratch, *d_pairs = d_rec + (size_t)nshards * Q * 16;
     hipError_t e = launch_read_seed(d_views, nshards, d_valid, d_len, Q, k, d_rec, stream);
@@ -1217,7 +1217,7 @@ int read_copies_launch(search_meter &m, const shard_view *d_views, uint32_t nsha
     ex.narrow = true;
     int rc = search_launch(m, d_views, nshards, num_cus, d_packed, d_valid, Q, k, d_pairs, nullptr, false, stream, &ex);
     if (rc) return rc;
-    e = launch_dollar_count(d_views, nshards, d_pairs, Q, d_copies, d_ending, m.counting ? m.d_work : nullptr, stream);
+    e = launch_dollar_count(d_views, nshards, d_pairs, Q, d_copies, d_ending, m.counting ? m.d_work : nullptr, stream, d_ordinal);
     if (e != hipSuccess) return fail_hip(e, "terminator-count kernel launch");
     return RSBWT_OK;
 }
@@ -1256,32 +1256,44 @@ int read_copies_host_views(search_meter &m, ctx_pool &pool, const shard_view *d_
 }
 
 // The same for queries of lengths of their own (for_each_var_slice): an empty query, one with a symbol outside ACGT or
-// one longer than 65,535 symbols gives 0 / 0.
+// one longer than 65,535 symbols gives 0 / 0.  ordinal (optional, [nshards][Q]): the first ordinal of the reads equal to
+// the query (0 where there is none); lf_steps (optional): += the LF steps of the searches when the meter is in counting
+// mode (word 0 of each slice's search launch; a slice then waits for its launch).
 int read_copies_host_views_var(search_meter &m, ctx_pool &pool, const shard_view *d_views, uint32_t nshards, int num_cus,
-                               const char *text, const uint64_t *off, size_t Q, uint64_t *copies, uint64_t *ending) {
+                               const char *text, const uint64_t *off, size_t Q, uint64_t *copies, uint64_t *ending, uint64_t *ordinal,
+                               uint64_t *lf_steps) {
     ctx_guard g(pool);
     if (!g.c) return fail(RSBWT_EHIP, "cannot create a HIP stream");
     hipStream_t st = g.c->st[0];
     auto a_scr = [&](size_t mq) { return al256(read_copies_scratch_bytes(nshards, mq)); };
     auto a_res = [&](size_t mq) { return al256((size_t)nshards * mq * 8); };
     return for_each_var_slice(
-        *g.c, st, text, off, Q, [&](size_t mq) { return a_scr(mq) + 2 * a_res(mq); },
+        *g.c, st, text, off, Q, [&](size_t mq) { return a_scr(mq) + 3 * a_res(mq); },
         [&](size_t q0, size_t mq) -> int {
             for (uint32_t s = 0; s < nshards; ++s)
                 for (size_t i = 0; i < mq; ++i) {
                     copies[s * Q + q0 + i] = 0;
                     if (ending) ending[s * Q + q0 + i] = 0;
+                    if (ordinal) ordinal[s * Q + q0 + i] = 0;
                 }
             return RSBWT_OK;
         },
         [&](const var_slice &sl) -> int {
             const size_t q0 = sl.q0, mq = sl.mq;
-            uint8_t *d_scr = sl.d_extra, *d_cp = d_scr + a_scr(mq), *d_en = d_cp + a_res(mq);
-            const int rc = read_copies_launch(m, d_views, nshards, num_cus, sl.d_pk, sl.d_ok, sl.d_len, mq, sl.k, d_scr, d_cp, ending ? d_en : nullptr, st);
+            uint8_t *d_scr = sl.d_extra, *d_cp = d_scr + a_scr(mq), *d_en = d_cp + a_res(mq), *d_od = d_en + a_res(mq);
+            const int rc = read_copies_launch(m, d_views, nshards, num_cus, sl.d_pk, sl.d_ok, sl.d_len, mq, sl.k, d_scr, d_cp, ending ? d_en : nullptr, st,
+                                              ordinal ? d_od : nullptr);
             if (rc) return rc;
             for (uint32_t s = 0; s < nshards; ++s) {
                 HIP_OK(hipMemcpyAsync(copies + s * Q + q0, d_cp + (size_t)s * mq * 8, mq * 8, hipMemcpyDeviceToHost, st));
                 if (ending) HIP_OK(hipMemcpyAsync(ending + s * Q + q0, d_en + (size_t)s * mq * 8, mq * 8, hipMemcpyDeviceToHost, st));
+                if (ordinal) HIP_OK(hipMemcpyAsync(ordinal + s * Q + q0, d_od + (size_t)s * mq * 8, mq * 8, hipMemcpyDeviceToHost, st));
+            }
+            if (lf_steps && m.counting) {
+                unsigned long long w0 = 0;
+                HIP_OK(hipMemcpyAsync(&w0, m.d_work, sizeof w0, hipMemcpyDeviceToHost, st));
+                HIP_OK(hipStreamSynchronize(st));
+                *lf_steps += w0;
             }
             return RSBWT_OK;
         });

@@ -101,16 +101,17 @@ int search_launch_walk(search_meter &m, const shard_view *d_views, uint32_t nsha
                        void *d_sparse, void *d_hit_bits, hipStream_t stream);
 int meter_history_ms(search_meter &m, float *ms, size_t cap, size_t *count);
 // Whole-read matches by backward search from the terminator rows (read_lookup.hip): start records, the search launch,
-// the '$' count -- copies / ending [nshards][Q] (ending may be null).  d_len: the queries' own lengths (u32[Q]), or
+// the '$' count -- copies / ending / ordinal [nshards][Q] (ending and ordinal may be null).  d_len: the queries' own lengths (u32[Q]), or
 // nullptr when every query has k symbols; d_scratch: read_copies_scratch_bytes(nshards, Q) bytes the launches may use.
 inline size_t read_copies_scratch_bytes(uint32_t nshards, size_t Q) { return (size_t)nshards * Q * 32; }
 int read_copies_launch(search_meter &m, const shard_view *d_views, uint32_t nshards, int num_cus, const void *d_packed,
                        const void *d_valid, const void *d_len, size_t Q, uint32_t k, void *d_scratch, void *d_copies, void *d_ending,
-                       hipStream_t stream);
+                       hipStream_t stream, void *d_ordinal = nullptr);
 int read_copies_host_views(search_meter &m, ctx_pool &pool, const shard_view *d_views, uint32_t nshards, int num_cus,
                            const char *kmers, size_t Q, uint32_t k, size_t stride, uint64_t *copies, uint64_t *ending);
 int read_copies_host_views_var(search_meter &m, ctx_pool &pool, const shard_view *d_views, uint32_t nshards, int num_cus,
-                               const char *text, const uint64_t *off, size_t Q, uint64_t *copies, uint64_t *ending);
+                               const char *text, const uint64_t *off, size_t Q, uint64_t *copies, uint64_t *ending,
+                               uint64_t *ordinal = nullptr, uint64_t *lf_steps = nullptr);
 // locate.hip: rows in host memory located through c's staging buffer (shard_of null: the one shard of d_views), the
 // answers into the caller's arrays (each optional), work2[0..1] += {rows ended on '$', LF steps}; and what
 // rsbwt_locate_last_work reports for the calling thread

@@ -135,8 +135,41 @@ uint32_t trace_entries(const shard_view &ix, uint32_t k);
 // continuation, 15 results that needed a second line are ADDED to.
 hipError_t launch_read_seed(const shard_view *d_shards, uint32_t nshards, const void *d_valid, const void *d_len, size_t Q, uint32_t k,
                             void *d_init, hipStream_t stream);
+// d_ordinal (optional, u64[nshards][Q]): Occ('$', lower - 1) where copies > 0, else 0 -- the first of the dense read
+// numbers (rsbwt_locate's ordinal) of the reads equal to the query; the rank is the one the count takes anyway.
 hipError_t launch_dollar_count(const shard_view *d_shards, uint32_t nshards, const void *d_pairs, size_t Q, void *d_copies,
-                               void *d_ending, unsigned long long *d_work, hipStream_t stream);
+                               void *d_ending, unsigned long long *d_work, hipStream_t stream, void *d_ordinal = nullptr);
+// read_meta.hip: the per-read sample table (rsbwt_set_meta_*).  A shard's table is off u64[num_strings + 1] and packed
+// value bytes: the value of ordinal o is bytes[off[o] .. off[o+1]).  off == nullptr: no table.
+struct meta_view {
+    const uint64_t *off;
+    const uint8_t *bytes;
+    uint64_t num_strings;
+};
+constexpr uint64_t META_NONE = ~0ull;  // src[] of an item that brings no bytes
+size_t meta_scan_bytes(size_t n);      // temporary bytes of launch_meta_scan over n values
+// d_first[n] = exclusive scan of d_len[n] (u64; the callers put a 0 behind the last length, so the last element is the total)
+hipError_t launch_meta_scan(void *d_temp, size_t temp_bytes, const void *d_len, void *d_first, size_t n, hipStream_t stream);
+// Sizes: one lane per item.  d_len u64[n + 1] (d_len[n] = 0) and d_src u64[n] (the item's first byte in its shard's
+// table, META_NONE for an item without bytes).  Q == 0: item i is ordinal d_ordinal[i] of shard d_shard[i] (d_shard
+// nullptr: shard 0).  Q > 0 (n = Q * S): item q * S + p is ordinal d_ordinal[p * Q + q] of shard p where
+// d_copies[p * Q + q] > 0, else empty -- the [S][Q] arrays launch_dollar_count writes.  A shard >= S, an ordinal >=
+// num_strings (UINT64_MAX included) and a shard without table give an empty value.
+hipError_t launch_meta_sizes(const meta_view *d_meta, uint32_t S, const void *d_shard, const void *d_ordinal, const void *d_copies,
+                             size_t Q, size_t n, void *d_len, void *d_src, hipStream_t stream);
+// Copy: item i's bytes = base[d_src[i] ..) -> d_dst[d_first[i] .. d_first[i+1]); base = d_base if given, else its shard's
+// table (shards as in launch_meta_sizes).  Nothing is written when d_first[n] > cap.
+hipError_t launch_meta_copy(const meta_view *d_meta, uint32_t S, const void *d_shard, size_t Q, const void *d_base, const void *d_src,
+                            const void *d_first, size_t n, void *d_dst, uint64_t cap, hipStream_t stream);
+// Build: pairs [base, base + n) of a build with (ordinal, copies) in one shard: win[o] = max(win[o], index + 1) over every
+// ordinal o of the pair (atomicMax: the pair with the higher index wins, whatever the order of the lanes)
+hipError_t launch_meta_winners(const void *d_ordinal, const void *d_copies, size_t n, uint64_t base, void *d_win, uint64_t num_strings,
+                               hipStream_t stream);
+// for the ordinals won by a pair of [c0, c1): d_len[o] = that pair's value length, d_src[o] = its value's offset from the
+// chunk's first value byte (d_voff = voff[c0 .. c1], c1 - c0 + 1 entries); either output may be nullptr; an ordinal won
+// by another chunk keeps its d_len and gets d_src META_NONE.  *d_given (optional) += ordinals with a winner in the chunk.
+hipError_t launch_meta_winner_values(const void *d_win, uint64_t num_strings, const void *d_voff, uint64_t c0, uint64_t c1, void *d_len,
+                                     void *d_src, void *d_given, hipStream_t stream);
 // The 1-mismatch search of a set by worklist (mm1_worklist.hip; k <= 32, 0 < tn < k, one table depth k - tn for all
 // shards).  launch_mm1_worklists takes the step of the three substitutions of every traced position (d_trace
 // [nshards][m][tn], d_own [nshards][m] pairs: the traced search's output) and appends the variants that survive it to

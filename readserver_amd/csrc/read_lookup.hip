@@ -17,7 +17,9 @@
 //     { 0 | L << 40 | INIT_EXPLICIT | INIT_VAR, C['A'] - 1 } -- the interval is all terminator rows, the next symbol is
 //     index L - 1, so all L symbols are stepped; no k-mer table is consulted (the pattern ends in '$');
 //   * the search launch as it is (search_lines.hip, search_extra::d_init), results as {lower, upper} pairs;
-//   * the '$'-COUNT kernel below: one lane per result, one 128-byte line fetch per non-empty result.
+//   * the '$'-COUNT kernel below: one lane per result, one 128-byte line fetch per non-empty result.  Its Occ('$', lower - 1)
+//     is also the first of the dense read numbers (rsbwt_locate's ordinal) of the reads equal to w: an optional third
+//     output, what the sample table is keyed by (read_meta.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -71,7 +73,8 @@ enum { WORK_RL_RANKED = 13, WORK_RL_CONT = 14, WORK_RL_SECOND = 15 };
 // (spill chunk / far line), or in another window.
 __global__ void __launch_bounds__(64 * WG_WAVES)
 read_dollar_count_kernel(const shard_view *__restrict__ shards, const ulonglong2 *__restrict__ pairs, size_t Q,
-                         uint64_t *__restrict__ copies, uint64_t *__restrict__ ending, unsigned long long *__restrict__ work) {
+                         uint64_t *__restrict__ copies, uint64_t *__restrict__ ending, unsigned long long *__restrict__ work,
+                         uint64_t *__restrict__ ordinal) {
     __shared__ uint4 s_stage[WG_WAVES][64 * SLOT_U4];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint4 *stage = s_stage[wave];
@@ -103,7 +106,7 @@ read_dollar_count_kernel(const shard_view *__restrict__ shards, const ulonglong2
     glds_fetch(lines_bytes, want, lane, stage_lds);  // (every lane takes part: lanes with nothing to rank ask for nothing)
     glds_wait();
 
-    uint64_t cp = 0, en = 0;
+    uint64_t cp = 0, en = 0, first = 0;
     uint32_t conts = 0;
     bool second = false;
     if (proper) {
@@ -137,10 +140,12 @@ read_dollar_count_kernel(const shard_view *__restrict__ shards, const ulonglong2
         }
         cp = occU - occL;
         en = hi - lo + 1ull;
+        first = cp ? occL : 0ull;  // the reads equal to the query are the ordinals [occL, occL + cp)
     }
     if (in) {
         copies[at] = cp;
         if (ending) ending[at] = en;
+        if (ordinal) ordinal[at] = first;
     }
     if (work) {
         const uint32_t ranked = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(proper));
@@ -170,12 +175,12 @@ hipError_t launch_read_seed(const shard_view *d_shards, uint32_t nshards, const 
 }
 
 hipError_t launch_dollar_count(const shard_view *d_shards, uint32_t nshards, const void *d_pairs, size_t Q, void *d_copies,
-                               void *d_ending, unsigned long long *d_work, hipStream_t stream) {
+                               void *d_ending, unsigned long long *d_work, hipStream_t stream, void *d_ordinal) {
     if (Q == 0 || nshards == 0) return hipSuccess;
     if (nshards > 65535u) return hipErrorInvalidValue;  // (the shard is the grid's y)
     const dim3 grid((unsigned)((Q + 64 * WG_WAVES - 1) / (64 * WG_WAVES)), nshards);
     hipLaunchKernelGGL(read_dollar_count_kernel, grid, dim3(64 * WG_WAVES), 0, stream, d_shards, (const ulonglong2 *)d_pairs, Q,
-                       (uint64_t *)d_copies, (uint64_t *)d_ending, d_work);
+                       (uint64_t *)d_copies, (uint64_t *)d_ending, d_work, (uint64_t *)d_ordinal);
     return hipGetLastError();
 }
 

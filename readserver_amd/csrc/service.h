@@ -7,10 +7,12 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/rsbwt.h"
+#include "meta_file.h"
 
 namespace rsb {
 
@@ -48,7 +50,22 @@ struct reads_config {
     uint64_t max_match_reads = 0;
     std::vector<std::string> suffix;                      // service.cfg `suffix` of each shard of the set ("" where absent): a tile is looked
                                                           // up only in the partitions whose suffix it ends with (is_suffix_of, :228-230)
+    // rsbwt_service_set_all (service.cfg `meta`): ExactMatch / KmerMatch requests whose return type is All or Samples are
+    // answered too -- the reads of the Reads paths, each with its ReadInfo records from the set's sample table
+    // (QueryTask::run's default branch, service.cpp:1292-1348; KmerTask::run, :917-975)
+    bool serve_all = false;
+    bool serve_reads = true;                  // rsbwt_service_set_reads' enable: off = Reads requests are not this batch's
+    std::map<std::string, std::string> hash;  // sample code -> name (service.cfg `hashfile`)
+    uint32_t size_of_sample = 2;              // service.cfg `size_of_sample` (service.cpp:59,1410-1412)
+    bool has_other_meta_data = true;          // service.cfg `has_other_meta_data` (:60,1413-1415)
 };
+// What the All / Samples paths reach the sample table through (sets.hip fills it in, as query_engine_hooks)
+struct meta_engine {
+    int (*read_meta_var)(rsbwt_set_t *, const char *, const uint64_t *, size_t, uint64_t *, uint8_t *, size_t, size_t *, uint64_t *);
+    uint64_t (*meta_bytes)(const rsbwt_set_t *);
+};
+extern meta_engine meta_engine_hooks;
+inline bool service_is_all_return(const service_request &r) { return r.rt == 3 || r.rt == 4; }  // All, Samples
 // capped (optional): capped[i] = 1 when a strand of request i was over cfg.max_match_reads
 int service_reads_batch(rsbwt_set_t *set, const std::vector<service_request> &rq, bool per_partition, const reads_config &cfg,
                         reply_arena *replies, std::vector<char> *handled, std::vector<char> *capped = nullptr);
@@ -61,12 +78,21 @@ struct query_engine {
 };
 extern query_engine query_engine_hooks;
 // the same requests answered with EMPTY read lists (a failed batch: the front-end has no timeout, server.cpp:469)
-void service_reads_empty(const std::vector<service_request> &rq, size_t rows, reply_arena *replies, std::vector<char> *handled);
+// (cfg given: the requests service_reads_batch takes under it -- All / Samples ones get an empty ReplyAll)
+void service_reads_empty(const std::vector<service_request> &rq, size_t rows, reply_arena *replies, std::vector<char> *handled,
+                         const reads_config *cfg = nullptr);
 inline bool service_is_reads_request(const service_request &r) { return r.t == 2 && r.rt == 2; }  // ExactMatch + Reads
+// the requests service_reads_batch answers under cfg: ExactMatch + Reads, and + All / Samples when cfg.serve_all
+inline bool service_takes_reads(const service_request &r, const reads_config &cfg) {
+    return r.t == 2 && ((cfg.serve_reads && r.rt == 2) || (cfg.serve_all && service_is_all_return(r)));
+}
 
 // KmerMatch with return type Count or Reads (KmerTask::run, service.cpp:871-960 around find_kmer_reads :466-502): per
 // request, partition (or once, summed) and strand one Reply{rt = KmerMatch, t = (ReplyType) rt, q, c | r}.
 inline bool service_is_kmer_request(const service_request &r) { return r.t == 3 && (r.rt == 1 || r.rt == 2); }
+inline bool service_takes_kmer(const service_request &r, const reads_config &cfg) {
+    return service_is_kmer_request(r) || (cfg.serve_all && r.t == 3 && service_is_all_return(r));
+}
 int service_kmer_batch(rsbwt_set_t *set, const std::vector<service_request> &rq, bool per_partition, const reads_config &cfg,
                        reply_arena *replies, std::vector<char> *handled);
 // appends the 2 x rows Replies (per row: forward, reverse complement) a reference service sends for request r when it

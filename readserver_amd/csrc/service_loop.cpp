@@ -431,6 +431,9 @@ struct rsbwt_service {
     // KmerMatch Count / Reads (KmerTask, service.cpp:1537-1544 -> find_kmer_reads :466-502): answered here when on
     bool serve_kmer = false;
     std::atomic<uint64_t> kmer_requests{0};
+    // ExactMatch / KmerMatch requests with return type All or Samples answered from the set's sample table
+    // (rsbwt_service_set_all: reads_cfg.serve_all)
+    std::atomic<uint64_t> all_requests{0};
     // requests nothing here answers and no `other` handler takes: 2 x P empty Replies when on
     bool unserved_empty = false;
     std::atomic<bool> unserved_logged{false};
@@ -479,7 +482,7 @@ struct rsbwt_service {
         for (size_t i = 0; i < n; ++i) {
             job.parsed[i] = service_decode(job.msgs[i].data(), job.msgs[i].size(), &job.rq[i]) ? 1 : 0;
             if (!job.parsed[i]) { job.rq[i].t = 0; malformed++; }
-            else if (serve_reads && service_is_reads_request(job.rq[i])) any_reads = true;
+            else if (service_takes_reads(job.rq[i], reads_cfg)) any_reads = true;
         }
         const size_t rows = per_partition ? rsbwt_set_size(set) : 1;
         int rc = service_count_batch(set, job.rq, per_partition, &job.rep, &job.handled);
@@ -513,8 +516,8 @@ struct rsbwt_service {
         bool any_kmer = false, any_unserved = false;
         for (size_t i = 0; i < n; ++i) {
             if (!job.parsed[i] || job.handled[i]) continue;
-            if (serve_kmer && service_is_kmer_request(job.rq[i])) any_kmer = true;
-            else if (!(serve_reads && service_is_reads_request(job.rq[i]))) any_unserved = true;
+            if (serve_kmer && service_takes_kmer(job.rq[i], reads_cfg)) any_kmer = true;
+            else if (!service_takes_reads(job.rq[i], reads_cfg)) any_unserved = true;
         }
         any_unserved = any_unserved && unserved_empty && !other;
         if (!any_reads && !any_kmer && !any_unserved) return;
@@ -524,7 +527,7 @@ struct rsbwt_service {
             rc = service_reads_batch(set, job.rq, per_partition, reads_cfg, &rr, &handled_r, &capped_r);
             if (rc != RSBWT_OK) {
                 note_failure(rc, n, "read");
-                service_reads_empty(job.rq, rows, &rr, &handled_r);
+                service_reads_empty(job.rq, rows, &rr, &handled_r, &reads_cfg);
             } else {
                 for (size_t i = 0; i < capped_r.size(); ++i)
                     if (capped_r[i]) note_capped(job.rq[i]);
@@ -556,8 +559,9 @@ struct rsbwt_service {
                 all.bytes.insert(all.bytes.end(), src->bytes.begin() + src->off[j], src->bytes.begin() + src->off[j + 1]);
                 all.off.push_back(all.bytes.size());
             }
-            if (handled_r[i]) { job.handled[i] = 2; read_requests++; }
-            if (handled_k[i]) { job.handled[i] = 3; kmer_requests++; }
+            const bool is_all = service_is_all_return(job.rq[i]);  // (counted apart: the Reads / KmerMatch counters keep their meaning)
+            if (handled_r[i]) { job.handled[i] = 2; if (is_all) all_requests++; else read_requests++; }
+            if (handled_k[i]) { job.handled[i] = 3; if (is_all) all_requests++; else kmer_requests++; }
         }
         all.first[n] = all.off.size() - 1;
         job.rep = std::move(all);
@@ -567,8 +571,8 @@ struct rsbwt_service {
     // here takes
     bool is_unserved(const service_request &r) const {
         if (r.t < 2 || r.t > 4 || r.rt < 1 || r.rt > 4) return false;
-        if (r.t == 2 && (r.rt == 1 || (serve_reads && r.rt == 2))) return false;
-        if (serve_kmer && service_is_kmer_request(r)) return false;
+        if (r.t == 2 && (r.rt == 1 || service_takes_reads(r, reads_cfg))) return false;
+        if (serve_kmer && service_takes_kmer(r, reads_cfg)) return false;
         return true;
     }
     void note_unserved(const service_request &r) {
@@ -592,7 +596,7 @@ struct rsbwt_service {
         handled_k->assign(n, 0);
         for (size_t i = 0; i < n; ++i) {
             kr->first[i] = kr->off.size() - 1;
-            if (!job.parsed[i] || job.handled[i] || !service_is_kmer_request(job.rq[i])) continue;
+            if (!job.parsed[i] || job.handled[i] || !service_takes_kmer(job.rq[i], reads_cfg)) continue;
             (*handled_k)[i] = 1;
             service_append_empty(job.rq[i], rows, kr);
         }
@@ -681,7 +685,7 @@ struct rsbwt_service {
             }
             reply_arena all, rr;
             std::vector<char> handled_r;
-            service_reads_empty(job.rq, rows, &rr, &handled_r);
+            service_reads_empty(job.rq, rows, &rr, &handled_r, &reads_cfg);
             all.off.assign(1, 0);
             all.first.assign(n + 1, 0);
             job.handled.assign(n, 0);
@@ -698,13 +702,13 @@ struct rsbwt_service {
                             rsbwt_proto_encode_count_reply(all.bytes.data() + at, len, job.rq[i].t, job.rq[i].q.data(), job.rq[i].q.size(), strand, 0);
                             all.off.push_back(all.bytes.size());
                         }
-                } else if (serve_reads && job.parsed[i] && handled_r[i]) {
+                } else if (job.parsed[i] && handled_r[i]) {
                     job.handled[i] = 2;
                     for (size_t j = rr.first[i]; j < rr.first[i + 1]; ++j) {
                         all.bytes.insert(all.bytes.end(), rr.bytes.begin() + rr.off[j], rr.bytes.begin() + rr.off[j + 1]);
                         all.off.push_back(all.bytes.size());
                     }
-                }  else if (serve_kmer && job.parsed[i] && service_is_kmer_request(job.rq[i])) {
+                }  else if (serve_kmer && job.parsed[i] && service_takes_kmer(job.rq[i], reads_cfg)) {
                     job.handled[i] = 3;
                     service_append_empty(job.rq[i], rows, &all);
                 } else if (unserved_empty && !other && job.parsed[i] && is_unserved(job.rq[i])) {
@@ -981,6 +985,7 @@ void rsbwt_service_set_workers(rsbwt_service_t *s, int workers) {
 void rsbwt_service_set_reads(rsbwt_service_t *s, int enable, uint32_t min_read_length, uint32_t max_read_length) {
     if (!s) return;
     s->serve_reads = enable != 0;
+    s->reads_cfg.serve_reads = s->serve_reads;
     if (min_read_length) s->reads_cfg.min_read_length = min_read_length;
     if (max_read_length) s->reads_cfg.max_read_length = max_read_length;
 }
@@ -1078,6 +1083,41 @@ void rsbwt_service_stats(const rsbwt_service_t *s, uint64_t *stats6) {
     stats6[5] = s->max_batch_seen.load();
 }
 
+int rsbwt_service_set_all(rsbwt_service_t *s, int enable, const char *hashfile, uint32_t size_of_sample, int has_other_meta_data) {
+    return guarded("rsbwt_service_set_all", [&]() -> int {
+        if (!s) return fail(RSBWT_EINVAL, "null service");
+        if (!enable) {
+            s->reads_cfg.serve_all = false;
+            return RSBWT_OK;
+        }
+        if (!meta_engine_hooks.meta_bytes || !kmer_engine_hooks.opened_for_reads) return fail(RSBWT_ENODEV, "the sample table is not part of this build");
+        if (meta_engine_hooks.meta_bytes(s->set) == 0)
+            return fail(RSBWT_EINVAL, "All / Samples replies need the set's sample table (rsbwt_set_meta_build / rsbwt_set_meta_load): it has none");
+        for (size_t i = 0; i < rsbwt_set_size(s->set); ++i)
+            if (!kmer_engine_hooks.opened_for_reads(rsbwt_set_shard(s->set, i)))
+                return fail(RSBWT_EINVAL, "All / Samples replies need every shard opened with RSBWT_OPEN_READS; shard %zu was not", i);
+        if (size_of_sample == 0 && !has_other_meta_data) return fail(RSBWT_EINVAL, "size_of_sample 0 without other meta data: a record of no bytes");
+        std::map<std::string, std::string> hash;
+        if (hashfile && *hashfile) {
+            FILE *f = fopen(hashfile, "rb");
+            if (!f) return fail(RSBWT_EIO, "cannot open the hash file %s", hashfile);
+            std::string data;
+            char buf[1 << 16];
+            size_t got;
+            while ((got = fread(buf, 1, sizeof buf, f)) > 0) data.append(buf, got);
+            const bool bad = ferror(f) != 0;
+            fclose(f);
+            if (bad) return fail(RSBWT_EIO, "cannot read the hash file %s", hashfile);
+            meta_parse_hash(data.data(), data.size(), &hash);
+        }
+        s->reads_cfg.hash = std::move(hash);
+        s->reads_cfg.size_of_sample = size_of_sample;
+        s->reads_cfg.has_other_meta_data = has_other_meta_data != 0;
+        s->reads_cfg.serve_all = true;
+        return RSBWT_OK;
+    });
+}
+uint64_t rsbwt_service_all_requests(const rsbwt_service_t *s) { return s ? s->all_requests.load() : 0; }
 uint64_t rsbwt_service_read_requests(const rsbwt_service_t *s) { return s ? s->read_requests.load() : 0; }
 uint64_t rsbwt_service_kmer_requests(const rsbwt_service_t *s) { return s ? s->kmer_requests.load() : 0; }
 

@@ -2,8 +2,11 @@
 // the BWT-only paths (src/service/service.cpp:1366-1583).  Reads the same configuration file, loads the
 // BWT(s) into HBM, connects the same three sockets and answers CountReads, ExactMatch-Count and ExactMatch-Reads
 // requests in micro-batches (`GET /get?output=count|reads`), and KmerMatch Count / Reads when `kmermatch = "on"`;
-// requests of other types are left unanswered unless `unserved = "empty"` (they belong to the RocksDB-backed paths of
-// the reference's service, which can run beside this process on `push`).
+// with `meta = "<pairs file>"` also ExactMatch requests whose return type is All or Samples (`output=all`, what
+// scripts/client.pl asks for by default) and, with kmermatch on, KmerMatch ones: every read with its samples, from a
+// table in HBM built from the file the reference loads into RocksDB.  Requests of other types (SiteMatch; All / Samples
+// without `meta`) are left unanswered unless `unserved = "empty"` (they belong to the RocksDB-backed paths of the
+// reference's service, which can run beside this process on `push`).
 //
 // One process may hold many partitions: besides the reference's `prefix` (one BWT), the engine reads
 //   shards  = [ "<prefix of shard 0>", ... ];     one .bwt per suffix partition (64)
@@ -18,9 +21,15 @@
 //                                                 rows (rsbwt_exactmatch_by_search); the replies are the same (default extract)
 //   max_match_reads = "100000";                   an ExactMatch-Reads query (each strand by itself) that brings more reads than
 //                                                 this over all shards is answered with none (default: absent or "0", no limit)
+//   meta = "<pairs file>";                        the file load_data_into_rocksdb reads (line 1 a read, line 2 its value, repeated;
+//                                                 the reads.ids files of all partitions concatenated): loaded into the
+//                                                 per-read sample table in HBM, and All / Samples requests are answered with
+//                                                 `hashfile`, `size_of_sample` and `has_other_meta_data` as the reference reads
+//                                                 them (service.cpp:1410-1415,1425,1477-1488); needs reads = "on" (default: absent)
 //   unserved = "empty";                           requests of any other kind get 2 x shards Replies with no matches
 //                                                 (default: no reply, as before)
 // and then sends 2 x shards replies per request (front-end `workers` = 2 x shards) or 2 (`summed`).
+#include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -66,6 +75,12 @@ int main(int argc, char **argv) {
         return EXIT_FAILURE;
     }
     const bool serve_kmer = strcmp(kmermatch, "on") == 0;
+    const char *meta = get(cfg, "meta", "");
+    const char *sos = get(cfg, "size_of_sample", "2");  // (defaults: service.cpp:59-60)
+    if (*meta && (!*sos || strspn(sos, "0123456789") != strlen(sos) || strlen(sos) > 6)) {
+        fprintf(stderr, "service.cfg: size_of_sample = \"%s\": a non-negative decimal number\n", sos);
+        return EXIT_FAILURE;
+    }
     printf("starting server for %s\n", get(cfg, "suffix", ""));
     // the sockets first: a box without libzmq should say so before minutes are spent loading shards into HBM
     // (connecting is asynchronous in ZeroMQ: nothing is received until the loop polls)
@@ -94,7 +109,7 @@ int main(int argc, char **argv) {
     // include/rsbwt.h, RSBWT_OPEN_READS)
     const bool serve_reads = strcmp(get(cfg, "reads", "on"), "off") != 0;
     if (rsbwt_set_open(cpaths.data(), cpaths.size(), devs.data(),
-                       RSBWT_OPEN_KTAB_GROUPED | (serve_reads || serve_kmer ? RSBWT_OPEN_READS : 0u), &set) != RSBWT_OK) {
+                       RSBWT_OPEN_KTAB_GROUPED | (serve_reads || serve_kmer || *meta ? RSBWT_OPEN_READS : 0u), &set) != RSBWT_OK) {
         fprintf(stderr, "%s\n", rsbwt_last_error());
         return EXIT_FAILURE;
     }
@@ -103,6 +118,15 @@ int main(int argc, char **argv) {
         return EXIT_FAILURE;
     }
     printf("loaded %zu bwt shard(s) on %zu GPU(s).\n", rsbwt_set_size(set), rsbwt_set_devices(set));
+    if (*meta) {
+        uint64_t st[4] = {0, 0, 0, 0};
+        if (rsbwt_set_meta_load(set, meta, st) != RSBWT_OK) {
+            fprintf(stderr, "%s\n", rsbwt_last_error());
+            return EXIT_FAILURE;
+        }
+        printf("loaded the sample table: %llu pairs matched, %llu matched no shard, %llu reads with samples, %llu bytes in HBM.\n",
+               (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[2], (unsigned long long)rsbwt_set_meta_bytes(set));
+    }
     rsbwt_service_t *svc = nullptr;
     const bool summed = strcmp(get(cfg, "replies", "per_partition"), "summed") == 0;
     if (rsbwt_service_create(set, tr, atoll(get(cfg, "batch_window_us", "200")), (size_t)atoll(get(cfg, "batch_max", "4096")),
@@ -118,6 +142,12 @@ int main(int argc, char **argv) {
         return EXIT_FAILURE;
     }
     if (rsbwt_service_set_max_match_reads(svc, strtoull(max_match, nullptr, 10)) != RSBWT_OK) {
+        fprintf(stderr, "%s\n", rsbwt_last_error());
+        return EXIT_FAILURE;
+    }
+    // has_other_meta_data: "1" turns it on, anything else off (service.cpp:1413-1415); absent: on (:60)
+    if (*meta && rsbwt_service_set_all(svc, 1, get(cfg, "hashfile", ""), (uint32_t)atoi(sos),
+                                       rsbwt_service_config_get(cfg, "has_other_meta_data") ? strcmp(get(cfg, "has_other_meta_data", ""), "1") == 0 : 1) != RSBWT_OK) {
         fprintf(stderr, "%s\n", rsbwt_last_error());
         return EXIT_FAILURE;
     }

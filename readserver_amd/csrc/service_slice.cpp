@@ -343,7 +343,7 @@ inline size_t chunked_head(size_t n) {
 
 }  // namespace
 
-void service_reads_empty(const std::vector<service_request> &rq, size_t rows, reply_arena *replies, std::vector<char> *handled) {
+void service_reads_empty(const std::vector<service_request> &rq, size_t rows, reply_arena *replies, std::vector<char> *handled, const reads_config *cfg) {
     const size_t n = rq.size();
     handled->assign(n, 0);
     replies->bytes.clear();
@@ -352,7 +352,12 @@ void service_reads_empty(const std::vector<service_request> &rq, size_t rows, re
     const std::vector<const std::string *> none;
     for (size_t i = 0; i < n; ++i) {
         replies->first[i] = replies->off.size() - 1;
-        if (!service_is_reads_request(rq[i])) continue;
+        if (cfg ? !service_takes_reads(rq[i], *cfg) : !service_is_reads_request(rq[i])) continue;
+        if (service_is_all_return(rq[i])) {
+            (*handled)[i] = 1;
+            service_append_empty(rq[i], rows, replies);
+            continue;
+        }
         (*handled)[i] = 1;
         for (size_t r = 0; r < rows; ++r)
             for (int strand = 0; strand < 2; ++strand) {
@@ -411,6 +416,75 @@ static int for_each_parallel(size_t n, F &&fn) {
 }
 
 query_engine query_engine_hooks = {nullptr};
+meta_engine meta_engine_hooks = {nullptr, nullptr};
+
+namespace {
+
+sample_codec codec_of(const reads_config &cfg) {
+    sample_codec c;
+    c.hash = &cfg.hash;
+    c.size_of_sample = cfg.size_of_sample;
+    c.has_other = cfg.has_other_meta_data;
+    return c;
+}
+
+// The sample values of the reads of a batch's All / Samples Replies: entry e of list li (a read of partition
+// lshard[li][e]) has value bytes[first[at[li] + e] .. first[at[li] + e + 1]).  One rsbwt_set_read_meta_var call over
+// all those reads: read x is query x, its value in ITS partition p is item x * S + p -- the other partitions' items of
+// that query are answered and not used.
+struct all_values {
+    std::vector<size_t> at;      // first entry of list li among the looked-up reads (lists that are not All: unused)
+    std::vector<uint32_t> shard;  // per looked-up read
+    std::vector<uint64_t> first;
+    std::vector<uint8_t> bytes;
+    size_t S = 1;
+    int lookup(rsbwt_set_t *set, const std::vector<std::vector<const std::string *>> &lists, const std::vector<std::vector<uint32_t>> &lshard,
+               const std::vector<char> &is_all) {
+        S = rsbwt_set_size(set);
+        at.assign(lists.size(), 0);
+        std::string text;
+        std::vector<uint64_t> off(1, 0);
+        for (size_t li = 0; li < lists.size(); ++li) {
+            if (!is_all[li]) continue;
+            at[li] = shard.size();
+            for (size_t e = 0; e < lists[li].size(); ++e) {
+                text += *lists[li][e];
+                off.push_back(text.size());
+                shard.push_back(lshard[li][e]);
+            }
+        }
+        const size_t Q = shard.size();
+        first.assign(Q * S + 1, 0);
+        if (Q == 0) return RSBWT_OK;
+        if (!meta_engine_hooks.read_meta_var) return fail(RSBWT_ENODEV, "the sample table is not part of this build");
+        size_t need = 0;
+        bytes.resize(64 * Q + 256);  // (a typical value is a few records; a call that does not fit says what does)
+        int rc = meta_engine_hooks.read_meta_var(set, text.data(), off.data(), Q, first.data(), bytes.data(), bytes.size(), &need, nullptr);
+        if (rc == RSBWT_ERANGE) {
+            bytes.resize(need);
+            rc = meta_engine_hooks.read_meta_var(set, text.data(), off.data(), Q, first.data(), bytes.data(), bytes.size(), &need, nullptr);
+        }
+        return rc;
+    }
+    // the Reply of list li (QueryTask::run / KmerTask::run with return type All or Samples); bytes needed, written when p
+    size_t encode(uint8_t *p, size_t cap, size_t li, const std::vector<const std::string *> &l, int t, int rt, const std::string &q, bool revcomp,
+                  const sample_codec &codec) const {
+        const size_t m = l.size();
+        std::vector<const char *> rp(m);
+        std::vector<size_t> rl(m), vl(m);
+        std::vector<const uint8_t *> vp(m);
+        for (size_t e = 0; e < m; ++e) {
+            const size_t x = at[li] + e, item = x * S + shard[x];
+            rp[e] = l[e]->data();
+            rl[e] = l[e]->size();
+            vp[e] = bytes.data() + first[item];
+            vl[e] = (size_t)(first[item + 1] - first[item]);
+        }
+        return meta_encode_all_reply(p, cap, t, rt, q.data(), q.size(), revcomp, rp.data(), rl.data(), vp.data(), vl.data(), m, codec);
+    }
+};
+
+}  // namespace
 
 int service_reads_batch(rsbwt_set_t *set, const std::vector<service_request> &rq, bool per_partition, const reads_config &cfg,
                         reply_arena *replies, std::vector<char> *handled, std::vector<char> *capped) {
@@ -439,7 +513,7 @@ int service_reads_batch(rsbwt_set_t *set, const std::vector<service_request> &rq
     };
     std::vector<job_t> jobs;
     for (size_t i = 0; i < n; ++i) {
-        if (!service_is_reads_request(rq[i])) continue;
+        if (!service_takes_reads(rq[i], cfg)) continue;
         (*handled)[i] = 1;
         for (int strand = 0; strand < 2; ++strand) {
             job_t j;
@@ -598,13 +672,26 @@ int service_reads_batch(rsbwt_set_t *set, const std::vector<service_request> &rq
     // forward then reverse complement
     const size_t rows = per_partition ? S : 1;
     std::vector<std::vector<const std::string *>> lists(jobs.size() * rows);
+    std::vector<std::vector<uint32_t>> lshard(lists.size());  // the partition each entry came from (its samples are that partition's)
     for (size_t ji = 0; ji < jobs.size(); ++ji)
         for (size_t p = 0; p < S; ++p) {
             std::vector<const std::string *> &l = lists[ji * rows + (per_partition ? p : 0)];
             // (a partition's list: its tile matches first, then the reads that contain w: service.cpp:757-769)
             for (const std::string &t : jobs[ji].tiles[p]) l.push_back(&t);
             for (const std::string &t : jobs[ji].reads[p]) l.push_back(&t);
+            lshard[ji * rows + (per_partition ? p : 0)].resize(l.size(), (uint32_t)p);
         }
+    // All / Samples: every read of those requests' lists is looked up in its partition's sample table, in one call
+    std::vector<char> is_all(lists.size(), 0);
+    for (size_t ji = 0; ji < jobs.size(); ++ji)
+        if (service_is_all_return(rq[jobs[ji].req]))
+            for (size_t r = 0; r < rows; ++r) is_all[ji * rows + r] = 1;
+    all_values vals;
+    {
+        const int rc = vals.lookup(set, lists, lshard, is_all);
+        if (rc != RSBWT_OK) return rc;
+    }
+    const sample_codec codec = codec_of(cfg);
     if (!per_partition) {
         // joined lists keep find_reads' order WITHIN a partition; across partitions the front-end concatenates in
         // arrival order (server.cpp:199-261): here shard order, tiles and reads of shard 0 first
@@ -613,8 +700,14 @@ int service_reads_batch(rsbwt_set_t *set, const std::vector<service_request> &rq
     size_t total = 0, messages = 0;
     for (size_t ji = 0; ji < jobs.size(); ++ji)
         for (size_t r = 0; r < rows; ++r) {
-            body[ji * rows + r] = reads_body_len(lists[ji * rows + r]);
-            total += reads_reply_len(rq[jobs[ji].req].t, rq[jobs[ji].req].q.size(), body[ji * rows + r]);
+            const size_t li = ji * rows + r;
+            const service_request &q = rq[jobs[ji].req];
+            if (is_all[li]) {
+                total += vals.encode(nullptr, 0, li, lists[li], q.t, q.rt, q.q, jobs[ji].strand == 1, codec);
+            } else {
+                body[li] = reads_body_len(lists[li]);
+                total += reads_reply_len(q.t, q.q.size(), body[li]);
+            }
             ++messages;
         }
     replies->bytes.resize(total);
@@ -629,7 +722,8 @@ int service_reads_batch(rsbwt_set_t *set, const std::vector<service_request> &rq
         for (size_t r = 0; r < rows; ++r)
             for (int strand = 0; strand < 2; ++strand) {
                 const size_t li = (ji + strand) * rows + r;
-                p = encode_reads_reply(p, rq[i].t, rq[i].q, strand == 1, lists[li], body[li]);
+                if (is_all[li]) p += vals.encode(p, (size_t)(replies->bytes.data() + total - p), li, lists[li], rq[i].t, rq[i].rt, rq[i].q, strand == 1, codec);
+                else p = encode_reads_reply(p, rq[i].t, rq[i].q, strand == 1, lists[li], body[li]);
                 replies->off.push_back((size_t)(p - replies->bytes.data()));
             }
         ji += 2;
@@ -708,7 +802,7 @@ int service_kmer_batch(rsbwt_set_t *set, const std::vector<service_request> &rq,
     replies->first.assign(n + 1, 0);
     std::vector<kmer_job> jobs;
     for (size_t i = 0; i < n; ++i) {
-        if (!service_is_kmer_request(rq[i])) continue;
+        if (!service_takes_kmer(rq[i], cfg)) continue;
         (*handled)[i] = 1;
         for (int strand = 0; strand < 2; ++strand) {
             kmer_job j;
@@ -729,21 +823,49 @@ int service_kmer_batch(rsbwt_set_t *set, const std::vector<service_request> &rq,
     const int rc = kmer_engine_hooks.batch(set, jobs, cfg.min_read_length, cfg.max_read_length, stride, &res, &failed, &wk);
     if (rc != RSBWT_OK) return rc;
     const size_t rows = per_partition ? S : 1;
+    // the lists of the All / Samples requests (KmerTask::run, service.cpp:917-975: each read with its samples), looked up
+    // in one call; list (job, row) as the loop below walks them
+    std::vector<std::vector<const std::string *>> lists(jobs.size() * rows);
+    std::vector<std::vector<uint32_t>> lshard(lists.size());
+    std::vector<char> is_all(lists.size(), 0);
+    {
+        size_t ji = 0;
+        for (size_t i = 0; i < n; ++i) {
+            if (!(*handled)[i]) continue;
+            for (int strand = 0; strand < 2; ++strand)
+                for (size_t r = 0; r < rows; ++r) {
+                    const size_t li = (ji + strand) * rows + r;
+                    // per partition: that shard's set; summed: counts added up, lists joined in shard order
+                    for (size_t p = per_partition ? r : 0; p < (per_partition ? r + 1 : S); ++p)
+                        for (const std::string &x : res[ji + strand][p]) {
+                            lists[li].push_back(&x);
+                            lshard[li].push_back((uint32_t)p);
+                        }
+                    is_all[li] = service_is_all_return(rq[i]) ? 1 : 0;
+                }
+            ji += 2;
+        }
+    }
+    all_values vals;
+    {
+        const int rv = vals.lookup(set, lists, lshard, is_all);
+        if (rv != RSBWT_OK) return rv;
+    }
+    const sample_codec codec = codec_of(cfg);
     size_t ji = 0;
-    std::vector<const std::string *> l;
     for (size_t i = 0; i < n; ++i) {
         replies->first[i] = replies->off.size() - 1;
         if (!(*handled)[i]) continue;
         for (size_t r = 0; r < rows; ++r)
             for (int strand = 0; strand < 2; ++strand) {
-                // per partition: that shard's set; summed: counts added up, lists joined in shard order
-                l.clear();
-                uint64_t count = 0;
-                for (size_t p = per_partition ? r : 0; p < (per_partition ? r + 1 : S); ++p) {
-                    for (const std::string &x : res[ji + strand][p]) l.push_back(&x);
-                    count += res[ji + strand][p].size();
+                const size_t li = (ji + strand) * rows + r;
+                if (is_all[li]) {
+                    const size_t at = replies->bytes.size(), len = vals.encode(nullptr, 0, li, lists[li], rq[i].t, rq[i].rt, rq[i].q, strand == 1, codec);
+                    replies->bytes.resize(at + len);
+                    vals.encode(replies->bytes.data() + at, len, li, lists[li], rq[i].t, rq[i].rt, rq[i].q, strand == 1, codec);
+                } else {
+                    append_kmer_reply(&replies->bytes, rq[i].t, rq[i].rt, rq[i].q, strand == 1, lists[li], lists[li].size());
                 }
-                append_kmer_reply(&replies->bytes, rq[i].t, rq[i].rt, rq[i].q, strand == 1, l, count);
                 replies->off.push_back(replies->bytes.size());
             }
         ji += 2;
@@ -828,6 +950,54 @@ size_t rsbwt_proto_encode_kmer_reply(uint8_t *out, size_t cap, int return_type, 
     } catch (const std::bad_alloc &) {
         return 0;
     }
+}
+
+size_t rsbwt_proto_encode_all_reply(uint8_t *out, size_t cap, int request_type, int return_type, const char *q, size_t qlen, int revcomp,
+                                    const char *const *reads, const size_t *read_len, const uint8_t *const *values, const size_t *value_len,
+                                    size_t nreads, const char *hash, size_t hash_len, uint32_t size_of_sample, int has_other_meta_data) {
+    if ((!q && qlen) || ((!reads || !read_len) && nreads) || (values && !value_len) || (!hash && hash_len) || request_type < 1 ||
+        request_type > 4 || return_type < 1 || return_type > 4 || (size_of_sample == 0 && !has_other_meta_data))
+        return 0;
+    try {
+        std::map<std::string, std::string> h;
+        rsb::meta_parse_hash(hash, hash_len, &h);
+        rsb::sample_codec c;
+        c.hash = &h;
+        c.size_of_sample = size_of_sample;
+        c.has_other = has_other_meta_data != 0;
+        return rsb::meta_encode_all_reply(out, cap, request_type, return_type, q, qlen, revcomp != 0, reads, read_len, values, value_len, nreads, c);
+    } catch (const std::bad_alloc &) {
+        return 0;
+    }
+}
+
+int rsbwt_meta_parse_file(const char *path, char *text, size_t text_cap, uint64_t *off, uint8_t *values, size_t values_cap, uint64_t *voff,
+                          size_t cap_pairs, size_t *sizes3) {
+    return rsb::guarded("rsbwt_meta_parse_file", [&]() -> int {
+        if (!path || !sizes3) return rsb::fail(RSBWT_EINVAL, "null argument");
+        FILE *f = fopen(path, "rb");
+        if (!f) return rsb::fail(RSBWT_EIO, "cannot open %s", path);
+        std::string data;
+        char buf[1 << 16];
+        size_t got;
+        while ((got = fread(buf, 1, sizeof buf, f)) > 0) data.append(buf, got);
+        const bool bad = ferror(f) != 0;
+        fclose(f);
+        if (bad) return rsb::fail(RSBWT_EIO, "cannot read %s", path);
+        rsb::meta_pairs pairs;
+        rsb::meta_parse_pairs(data.data(), data.size(), &pairs);
+        const size_t n = pairs.size();
+        sizes3[0] = n;
+        sizes3[1] = pairs.text.size();
+        sizes3[2] = pairs.values.size();
+        if (!off || !voff || n > cap_pairs || (!text && sizes3[1]) || sizes3[1] > text_cap || (!values && sizes3[2]) || sizes3[2] > values_cap)
+            return rsb::fail(RSBWT_ERANGE, "%zu pairs, %zu read bytes, %zu value bytes", n, sizes3[1], sizes3[2]);
+        if (sizes3[1]) memcpy(text, pairs.text.data(), sizes3[1]);
+        if (sizes3[2]) memcpy(values, pairs.values.data(), sizes3[2]);
+        memcpy(off, pairs.off.data(), (n + 1) * sizeof(uint64_t));
+        memcpy(voff, pairs.voff.data(), (n + 1) * sizeof(uint64_t));
+        return RSBWT_OK;
+    });
 }
 
 size_t rsbwt_proto_encode_empty_reply(uint8_t *out, size_t cap, int t, int rt, const char *q, size_t qlen, int revcomp) {

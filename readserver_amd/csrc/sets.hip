@@ -29,6 +29,7 @@
 #include "../../include/rsbwt.h"
 #include "capi_guard.h"
 #include "capi_internal.h"
+#include "meta_file.h"
 #include "service.h"
 
 using namespace rsb;
@@ -104,6 +105,7 @@ struct dev_group : search_meter {
     shard_view *d_xviews = nullptr;  // the same WITH the shards' select samples, for the fused extraction: a second array, made once
     std::atomic<bool> xviews_ready{false};
     uint64_t *d_ktab = nullptr;      // the interleaved k-mer tables of the shards this set gave one
+    meta_view *d_meta = nullptr;     // [idx.size()] in HBM: the shards' sample tables (rsbwt_set_meta_*), made with the first build
     ctx_pool pool;
     ncclComm_t comm = nullptr;
     // the gather without RCCL (peer copies issued on the root's stream): "the block is ready" on this group's stream,
@@ -142,6 +144,14 @@ struct rsbwt_set {
     // Collectives on the set's communicators are enqueued by one thread at a time: two callers
     // interleaving their group calls could reach the communicators in different orders.
     std::mutex comm_mu;
+    // the per-read sample table (rsbwt_set_meta_*): shard i's off u64[num_strings + 1] / value bytes, on shard i's device;
+    // empty = no table.  Written by build / load / clear only, which must not run beside a lookup.
+    struct meta_shard {
+        uint64_t *d_off = nullptr;
+        uint8_t *d_bytes = nullptr;
+    };
+    std::vector<meta_shard> meta;
+    uint64_t meta_bytes = 0;
 };
 
 namespace {
@@ -321,12 +331,16 @@ void scatter_read(const char *ho, const uint32_t *hl, const uint32_t *hp, size_t
 
 }  // namespace
 
+static void meta_free(rsbwt_set_t *s);  // the sample tables (below, rsbwt_set_meta_*)
+
 extern "C" {
 
 void rsbwt_set_close(rsbwt_set_t *s) {
     if (!s) return;
+    meta_free(s);
     for (dev_group *g : s->groups) {
         (void)hipSetDevice(g->device);
+        if (g->d_meta) (void)hipFree(g->d_meta);
         g->pool.destroy();
         if (g->comm && rccl().ok) (void)rccl().CommDestroy(g->comm);
         if (g->d_ktab) {  // shards that outlive the set lose the table that lived in it
@@ -599,12 +613,24 @@ int rsbwt_set_count_var(rsbwt_set_t *s, const char *text, const uint64_t *off, s
 // Whole-read matches of queries of lengths of their own (read_lookup.hip): copies / ending [num_shards][Q] in the set's
 // shard order, per device group one launch sequence over its shards, sliced as rsbwt_set_count_var is (for_each_var_slice).
 static int rsbwt_set_read_copies_var_body(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *copies,
-                                          uint64_t *ending) {
+                                          uint64_t *ending, uint64_t *ordinal = nullptr, std::atomic<uint64_t> *lf_steps = nullptr) {
     if (!s) return fail(RSBWT_EINVAL, "null set");
     if (Q == 0) return RSBWT_OK;
     if (!off || !copies || (!text && off[Q] != off[0])) return fail(RSBWT_EINVAL, "null argument");
     for (rsbwt_t *h : s->shards)
         if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
+    if (ordinal) {  // (group_scatter carries two arrays: the ordinals ride in the second one's place)
+        if (ending) return fail(RSBWT_EINVAL, "ordinal and ending in one call");
+        return for_each_group(s, [&](size_t gi) -> int {
+            return group_scatter(s, gi, Q, copies, ordinal, [&](dev_group *g, uint64_t *cp, uint64_t *od) -> int {
+                uint64_t steps = 0;
+                const int rc = read_copies_host_views_var(*g, g->pool, g->d_views, (uint32_t)g->idx.size(), g->num_cus, text, off, Q, cp, nullptr, od,
+                                                          lf_steps ? &steps : nullptr);
+                if (lf_steps) *lf_steps += steps;
+                return rc;
+            });
+        });
+    }
     return for_each_group(s, [&](size_t gi) -> int {
         return group_scatter(s, gi, Q, copies, ending, [&](dev_group *g, uint64_t *cp, uint64_t *en) -> int {
             return read_copies_host_views_var(*g, g->pool, g->d_views, (uint32_t)g->idx.size(), g->num_cus, text, off, Q, cp, en);
@@ -2461,6 +2487,471 @@ int rsbwt_set_extract_dev(rsbwt_set_t *s, const void *d_rows, size_t n, void *d_
                                              (hipStream_t)stream, work);
     if (e != hipSuccess) return fail_hip(e, "extract kernel launch");
     return RSBWT_OK;
+}
+
+}  // extern "C"
+
+// ---- the per-read sample table (read_meta.hip): build / load / clear, and the lookups by ordinal and by string ----
+namespace {
+
+// the calling thread's last lookup: items, items with a value, value bytes copied, LF steps of the string searches
+thread_local uint64_t meta_last_work[4] = {0, 0, 0, 0};
+
+int meta_required(const rsbwt_set_t *s) {
+    return s->meta.empty() ? fail(RSBWT_EINVAL, "the set has no sample table (rsbwt_set_meta_build / rsbwt_set_meta_load)") : RSBWT_OK;
+}
+
+// what a build allocates on the way and lets go of when it leaves, however it leaves
+struct dev_tmp {
+    std::vector<void *> p;
+    ~dev_tmp() {
+        for (void *x : p) (void)hipFree(x);
+    }
+    hipError_t get(size_t bytes, void **out) {
+        *out = nullptr;
+        const hipError_t e = hipMalloc(out, bytes ? bytes : 1);
+        if (e == hipSuccess) p.push_back(*out);
+        return e;
+    }
+};
+
+// One shard's table from the pairs' (ordinal, copies) in that shard (ord / cp: n entries), on the current device.  Three
+// passes over the pairs in chunks: winners (atomicMax of index + 1 per ordinal), the winners' lengths -> scan -> off[],
+// the winners' bytes from each uploaded chunk of values into the table (read_meta.hip's copy kernel).
+int meta_build_shard(hipStream_t st, uint64_t ns, const uint64_t *ord, const uint64_t *cp, const uint8_t *values, const uint64_t *voff, size_t n,
+                     rsbwt_set::meta_shard *out, uint64_t *bytes, uint64_t *given) {
+    const size_t CH = (size_t)1 << 20;           // pairs per chunk
+    const uint64_t VB = (uint64_t)64 << 20;      // value bytes per chunk (one value may be longer: a chunk of its own)
+    dev_tmp tmp;
+    void *d_win, *d_len, *d_src, *d_given, *d_a, *d_b, *d_voff, *d_scan;
+    const size_t m_max = std::min(n, CH), scan_bytes = meta_scan_bytes(ns + 1);
+    HIP_OK(tmp.get((ns + 1) * 8, &d_win));
+    HIP_OK(tmp.get((ns + 1) * 8, &d_len));
+    HIP_OK(tmp.get((ns + 1) * 8, &d_src));
+    HIP_OK(tmp.get(8, &d_given));
+    HIP_OK(tmp.get(m_max * 8, &d_a));
+    HIP_OK(tmp.get(m_max * 8, &d_b));
+    HIP_OK(tmp.get((m_max + 1) * 8, &d_voff));
+    HIP_OK(tmp.get(scan_bytes, &d_scan));
+    HIP_OK(hipMemsetAsync(d_win, 0, (ns + 1) * 8, st));
+    HIP_OK(hipMemsetAsync(d_len, 0, (ns + 1) * 8, st));
+    HIP_OK(hipMemsetAsync(d_given, 0, 8, st));
+    hipError_t e;
+    for (size_t c0 = 0; c0 < n; c0 += CH) {
+        const size_t m = std::min(CH, n - c0);
+        HIP_OK(hipMemcpyAsync(d_a, ord + c0, m * 8, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_b, cp + c0, m * 8, hipMemcpyHostToDevice, st));
+        if ((e = launch_meta_winners(d_a, d_b, m, c0, d_win, ns, st)) != hipSuccess) return fail_hip(e, "winner kernel launch");
+    }
+    for (size_t c0 = 0; c0 < n; c0 += CH) {
+        const size_t m = std::min(CH, n - c0);
+        HIP_OK(hipMemcpyAsync(d_voff, voff + c0, (m + 1) * 8, hipMemcpyHostToDevice, st));
+        if ((e = launch_meta_winner_values(d_win, ns, d_voff, c0, c0 + m, d_len, nullptr, d_given, st)) != hipSuccess)
+            return fail_hip(e, "winner-length kernel launch");
+    }
+    HIP_OK(hipMalloc((void **)&out->d_off, (ns + 1) * 8));
+    if ((e = launch_meta_scan(d_scan, scan_bytes, d_len, out->d_off, ns + 1, st)) != hipSuccess) return fail_hip(e, "offset scan");
+    uint64_t total = 0;
+    HIP_OK(hipMemcpyAsync(&total, out->d_off + ns, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(given, d_given, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipMalloc((void **)&out->d_bytes, total ? total : 1));
+    *bytes = total;
+    void *d_val = nullptr;
+    uint64_t val_room = 0;
+    for (size_t c0 = 0; c0 < n && total;) {
+        size_t c1 = c0 + 1;
+        while (c1 < n && c1 - c0 < CH && voff[c1 + 1] - voff[c0] <= VB) ++c1;
+        const uint64_t vb = voff[c1] - voff[c0];
+        if (vb) {
+            if (vb > val_room) {
+                HIP_OK(hipStreamSynchronize(st));
+                HIP_OK(tmp.get(vb, &d_val));  // (the smaller one goes with the rest)
+                val_room = vb;
+            }
+            HIP_OK(hipMemcpyAsync(d_val, values + voff[c0], vb, hipMemcpyHostToDevice, st));
+            HIP_OK(hipMemcpyAsync(d_voff, voff + c0, (c1 - c0 + 1) * 8, hipMemcpyHostToDevice, st));
+            if ((e = launch_meta_winner_values(d_win, ns, d_voff, c0, c1, nullptr, d_src, nullptr, st)) != hipSuccess)
+                return fail_hip(e, "winner-offset kernel launch");
+            if ((e = launch_meta_copy(nullptr, 1, nullptr, 0, d_val, d_src, out->d_off, ns, out->d_bytes, total, st)) != hipSuccess)
+                return fail_hip(e, "value copy kernel launch");
+        }
+        c0 = c1;
+    }
+    HIP_OK(hipStreamSynchronize(st));
+    return RSBWT_OK;
+}
+
+// the tables' views, as the lookups of group g read them
+int meta_publish(rsbwt_set_t *s) {
+    for (dev_group *g : s->groups) {
+        int rc = use_device(g->device);
+        if (rc) return rc;
+        std::vector<meta_view> v;
+        for (size_t i : g->idx) {
+            meta_view mv = {nullptr, nullptr, 0};
+            if (!s->meta.empty()) mv = {s->meta[i].d_off, s->meta[i].d_bytes, s->shards[i]->view.C[1]};
+            v.push_back(mv);
+        }
+        if (!g->d_meta) HIP_OK(hipMalloc((void **)&g->d_meta, v.size() * sizeof(meta_view)));
+        HIP_OK(hipMemcpy(g->d_meta, v.data(), v.size() * sizeof(meta_view), hipMemcpyHostToDevice));
+    }
+    return RSBWT_OK;
+}
+
+void meta_free_tables(rsbwt_set_t *s, std::vector<rsbwt_set::meta_shard> &tabs) {
+    for (size_t i = 0; i < tabs.size(); ++i) {
+        if (!tabs[i].d_off && !tabs[i].d_bytes) continue;
+        (void)hipSetDevice(s->shards[i]->device);
+        if (tabs[i].d_off) (void)hipFree(tabs[i].d_off);
+        if (tabs[i].d_bytes) (void)hipFree(tabs[i].d_bytes);
+    }
+    tabs.clear();
+}
+
+int set_meta_build_body(rsbwt_set_t *s, const char *text, const uint64_t *off, const uint8_t *values, const uint64_t *voff, size_t n,
+                        uint64_t *stats4) {
+    if (!s) return fail(RSBWT_EINVAL, "null set");
+    if (n && (!off || !voff || (!text && off[n] != off[0]) || (!values && voff[n] != voff[0]))) return fail(RSBWT_EINVAL, "null argument");
+    for (size_t i = 0; i < n; ++i)
+        if (voff[i + 1] < voff[i]) return fail(RSBWT_EINVAL, "pair %zu: its value's end lies before its start", i);
+    for (rsbwt_t *h : s->shards)
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
+    const size_t S = s->shards.size();
+    std::vector<uint64_t> ord(S * n), cp(S * n);
+    int rc = n ? rsbwt_set_read_copies_var_body(s, text, off, n, cp.data(), nullptr, ord.data()) : RSBWT_OK;
+    if (rc) return rc;
+    std::vector<rsbwt_set::meta_shard> tabs(S);
+    std::vector<uint64_t> bytes(S, 0), given(S, 0);
+    rc = for_each_group(s, [&](size_t gi) -> int {
+        dev_group *g = s->groups[gi];
+        group_call gc(g);
+        if (gc.rc) return gc.rc;
+        for (size_t i : g->idx) {
+            const int rb = meta_build_shard(gc.st, s->shards[i]->view.C[1], ord.data() + i * n, cp.data() + i * n, values, voff, n, &tabs[i],
+                                            &bytes[i], &given[i]);
+            if (rb) return rb;
+        }
+        return RSBWT_OK;
+    });
+    if (rc) {
+        meta_free_tables(s, tabs);
+        return rc;
+    }
+    meta_free_tables(s, s->meta);
+    s->meta = std::move(tabs);
+    s->meta_bytes = 0;
+    uint64_t st[4] = {0, 0, 0, 0};
+    for (size_t i = 0; i < S; ++i) {
+        s->meta_bytes += (s->shards[i]->view.C[1] + 1) * 8 + bytes[i];
+        st[2] += given[i];
+        st[3] += bytes[i];
+    }
+    for (size_t q = 0; q < n; ++q) {
+        bool any = false;
+        for (size_t i = 0; i < S && !any; ++i) any = cp[i * n + q] != 0;
+        st[any ? 0 : 1] += 1;
+    }
+    if (stats4) memcpy(stats4, st, sizeof st);
+    return meta_publish(s);
+}
+
+// One device group's items (shards as the group numbers them; sh nullptr: its shard 0): first[m + 1] always; the bytes
+// into `bytes` when they fit cap, or into *own (resized) when that is given.
+int meta_group_lookup(dev_group *g, const uint32_t *sh, const uint64_t *od, size_t m, uint64_t *first, uint8_t *bytes, size_t cap,
+                      std::vector<uint8_t> *own) {
+    group_call gc(g, true);
+    if (gc.rc) return gc.rc;
+    hipStream_t st = gc.st;
+    const size_t a4 = al256(m * 4), a8 = al256((m + 1) * 8), a_tmp = meta_scan_bytes(m + 1);
+    hipError_t e = g->scratch.take(a4 + 4 * a8 + a_tmp, st, &gc.la);
+    if (e != hipSuccess) return fail_hip(e, "scratch for a sample lookup");
+    uint8_t *d_sh = (uint8_t *)gc.la.p, *d_od = d_sh + a4, *d_len = d_od + a8, *d_src = d_len + a8, *d_first = d_src + a8, *d_tmp = d_first + a8;
+    if (sh) HIP_OK(hipMemcpyAsync(d_sh, sh, m * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_od, od, m * 8, hipMemcpyHostToDevice, st));
+    const uint32_t S = (uint32_t)g->idx.size();
+    if ((e = launch_meta_sizes(g->d_meta, S, sh ? d_sh : nullptr, d_od, nullptr, 0, m, d_len, d_src, st)) != hipSuccess)
+        return fail_hip(e, "sample sizes kernel launch");
+    if ((e = launch_meta_scan(d_tmp, a_tmp, d_len, d_first, m + 1, st)) != hipSuccess) return fail_hip(e, "sample offsets scan");
+    HIP_OK(hipMemcpyAsync(first, d_first, (m + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    const uint64_t total = first[m];
+    if (own) own->resize(total);
+    else if (total > cap) return RSBWT_OK;  // (the caller reports the size)
+    if (total == 0) return RSBWT_OK;
+    if ((e = g->scratch.take(total, st, &gc.lb)) != hipSuccess)
+        return fail(RSBWT_ENOMEM, "%llu value bytes do not fit the device's free memory: %s", (unsigned long long)total, hipGetErrorString(e));
+    if ((e = launch_meta_copy(g->d_meta, S, sh ? d_sh : nullptr, 0, nullptr, d_src, d_first, m, gc.lb.p, total, st)) != hipSuccess)
+        return fail_hip(e, "sample copy kernel launch");
+    HIP_OK(hipMemcpyAsync(own ? own->data() : bytes, gc.lb.p, total, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return RSBWT_OK;
+}
+
+int set_meta_by_ordinal_body(rsbwt_set_t *s, const uint32_t *shard_of, const uint64_t *ordinal, size_t n, uint64_t *first, uint8_t *bytes,
+                             size_t cap, size_t *nbytes) {
+    const size_t S = s->shards.size();
+    for (size_t i = 0; i < n; ++i)
+        if (shard_of[i] >= S) return fail(RSBWT_EINVAL, "item %zu names shard %u of %zu", i, shard_of[i], S);
+    if (s->groups.size() == 1) {
+        const int rc = meta_group_lookup(s->groups[0], shard_of, ordinal, n, first, bytes, bytes ? cap : 0, nullptr);
+        if (rc) return rc;
+    } else {
+        // several device groups: each gathers its share where its tables are; the host lays the values out in the order asked
+        const size_t G = s->groups.size();
+        std::vector<group_share> share(G);
+        std::vector<std::vector<uint64_t>> gfirst(G);
+        std::vector<std::vector<uint8_t>> gbytes(G);
+        const int rc = for_each_group(s, [&](size_t gi) -> int {
+            share[gi] = share_of_group(s, s->groups[gi], shard_of, ordinal, n);
+            const size_t m = share[gi].pos.size();
+            gfirst[gi].assign(m + 1, 0);
+            if (m == 0) return RSBWT_OK;
+            return meta_group_lookup(s->groups[gi], share[gi].shard.data(), share[gi].rows.data(), m, gfirst[gi].data(), nullptr, 0, &gbytes[gi]);
+        });
+        if (rc) return rc;
+        for (size_t gi = 0; gi < G; ++gi)
+            for (size_t t = 0; t < share[gi].pos.size(); ++t) first[share[gi].pos[t] + 1] = gfirst[gi][t + 1] - gfirst[gi][t];
+        first[0] = 0;
+        for (size_t i = 0; i < n; ++i) first[i + 1] += first[i];
+        if (bytes && first[n] <= cap)
+            for (size_t gi = 0; gi < G; ++gi)
+                for (size_t t = 0; t < share[gi].pos.size(); ++t) {
+                    const uint64_t l = gfirst[gi][t + 1] - gfirst[gi][t];
+                    if (l) memcpy(bytes + first[share[gi].pos[t]], gbytes[gi].data() + gfirst[gi][t], l);
+                }
+    }
+    *nbytes = (size_t)first[n];
+    meta_last_work[0] = n;
+    for (size_t i = 0; i < n; ++i) meta_last_work[1] += first[i + 1] != first[i];
+    if (first[n] > (bytes ? cap : 0)) return fail(RSBWT_ERANGE, "%llu value bytes, room for %zu", (unsigned long long)first[n], bytes ? cap : 0);
+    meta_last_work[2] = first[n];
+    return RSBWT_OK;
+}
+
+// One device group holding every shard: per slice of the batch the whole-read search, the sizes, the scan and the copy run
+// in HBM; the slice's first[] and copies cross to the host before its bytes (they size them), the bytes after.
+int meta_read_device(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *first, uint8_t *bytes, size_t cap,
+                     uint64_t *copies, uint64_t *lf_steps) {
+    dev_group *g = s->groups[0];
+    group_call gc(g, true);
+    if (gc.rc) return gc.rc;
+    hipStream_t st = gc.st;
+    const uint32_t S = (uint32_t)g->idx.size();
+    auto a_scr = [&](size_t mq) { return al256(read_copies_scratch_bytes(S, mq)); };
+    auto a_res = [&](size_t mq) { return al256((size_t)S * mq * 8 + 8); };
+    uint64_t base = 0;
+    std::vector<uint64_t> hf;
+    const int rc = for_each_var_slice(
+        *gc.c, st, text, off, Q, [&](size_t mq) { return a_scr(mq) + 5 * a_res(mq) + meta_scan_bytes(S * mq + 1); },
+        [&](size_t q0, size_t mq) -> int {
+            for (size_t i = 0; i < mq * S; ++i) first[q0 * S + i] = base;
+            if (copies)
+                for (uint32_t p = 0; p < S; ++p) memset(copies + p * Q + q0, 0, mq * 8);
+            return RSBWT_OK;
+        },
+        [&](const var_slice &sl) -> int {
+            const size_t q0 = sl.q0, mq = sl.mq, items = mq * S, a_tmp = meta_scan_bytes(items + 1);
+            uint8_t *d_scr = sl.d_extra, *d_cp = d_scr + a_scr(mq), *d_od = d_cp + a_res(mq), *d_len = d_od + a_res(mq), *d_src = d_len + a_res(mq),
+                    *d_first = d_src + a_res(mq), *d_tmp = d_first + a_res(mq);
+            int r = read_copies_launch(*g, g->d_views, S, g->num_cus, sl.d_pk, sl.d_ok, sl.d_len, mq, sl.k, d_scr, d_cp, nullptr, st, d_od);
+            if (r) return r;
+            unsigned long long w0 = 0;
+            if (g->counting) HIP_OK(hipMemcpyAsync(&w0, g->d_work, sizeof w0, hipMemcpyDeviceToHost, st));
+            hipError_t e = launch_meta_sizes(g->d_meta, S, nullptr, d_od, d_cp, mq, items, d_len, d_src, st);
+            if (e != hipSuccess) return fail_hip(e, "sample sizes kernel launch");
+            if ((e = launch_meta_scan(d_tmp, a_tmp, d_len, d_first, items + 1, st)) != hipSuccess) return fail_hip(e, "sample offsets scan");
+            hf.resize(items + 1);
+            HIP_OK(hipMemcpyAsync(hf.data(), d_first, (items + 1) * 8, hipMemcpyDeviceToHost, st));
+            if (copies)
+                for (uint32_t p = 0; p < S; ++p) HIP_OK(hipMemcpyAsync(copies + p * Q + q0, d_cp + (size_t)p * mq * 8, mq * 8, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+            *lf_steps += w0;
+            const uint64_t total = hf[items];
+            for (size_t i = 0; i < items; ++i) first[q0 * S + i] = base + hf[i];
+            if (total && bytes && base + total <= cap) {
+                scratch_cache::lease mem;
+                if ((e = g->scratch.take(total, st, &mem)) != hipSuccess)
+                    return fail(RSBWT_ENOMEM, "%llu value bytes do not fit the device's free memory: %s", (unsigned long long)total, hipGetErrorString(e));
+                e = launch_meta_copy(g->d_meta, S, nullptr, mq, nullptr, d_src, d_first, items, mem.p, total, st);
+                if (e == hipSuccess) e = hipMemcpyAsync(bytes + base, mem.p, total, hipMemcpyDeviceToHost, st);
+                if (e == hipSuccess) e = hipStreamSynchronize(st);
+                g->scratch.give(mem, st);
+                if (e != hipSuccess) return fail_hip(e, "sample copy");
+            }
+            base += total;
+            return RSBWT_OK;
+        });
+    if (rc) return rc;
+    first[Q * S] = base;
+    return RSBWT_OK;
+}
+
+int set_read_meta_var_body(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *first, uint8_t *bytes, size_t cap,
+                           size_t *nbytes, uint64_t *copies) {
+    const size_t S = s->shards.size();
+    for (rsbwt_t *h : s->shards)
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
+    uint64_t steps = 0;
+    if (s->groups.size() == 1 && S <= 1024) {
+        const int rc = meta_read_device(s, text, off, Q, first, bytes, bytes ? cap : 0, copies, &steps);
+        if (rc) return rc;
+    } else {
+        // several device groups: the ordinals come to the host and go the way rsbwt_set_meta_by_ordinal's go
+        std::vector<uint64_t> od(S * Q), cp_own(copies ? 0 : S * Q);
+        uint64_t *cp = copies ? copies : cp_own.data();
+        std::atomic<uint64_t> st{0};
+        int rc = rsbwt_set_read_copies_var_body(s, text, off, Q, cp, nullptr, od.data(), &st);
+        if (rc) return rc;
+        steps = st.load();
+        std::vector<uint32_t> sh(Q * S);
+        std::vector<uint64_t> it(Q * S);
+        for (size_t q = 0; q < Q; ++q)
+            for (size_t p = 0; p < S; ++p) {
+                sh[q * S + p] = (uint32_t)p;
+                it[q * S + p] = cp[p * Q + q] ? od[p * Q + q] : ~0ull;
+            }
+        size_t nb = 0;
+        rc = set_meta_by_ordinal_body(s, sh.data(), it.data(), Q * S, first, bytes, cap, &nb);
+        if (rc && rc != RSBWT_ERANGE) return rc;
+    }
+    const size_t n = Q * S;
+    *nbytes = (size_t)first[n];
+    meta_last_work[0] = n;
+    meta_last_work[1] = 0;
+    for (size_t i = 0; i < n; ++i) meta_last_work[1] += first[i + 1] != first[i];
+    meta_last_work[2] = 0;
+    meta_last_work[3] = steps;
+    if (first[n] > (bytes ? cap : 0)) return fail(RSBWT_ERANGE, "%llu value bytes, room for %zu", (unsigned long long)first[n], bytes ? cap : 0);
+    meta_last_work[2] = first[n];
+    return RSBWT_OK;
+}
+
+int read_file(const char *path, std::string *out) {
+    FILE *f = fopen(path, "rb");
+    if (!f) return fail(RSBWT_EIO, "cannot open %s", path);
+    char buf[1 << 16];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof buf, f)) > 0) out->append(buf, got);
+    const bool bad = ferror(f) != 0;
+    fclose(f);
+    return bad ? fail(RSBWT_EIO, "cannot read %s", path) : RSBWT_OK;
+}
+
+}  // namespace
+
+static void meta_free(rsbwt_set_t *s) {
+    meta_free_tables(s, s->meta);
+    s->meta_bytes = 0;
+}
+
+namespace {
+// the service code's way in (service.h: service_slice.cpp is also linked into host harnesses without the engine)
+struct register_meta_hooks {
+    register_meta_hooks() {
+        rsb::meta_engine_hooks.read_meta_var = rsbwt_set_read_meta_var;
+        rsb::meta_engine_hooks.meta_bytes = rsbwt_set_meta_bytes;
+    }
+} register_meta_hooks_now;
+}  // namespace
+
+extern "C" {
+
+int rsbwt_set_meta_build(rsbwt_set_t *s, const char *text, const uint64_t *off, const uint8_t *values, const uint64_t *voff, size_t n,
+                         uint64_t *stats4) {
+    return guarded("rsbwt_set_meta_build", [&]() -> int { return set_meta_build_body(s, text, off, values, voff, n, stats4); });
+}
+
+// The whole file is parsed into pairs on the host (two copies of it at the peak) and built as rsbwt_set_meta_build builds:
+// the higher index wins over the whole file because the pairs keep the file's order.
+int rsbwt_set_meta_load(rsbwt_set_t *s, const char *path, uint64_t *stats4) {
+    return guarded("rsbwt_set_meta_load", [&]() -> int {
+        if (!s || !path) return fail(RSBWT_EINVAL, "null argument");
+        meta_pairs pairs;
+        {
+            std::string data;
+            const int rc = read_file(path, &data);
+            if (rc) return rc;
+            meta_parse_pairs(data.data(), data.size(), &pairs);
+        }
+        return set_meta_build_body(s, pairs.text.data(), pairs.off.data(), (const uint8_t *)pairs.values.data(), pairs.voff.data(), pairs.size(),
+                                   stats4);
+    });
+}
+
+int rsbwt_set_meta_clear(rsbwt_set_t *s) {
+    return guarded("rsbwt_set_meta_clear", [&]() -> int {
+        if (!s) return fail(RSBWT_EINVAL, "null set");
+        meta_free(s);
+        return meta_publish(s);
+    });
+}
+
+uint64_t rsbwt_set_meta_bytes(const rsbwt_set_t *s) { return s ? s->meta_bytes : 0; }
+
+int rsbwt_set_read_ordinals_var(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *ordinal, uint64_t *copies) {
+    return guarded("rsbwt_set_read_ordinals_var", [&]() -> int {
+        if (Q && (!ordinal || !copies)) return fail(RSBWT_EINVAL, "null argument");
+        return rsbwt_set_read_copies_var_body(s, text, off, Q, copies, nullptr, ordinal);
+    });
+}
+
+int rsbwt_set_meta_by_ordinal(rsbwt_set_t *s, const uint32_t *shard_of, const uint64_t *ordinal, size_t n, uint64_t *first, uint8_t *bytes,
+                              size_t cap, size_t *nbytes) {
+    return guarded("rsbwt_set_meta_by_ordinal", [&]() -> int {
+        for (uint64_t &w : meta_last_work) w = 0;
+        if (!s || !first || !nbytes || (n && (!shard_of || !ordinal))) return fail(RSBWT_EINVAL, "null argument");
+        *nbytes = 0;
+        first[0] = 0;
+        const int rc = meta_required(s);
+        if (rc || n == 0) return rc;
+        return set_meta_by_ordinal_body(s, shard_of, ordinal, n, first, bytes, cap, nbytes);
+    });
+}
+
+int rsbwt_set_meta_by_ordinal_dev(rsbwt_set_t *s, const void *d_shard, const void *d_ordinal, size_t n, void *d_first, void *d_bytes, size_t cap,
+                                  void *stream) {
+    return guarded("rsbwt_set_meta_by_ordinal_dev", [&]() -> int {
+        dev_group *g = nullptr;
+        int rc = one_device_group(s, &g);
+        if (rc) return rc;
+        if ((rc = meta_required(s)) != RSBWT_OK) return rc;
+        if (!d_first || (n && (!d_shard || !d_ordinal))) return fail(RSBWT_EINVAL, "null argument");
+        hipStream_t st = (hipStream_t)stream;
+        if (n == 0) {
+            HIP_OK(hipMemsetAsync(d_first, 0, 8, st));
+            return RSBWT_OK;
+        }
+        const size_t a8 = al256((n + 1) * 8), a_tmp = meta_scan_bytes(n + 1);
+        scratch_cache::lease mem;
+        hipError_t e = g->scratch.take(2 * a8 + a_tmp, st, &mem);
+        if (e != hipSuccess) return fail_hip(e, "scratch for a sample lookup");
+        uint8_t *d_len = (uint8_t *)mem.p, *d_src = d_len + a8, *d_tmp = d_src + a8;
+        const uint32_t S = (uint32_t)g->idx.size();
+        e = launch_meta_sizes(g->d_meta, S, d_shard, d_ordinal, nullptr, 0, n, d_len, d_src, st);
+        if (e == hipSuccess) e = launch_meta_scan(d_tmp, a_tmp, d_len, d_first, n + 1, st);
+        if (e == hipSuccess && d_bytes && cap) e = launch_meta_copy(g->d_meta, S, d_shard, 0, nullptr, d_src, d_first, n, d_bytes, cap, st);
+        g->scratch.give(mem, st);
+        return e == hipSuccess ? RSBWT_OK : fail_hip(e, "sample lookup kernels");
+    });
+}
+
+int rsbwt_set_read_meta_var(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *first, uint8_t *bytes, size_t cap,
+                            size_t *nbytes, uint64_t *copies) {
+    return guarded("rsbwt_set_read_meta_var", [&]() -> int {
+        for (uint64_t &w : meta_last_work) w = 0;
+        if (!s || !first || !nbytes) return fail(RSBWT_EINVAL, "null argument");
+        *nbytes = 0;
+        first[0] = 0;
+        const int rc = meta_required(s);
+        if (rc || Q == 0) return rc;
+        if (!off || (!text && off[Q] != off[0])) return fail(RSBWT_EINVAL, "null argument");
+        return set_read_meta_var_body(s, text, off, Q, first, bytes, cap, nbytes, copies);
+    });
+}
+
+void rsbwt_set_meta_last_work(uint64_t *work4) {
+    if (work4) memcpy(work4, meta_last_work, sizeof meta_last_work);
 }
 
 int rsbwt_rccl_available(void) { return rccl().ok ? 1 : 0; }

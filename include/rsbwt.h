@@ -742,6 +742,67 @@ int rsbwt_set_meta_by_ordinal_dev(rsbwt_set_t *s, const void *d_shard, const voi
 int rsbwt_set_read_meta_var(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint64_t *first, uint8_t *bytes, size_t cap,
                             size_t *nbytes, uint64_t *copies);
 void rsbwt_set_meta_last_work(uint64_t *work4);
+/* Sample counts: in which samples does each query occur, and how often -- the sum over the reads that ExactMatch + All |
+ * Samples returns one by one, made on the device from the sample table above.  Queries arrive as in the _var calls.
+ *   codes     the caller's sample dictionary: C codes of size_of_sample bytes each, back to back, strictly ascending in
+ *             memcmp order.  RSBWT_EINVAL: codes not ascending or not distinct, size_of_sample outside 1..8, C == 0, a set
+ *             without a sample table ("no sample table"), a shard with 2^40 or more strings.
+ *   records   a value is cut into records of R = size_of_sample + (has_other_meta_data ? 2 : 0) bytes as
+ *             rsbwt_proto_encode_all_reply cuts it: code, then the c byte and the l byte.  The tail that is no whole
+ *             record is dropped.
+ *   rows      query q is searched in every shard exactly as rsbwt_set_locate_var_capped searches it (a symbol outside
+ *             ACGT or an empty string: the empty interval).  matches[q] = its rows summed over the shards.  If max_rows > 0
+ *             and matches[q] > max_rows the query contributes nothing: its rows of the matrices and carriers[q] stay zero,
+ *             matches[q] still reports the count.  Every row of a kept query is located (max_steps as in rsbwt_set_locate;
+ *             0 = 2^20); a row that is not located fails the call with RSBWT_EINVAL, as the SiteMatch and KmerMatch paths
+ *             fail an unfinished walk.
+ *   carriers  the sum runs over distinct read STRINGS, not rows: a read that holds the query at three offsets is one read,
+ *             and the 20 copies of a string share one RocksDB key and one value (find_reads returns an
+ *             unordered_set<string>).  For that the table holds one more array per shard, `heads`, one bit per ordinal,
+ *             built by rsbwt_set_meta_build / _load on the shard's device: bit `ordinal` is set for every pair whose string
+ *             matched that shard with copies > 0 (two pairs that name one string set one bit); rsbwt_set_meta_clear and a
+ *             second build free or replace it with the table.  rsbwt_set_meta_bytes keeps its meaning and its value;
+ *             rsbwt_set_meta_head_bytes alone reports the bitmaps: 4 * ceil(num_strings / 32) bytes per shard (0: no
+ *             table).  The carriers of (q, p) are the distinct ordinals o among the located rows of q in shard p with
+ *             heads_p[o] = 1.  Dropping a row on a copy that is no head loses nothing: all copies of a string hold the query
+ *             at the same offsets, so the head copy is among the rows whenever any copy is; and a query over the limit
+ *             contributes nothing at all, so the limit never splits a group of copies.  carriers[q] = the carriers summed
+ *             over the shards; a string present in two shards counts in each.
+ *   the sum   for every carrier and every whole record i of its value: col = the index of the record's code in codes, C if
+ *             it is absent; strings[q][col] += 1; copies[q][col] += c with c = (int)(signed char)value[i R + size_of_sample]
+ *             - 33 when has_other_meta_data (the encoder's rule), else 1.  The l byte is not used.  A value that lists one
+ *             code twice adds twice.  strings u32[Q][C + 1], copies i64[Q][C + 1], matches / carriers u64[Q]; any may be
+ *             NULL, not all of them.  Summed over the shards: a per-partition answer is the same call on a set of one.  All
+ *             arithmetic is in integers: the answers do not depend on the order the lanes run in and are bit-identical from
+ *             run to run.
+ * On a one-device set nothing but matches[], the row total and the answers leaves the device (csrc/sample_counts.hip); a
+ * set over several devices expands the rows on the host, every device tallies its shards' rows into matrices of its own
+ * and the host adds them: same answers either way.  A call of many queries runs in slices whose matrices stay under 1.5 GiB
+ * of HBM (and under 2^24 queries: the query number is part of a 64-bit key).  Re-entrant like the other lookups; not
+ * beside build / load / clear.
+ *   rsbwt_set_sample_counts_dev   a set on ONE device, nothing synchronised, everything enqueued on `stream`: d_text, d_off
+ *       (u64[Q + 1], d_off[0] = 0) as rsbwt_set_match_lengths_dev takes them, Q <= 2^24; max_len in 1..65,535 = the longest
+ *       query (a longer one gives the empty interval); d_keys u64[C] = the dictionary's keys as rsbwt_sample_keys spells
+ *       them, which the call cannot check; cap_rows = room for the kept rows of the batch.  d_strings / d_copies /
+ *       d_matches / d_carriers (any may be NULL, not all) are OVERWRITTEN: zeroed on the stream, then added to.  d_status8
+ *       u64[8] = {kept rows of the batch, rows on a head ordinal, carriers, records added, records with an unknown code, LF
+ *       steps of the walks, rows not located, 0}.  When status[0] > cap_rows nothing was tallied (ask again with that
+ *       much room); when status[6] > 0 the answers are not complete (the host form's RSBWT_EINVAL).
+ *   rsbwt_sample_keys             checks a dictionary as the host form does and writes its keys: key = the code's bytes as a
+ *       big-endian number (so ascending codes have ascending keys).  Host code, no device.
+ *   rsbwt_set_sample_last_work    the calling thread's last host-form call: {candidate rows, rows on a head ordinal,
+ *       distinct carriers, records added, records with an unknown code, LF steps of the rows' walks (counted only while
+ *       rsbwt_set_set_counting is on, else 0)}. */
+int rsbwt_set_sample_counts(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint8_t *codes, size_t C,
+                            uint32_t size_of_sample, int has_other_meta_data, uint64_t max_rows, uint32_t max_steps,
+                            uint32_t *strings, int64_t *copies, uint64_t *matches, uint64_t *carriers);
+int rsbwt_set_sample_counts_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, uint32_t max_len, const void *d_keys,
+                                size_t C, uint32_t size_of_sample, int has_other_meta_data, uint64_t max_rows, uint32_t max_steps,
+                                size_t cap_rows, void *d_strings, void *d_copies, void *d_matches, void *d_carriers, void *d_status8,
+                                void *stream);
+int rsbwt_sample_keys(const uint8_t *codes, size_t C, uint32_t size_of_sample, uint64_t *keys);
+void rsbwt_set_sample_last_work(uint64_t *work6);
+uint64_t rsbwt_set_meta_head_bytes(const rsbwt_set_t *s);
 /* Device-resident forms, for a set on ONE device (one process per GPU: bench.py --mode 1mm|extract).
  * d_hits [num_shards][cap_per_shard] x 32-byte records (rsbwt_hits_1mm_dev's), d_totals u64[num_shards];
  * d_rows [num_shards][n] (row numbers are per shard), d_out [num_shards][n][stride], d_len / d_prefix_len [num_shards][n]. */

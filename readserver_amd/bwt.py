@@ -843,6 +843,42 @@ class ShardSet:
         lib().rsbwt_set_meta_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
         return dict(zip(("items", "valued", "bytes", "lf_steps"), (int(x) for x in w)))
 
+    # -- sample counts (csrc/sample_counts.hip): rsbwt_set_sample_counts
+    def meta_head_bytes(self):
+        """bytes of the sample table's head bitmaps in HBM over all shards (0: no table); not part of meta_bytes()"""
+        return int(lib().rsbwt_set_meta_head_bytes(self._s))
+
+    def sample_counts(self, queries, codes, size_of_sample, has_other_meta_data=True, max_rows=0, max_steps=0):
+        """In which samples each query occurs and how often (rsbwt_set_sample_counts).  codes: the sample dictionary, byte
+        strings of size_of_sample bytes in any order.  Returns a dict of strings (Q, C + 1) uint32 -- the distinct reads
+        holding the query that list the sample --, copies (Q, C + 1) int64 -- the sum of their c fields --, both with the
+        columns in the caller's order and the records of unknown codes in the last column, matches (Q) -- the query's rows
+        over the shards -- and carriers (Q) -- the distinct reads with a value entry that hold it."""
+        cs = [bytes(c) for c in codes]
+        if any(len(c) != size_of_sample for c in cs):
+            raise ValueError("a code is not size_of_sample bytes long")
+        order = sorted(range(len(cs)), key=lambda i: cs[i])
+        flat = np.frombuffer(b"".join(cs[i] for i in order) + b"\0", np.uint8).copy()
+        text, off = self._var_text(queries)
+        Q, n = len(queries), len(cs)
+        strings = np.zeros((max(Q, 1), n + 1), np.uint32)
+        copies = np.zeros((max(Q, 1), n + 1), np.int64)
+        matches, carriers = np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64)
+        check(lib().rsbwt_set_sample_counts(self._s, _ptr(text), _ptr(off), Q, _ptr(flat), n, size_of_sample, 1 if has_other_meta_data else 0,
+                                            max_rows, max_steps, _ptr(strings), _ptr(copies), _ptr(matches), _ptr(carriers)))
+        back = np.empty(n + 1, np.int64)  # the caller's column -> the sorted column
+        back[np.array(order, np.int64)] = np.arange(n)
+        back[n] = n
+        return dict(strings=strings[:Q][:, back], copies=copies[:Q][:, back], matches=matches[:Q].copy(), carriers=carriers[:Q].copy())
+
+    @staticmethod
+    def sample_last_work():
+        """{rows, head_rows, carriers, records, unknown, lf_steps} of this thread's last sample_counts call (lf_steps: in
+        counting mode only)"""
+        w = np.zeros(6, np.uint64)
+        lib().rsbwt_set_sample_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return dict(zip(("rows", "head_rows", "carriers", "records", "unknown", "lf_steps"), (int(x) for x in w)))
+
     # -- BASELINE configs[3] / configs[4] over the set: per-shard results side by side, the way the front-end
     # concatenates its partitions' replies (src/service/server.cpp:199-261)
     def hits_1mm(self, kmers):

@@ -145,6 +145,7 @@ struct meta_view {
     const uint64_t *off;
     const uint8_t *bytes;
     uint64_t num_strings;
+    const uint32_t *heads;  // one bit per ordinal: the FIRST ordinal of a string some pair named (sample_counts.hip); bit o = heads[o / 32] >> (o % 32)
 };
 constexpr uint64_t META_NONE = ~0ull;  // src[] of an item that brings no bytes
 size_t meta_scan_bytes(size_t n);      // temporary bytes of launch_meta_scan over n values
@@ -170,6 +171,41 @@ hipError_t launch_meta_winners(const void *d_ordinal, const void *d_copies, size
 // by another chunk keeps its d_len and gets d_src META_NONE.  *d_given (optional) += ordinals with a winner in the chunk.
 hipError_t launch_meta_winner_values(const void *d_win, uint64_t num_strings, const void *d_voff, uint64_t c0, uint64_t c1, void *d_len,
                                      void *d_src, void *d_given, hipStream_t stream);
+// sample_counts.hip: rsbwt_set_sample_counts' reduction of located rows to per-query sample matrices.
+//   launch_meta_heads: the build's head bits: bit o of d_heads (u32 words, zeroed by the caller) is set for every pair with
+//     copies > 0 and ordinal o < num_strings (atomicOr: two pairs that name one string set one bit)
+//   launch_sample_regions: d_rows_of[p] (u64[S], zeroed by the caller) += the rows of d_shard u32[first[Q]] that name shard p,
+//     then d_region u64[S][2] = every shard's first slot and slot count - 1: a power of two strictly above its rows, at least
+//     twice its rows unless `tight` -- under 4 x rows + 1 slots, so 4 x cap + S slots hold all regions.  Nothing is counted
+//     when first[Q] > cap (the rows were not made).
+//   launch_sample_tally: one lane per row; see the struct.  keys_in_lds is set by the launcher.
+//   launch_sample_status: d_status8 = {first[Q], rows on a head ordinal, carriers, records, records with an unknown code,
+//     launch_locate's LF steps (d_locate_work2[1]; nullptr: 0), rows not located, 0}
+constexpr size_t TALLY_LDS_BYTES = 32u << 10;  // the dictionary's keys live in LDS while 8 C fits this
+enum { TALLY_WORK_HEADS = 0, TALLY_WORK_CARRIERS, TALLY_WORK_RECORDS, TALLY_WORK_UNKNOWN, TALLY_WORK_LOST, TALLY_WORK_COUNTERS };
+constexpr size_t TALLY_WORK_STRIDE = 32;  // u64 words between two counters: 256 bytes
+struct sample_tally {
+    const meta_view *meta;  // [S]
+    uint32_t S;
+    const uint64_t *first;  // [Q + 1]: the rows of query q are first[q] .. first[q + 1] (launch_interval_totals)
+    size_t Q;               // <= 2^24
+    const uint32_t *shard;  // [total] (launch_interval_fill)
+    const uint64_t *ordinal;  // [total] (launch_locate; UINT64_MAX: not located -> counted in TALLY_WORK_LOST)
+    uint64_t total;           // room for rows: the rows are the first first[Q] of them, none when first[Q] > total
+    unsigned long long *set;  // the regions' slots, all ones (empty) when the launch starts
+    const uint64_t *region;   // [S][2]: a shard's first slot and its slot count - 1 (a power of two above its rows, minus 1)
+    const uint64_t *keys;     // [C] ascending (sample_codes.h)
+    uint32_t C, size_of_sample, has_other, keys_in_lds;
+    uint32_t *strings;        // [Q][C + 1], zeroed by the caller; may be nullptr
+    long long *copies;        // [Q][C + 1], zeroed by the caller; may be nullptr
+    unsigned long long *carriers;  // [Q], zeroed by the caller; may be nullptr
+    unsigned long long *work;      // TALLY_WORK_COUNTERS counters TALLY_WORK_STRIDE words apart, zeroed by the caller
+};
+hipError_t launch_meta_heads(const void *d_ordinal, const void *d_copies, size_t n, void *d_heads, uint64_t num_strings, hipStream_t stream);
+hipError_t launch_sample_regions(const void *d_shard, const void *d_first, size_t Q, uint64_t cap, uint32_t S, bool tight, void *d_rows_of,
+                                 void *d_region, hipStream_t stream);
+hipError_t launch_sample_status(const void *d_first, size_t Q, const void *d_work, const void *d_locate_work2, void *d_status8, hipStream_t stream);
+hipError_t launch_sample_tally(const sample_tally &a, hipStream_t stream);
 // The 1-mismatch search of a set by worklist (mm1_worklist.hip; k <= 32, 0 < tn < k, one table depth k - tn for all
 // shards).  launch_mm1_worklists takes the step of the three substitutions of every traced position (d_trace
 // [nshards][m][tn], d_own [nshards][m] pairs: the traced search's output) and appends the variants that survive it to

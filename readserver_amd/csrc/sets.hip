@@ -30,6 +30,7 @@
 #include "capi_guard.h"
 #include "capi_internal.h"
 #include "meta_file.h"
+#include "sample_codes.h"
 #include "service.h"
 
 using namespace rsb;
@@ -146,12 +147,14 @@ struct rsbwt_set {
     std::mutex comm_mu;
     // the per-read sample table (rsbwt_set_meta_*): shard i's off u64[num_strings + 1] / value bytes, on shard i's device;
     // empty = no table.  Written by build / load / clear only, which must not run beside a lookup.
+    // d_heads: one bit per ordinal, set at the first ordinal of every string a pair named (rsbwt_set_sample_counts)
     struct meta_shard {
         uint64_t *d_off = nullptr;
         uint8_t *d_bytes = nullptr;
+        uint32_t *d_heads = nullptr;
     };
     std::vector<meta_shard> meta;
-    uint64_t meta_bytes = 0;
+    uint64_t meta_bytes = 0, meta_head_bytes = 0;
 };
 
 namespace {
@@ -2497,6 +2500,8 @@ namespace {
 // the calling thread's last lookup: items, items with a value, value bytes copied, LF steps of the string searches
 thread_local uint64_t meta_last_work[4] = {0, 0, 0, 0};
 
+inline size_t meta_head_words(uint64_t num_strings) { return (size_t)((num_strings + 31) / 32); }
+
 int meta_required(const rsbwt_set_t *s) {
     return s->meta.empty() ? fail(RSBWT_EINVAL, "the set has no sample table (rsbwt_set_meta_build / rsbwt_set_meta_load)") : RSBWT_OK;
 }
@@ -2536,12 +2541,16 @@ int meta_build_shard(hipStream_t st, uint64_t ns, const uint64_t *ord, const uin
     HIP_OK(hipMemsetAsync(d_win, 0, (ns + 1) * 8, st));
     HIP_OK(hipMemsetAsync(d_len, 0, (ns + 1) * 8, st));
     HIP_OK(hipMemsetAsync(d_given, 0, 8, st));
+    const size_t head_bytes = meta_head_words(ns) * 4;
+    HIP_OK(hipMalloc((void **)&out->d_heads, head_bytes ? head_bytes : 4));
+    HIP_OK(hipMemsetAsync(out->d_heads, 0, head_bytes ? head_bytes : 4, st));
     hipError_t e;
     for (size_t c0 = 0; c0 < n; c0 += CH) {
         const size_t m = std::min(CH, n - c0);
         HIP_OK(hipMemcpyAsync(d_a, ord + c0, m * 8, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(d_b, cp + c0, m * 8, hipMemcpyHostToDevice, st));
         if ((e = launch_meta_winners(d_a, d_b, m, c0, d_win, ns, st)) != hipSuccess) return fail_hip(e, "winner kernel launch");
+        if ((e = launch_meta_heads(d_a, d_b, m, out->d_heads, ns, st)) != hipSuccess) return fail_hip(e, "head-bit kernel launch");
     }
     for (size_t c0 = 0; c0 < n; c0 += CH) {
         const size_t m = std::min(CH, n - c0);
@@ -2589,8 +2598,8 @@ int meta_publish(rsbwt_set_t *s) {
         if (rc) return rc;
         std::vector<meta_view> v;
         for (size_t i : g->idx) {
-            meta_view mv = {nullptr, nullptr, 0};
-            if (!s->meta.empty()) mv = {s->meta[i].d_off, s->meta[i].d_bytes, s->shards[i]->view.C[1]};
+            meta_view mv = {nullptr, nullptr, 0, nullptr};
+            if (!s->meta.empty()) mv = {s->meta[i].d_off, s->meta[i].d_bytes, s->shards[i]->view.C[1], s->meta[i].d_heads};
             v.push_back(mv);
         }
         if (!g->d_meta) HIP_OK(hipMalloc((void **)&g->d_meta, v.size() * sizeof(meta_view)));
@@ -2601,10 +2610,11 @@ int meta_publish(rsbwt_set_t *s) {
 
 void meta_free_tables(rsbwt_set_t *s, std::vector<rsbwt_set::meta_shard> &tabs) {
     for (size_t i = 0; i < tabs.size(); ++i) {
-        if (!tabs[i].d_off && !tabs[i].d_bytes) continue;
+        if (!tabs[i].d_off && !tabs[i].d_bytes && !tabs[i].d_heads) continue;
         (void)hipSetDevice(s->shards[i]->device);
         if (tabs[i].d_off) (void)hipFree(tabs[i].d_off);
         if (tabs[i].d_bytes) (void)hipFree(tabs[i].d_bytes);
+        if (tabs[i].d_heads) (void)hipFree(tabs[i].d_heads);
     }
     tabs.clear();
 }
@@ -2641,9 +2651,11 @@ int set_meta_build_body(rsbwt_set_t *s, const char *text, const uint64_t *off, c
     meta_free_tables(s, s->meta);
     s->meta = std::move(tabs);
     s->meta_bytes = 0;
+    s->meta_head_bytes = 0;
     uint64_t st[4] = {0, 0, 0, 0};
     for (size_t i = 0; i < S; ++i) {
         s->meta_bytes += (s->shards[i]->view.C[1] + 1) * 8 + bytes[i];
+        s->meta_head_bytes += meta_head_words(s->shards[i]->view.C[1]) * 4;
         st[2] += given[i];
         st[3] += bytes[i];
     }
@@ -2827,6 +2839,277 @@ int set_read_meta_var_body(rsbwt_set_t *s, const char *text, const uint64_t *off
     return RSBWT_OK;
 }
 
+// ---- sample counts (sample_counts.hip): the located rows of a batch reduced to per-query sample matrices ----
+// the calling thread's last call: candidate rows, rows on a head ordinal, distinct carriers, records added, records with an
+// unknown code, LF steps of the rows' walks (counting mode only)
+thread_local uint64_t sample_last_work[6] = {0, 0, 0, 0, 0, 0};
+
+struct sample_dict {
+    std::vector<uint64_t> keys;  // (host form; the device form brings them in HBM)
+    uint32_t C = 0, size_of_sample = 0, has_other = 0;
+};
+
+int sample_shape_ok(size_t C, uint32_t size_of_sample) {
+    if (size_of_sample < 1u || size_of_sample > SAMPLE_CODE_MAX) return fail(RSBWT_EINVAL, "size_of_sample %u: 1 to 8 bytes", size_of_sample);
+    if (C == 0) return fail(RSBWT_EINVAL, "an empty sample dictionary");
+    if (C >= (1ull << 31)) return fail(RSBWT_EINVAL, "%zu sample codes: at most 2^31 - 1", C);
+    return RSBWT_OK;
+}
+
+int sample_dict_make(const uint8_t *codes, size_t C, uint32_t size_of_sample, int has_other, sample_dict *d) {
+    const int rc = sample_shape_ok(C, size_of_sample);
+    if (rc) return rc;
+    size_t bad = 0;
+    switch (sample_codes_check(codes, C, size_of_sample, &d->keys, &bad)) {
+    case SAMPLE_CODES_OK: break;
+    case SAMPLE_CODES_ORDER: return fail(RSBWT_EINVAL, "sample code %zu is not above code %zu: the dictionary must be strictly ascending", bad, bad - 1);
+    default: return fail(RSBWT_EINVAL, "null argument");
+    }
+    d->C = (uint32_t)C;
+    d->size_of_sample = size_of_sample;
+    d->has_other = has_other ? 1u : 0u;
+    return RSBWT_OK;
+}
+
+int sample_set_ok(const rsbwt_set_t *s) {
+    if (!s) return fail(RSBWT_EINVAL, "null set");
+    const int rc = meta_required(s);
+    if (rc) return rc;
+    for (const rsbwt_t *h : s->shards) {
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
+        if (h->view.C[1] >= (1ull << 40)) return fail(RSBWT_EINVAL, "a shard of %llu strings: sample counts take fewer than 2^40", (unsigned long long)h->view.C[1]);
+    }
+    return RSBWT_OK;
+}
+
+// (read at every call: a test turns it on and off inside one process)
+bool sample_tight_set() {
+    const char *e = getenv("RSBWT_SAMPLE_TIGHT_SET");
+    return e && e[0] == '1' && e[1] == 0;
+}
+
+inline size_t sample_tally_scratch(uint32_t S, uint64_t cap) {
+    return al256((size_t)S * 8) + al256((size_t)S * 16) + al256(TALLY_WORK_COUNTERS * TALLY_WORK_STRIDE * 8) + al256((size_t)(4 * cap + S) * 8);
+}
+
+// What follows the walks, enqueued on st and nothing else: the matrices and carriers[] zeroed, the set's regions sized from
+// the rows each shard has, the tally, and status8 (launch_sample_status).  d_scratch: sample_tally_scratch(S, cap) bytes.
+int sample_tally_enqueue(dev_group *g, hipStream_t st, uint8_t *d_scratch, const void *d_first, size_t Q, const void *d_sh, const void *d_od,
+                         uint64_t cap, const void *d_keys, const sample_dict &d, bool tight, const void *d_locate_work2, void *d_strings,
+                         void *d_copies, void *d_carriers, void *d_status8) {
+    const uint32_t S = (uint32_t)g->idx.size();
+    const size_t cells = Q * ((size_t)d.C + 1), work_bytes = TALLY_WORK_COUNTERS * TALLY_WORK_STRIDE * 8, slots = (size_t)(4 * cap + S);
+    uint8_t *d_rows_of = d_scratch, *d_region = d_rows_of + al256((size_t)S * 8), *d_work = d_region + al256((size_t)S * 16),
+            *d_set = d_work + al256(work_bytes);
+    if (d_strings) HIP_OK(hipMemsetAsync(d_strings, 0, cells * 4, st));
+    if (d_copies) HIP_OK(hipMemsetAsync(d_copies, 0, cells * 8, st));
+    if (d_carriers) HIP_OK(hipMemsetAsync(d_carriers, 0, Q * 8, st));
+    HIP_OK(hipMemsetAsync(d_rows_of, 0, (size_t)S * 8, st));
+    HIP_OK(hipMemsetAsync(d_work, 0, work_bytes, st));
+    HIP_OK(hipMemsetAsync(d_set, 0xFF, slots * 8, st));
+    hipError_t e = launch_sample_regions(d_sh, d_first, Q, cap, S, tight, d_rows_of, d_region, st);
+    if (e != hipSuccess) return fail_hip(e, "region kernel launches");
+    sample_tally a;
+    a.meta = g->d_meta;
+    a.S = S;
+    a.first = (const uint64_t *)d_first;
+    a.Q = Q;
+    a.shard = (const uint32_t *)d_sh;
+    a.ordinal = (const uint64_t *)d_od;
+    a.total = cap;
+    a.set = (unsigned long long *)d_set;
+    a.region = (const uint64_t *)d_region;
+    a.keys = (const uint64_t *)d_keys;
+    a.C = d.C;
+    a.size_of_sample = d.size_of_sample;
+    a.has_other = d.has_other;
+    a.keys_in_lds = 0;
+    a.strings = (uint32_t *)d_strings;
+    a.copies = (long long *)d_copies;
+    a.carriers = (unsigned long long *)d_carriers;
+    a.work = (unsigned long long *)d_work;
+    if ((e = launch_sample_tally(a, st)) != hipSuccess) return fail_hip(e, "tally kernel launch");
+    if ((e = launch_sample_status(d_first, Q, d_work, d_locate_work2, d_status8, st)) != hipSuccess) return fail_hip(e, "status kernel launch");
+    return RSBWT_OK;
+}
+
+// One device group's `total` rows of mq queries -> that group's matrices in host memory (each optional), on gc's stream and
+// in gc.lb.  The rows' first[] is d_first_in in HBM, or h_first to upload; fill(d_sh, d_rows) enqueues what makes the rows.
+// Once that is enqueued nothing of gc.la is read again (first[] has been copied), and the lease goes back: a call then
+// holds one lease plus a launch's own short one, so eight calls at once stay inside the cache's 16 slots.
+// work6 += the group's counters (work6[0], the rows, is the caller's).
+template <class Fill>
+int sample_group_counts(dev_group *g, group_call &gc, size_t mq, const void *d_first_in, const uint64_t *h_first, uint64_t total,
+                        const sample_dict &d, bool tight, uint32_t max_steps, Fill &&fill, uint32_t *strings, int64_t *copies, uint64_t *carriers,
+                        uint64_t *work6) {
+    hipStream_t st = gc.st;
+    const uint32_t S = (uint32_t)g->idx.size();
+    const size_t cells = mq * ((size_t)d.C + 1);
+    const size_t a8 = al256(total * 8), a4 = al256(total * 4), a_first = al256((mq + 1) * 8), a_keys = al256((size_t)d.C * 8),
+                 a_str = strings ? al256(cells * 4) : 0, a_cp = copies ? al256(cells * 8) : 0, a_car = al256(mq * 8);
+    hipError_t e = g->scratch.take(2 * a8 + a4 + a_first + a_keys + a_str + a_cp + a_car + 512 + sample_tally_scratch(S, total), st, &gc.lb);
+    if (e != hipSuccess)
+        return fail(RSBWT_ENOMEM, "%llu rows and %zu matrix cells do not fit the device's free memory: %s", (unsigned long long)total, cells,
+                    hipGetErrorString(e));
+    uint8_t *d_rows = (uint8_t *)gc.lb.p, *d_od = d_rows + a8, *d_sh = d_od + a8, *d_first = d_sh + a4, *d_keys = d_first + a_first,
+            *d_str = d_keys + a_keys, *d_cp = d_str + a_str, *d_car = d_cp + a_cp, *d_wk = d_car + a_car, *d_status = d_wk + 256,
+            *d_scratch = d_status + 256;
+    if (d_first_in) HIP_OK(hipMemcpyAsync(d_first, d_first_in, (mq + 1) * 8, hipMemcpyDeviceToDevice, st));
+    else HIP_OK(hipMemcpyAsync(d_first, h_first, (mq + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_keys, d.keys.data(), (size_t)d.C * 8, hipMemcpyHostToDevice, st));
+    int rc = fill(d_sh, d_rows);
+    if (rc) return rc;
+    if (gc.la.slot >= 0) {
+        g->scratch.give(gc.la, st);
+        gc.la = scratch_cache::lease();
+    }
+    HIP_OK(hipMemsetAsync(d_wk, 0, 16, st));
+    e = launch_locate(g->scratch, g->d_views, S, d_sh, d_rows, (size_t)total, max_steps, nullptr, d_od, nullptr, (unsigned long long *)d_wk,
+                      g->num_cus, st);
+    if (e != hipSuccess) return fail_hip(e, "locate kernel launch");
+    rc = sample_tally_enqueue(g, st, d_scratch, d_first, mq, d_sh, d_od, total, d_keys, d, tight, d_wk, strings ? d_str : nullptr,
+                              copies ? d_cp : nullptr, d_car, d_status);
+    if (rc) return rc;
+    uint64_t status[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (strings) HIP_OK(hipMemcpyAsync(strings, d_str, cells * 4, hipMemcpyDeviceToHost, st));
+    if (copies) HIP_OK(hipMemcpyAsync(copies, d_cp, cells * 8, hipMemcpyDeviceToHost, st));
+    if (carriers) HIP_OK(hipMemcpyAsync(carriers, d_car, mq * 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(status, d_status, sizeof status, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (status[6] != 0)
+        return fail(RSBWT_EINVAL, "%llu rows whose walk to their read's start does not end within max_steps (a corrupt index, or a read longer than the limit)",
+                    (unsigned long long)status[6]);
+    for (int i = 1; i <= 4; ++i) work6[i] += status[i];
+    if (g->counting) work6[5] += status[5];
+    return RSBWT_OK;
+}
+
+void sample_zero(size_t mq, size_t C, uint32_t *strings, int64_t *copies, uint64_t *carriers) {
+    const size_t cells = mq * (C + 1);
+    if (strings) memset(strings, 0, cells * 4);
+    if (copies) memset(copies, 0, cells * 8);
+    if (carriers) memset(carriers, 0, mq * 8);
+}
+
+// a slice of mq queries on a set of ONE device group: nothing but first[], matches[] and the answers leaves the device
+int sample_counts_device(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t mq, const sample_dict &d, bool tight, uint64_t max_rows,
+                         uint32_t max_steps, uint32_t *strings, int64_t *copies, uint64_t *matches, uint64_t *carriers, uint64_t *work6) {
+    capped_intervals ci;  // (before gc: a copy into it may still be in flight when gc waits for the stream)
+    std::vector<uint64_t> first(mq + 1);
+    group_call gc(s->groups[0], true);
+    if (gc.rc) return gc.rc;
+    dev_group *g = gc.g;
+    const uint32_t S = (uint32_t)g->idx.size();
+    int rc = capped_intervals_device(s, gc, text, off, mq, max_rows, 0, mq + 1, "scratch for sample counts", first.data(), matches, &ci);
+    if (rc) return rc;
+    const uint64_t total = ci.total;
+    work6[0] += total;
+    if (total == 0) {
+        sample_zero(mq, d.C, strings, copies, carriers);
+        return RSBWT_OK;
+    }
+    if (total >= (1ull << 38)) return fail(RSBWT_ERANGE, "%llu rows in one slice: at most 2^38 (set max_rows)", (unsigned long long)total);
+    return sample_group_counts(
+        g, gc, mq, ci.d_first, nullptr, total, d, tight, max_steps,
+        [&](uint8_t *d_sh, uint8_t *d_rows) -> int {
+            const hipError_t e = launch_interval_fill(g->d_views, S, ci.d_pairs, mq, ci.d_first, (size_t)total, d_sh, d_rows, nullptr, nullptr, nullptr, gc.st);
+            return e == hipSuccess ? RSBWT_OK : fail_hip(e, "row expansion");
+        },
+        strings, copies, carriers, work6);
+}
+
+// the same over several device groups: the intervals come to the host, the limit and the expansion run there
+// (intervals_to_rows_host); every group locates and tallies its shards' rows into matrices of its own, and the host adds them
+int sample_counts_groups(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t mq, const sample_dict &d, bool tight, uint64_t max_rows,
+                         uint32_t max_steps, uint32_t *strings, int64_t *copies, uint64_t *matches, uint64_t *carriers, uint64_t *work6) {
+    const size_t S = s->shards.size(), G = s->groups.size(), cells = mq * ((size_t)d.C + 1);
+    std::vector<uint64_t> lo(S * mq), up(S * mq), first(mq + 1);
+    int rc = rsbwt_set_find_intervals_var_body(s, text, off, mq, lo.data(), up.data(), false);
+    if (rc) return rc;
+    const expanded_rows hr = intervals_to_rows_host(s, mq, lo, up, max_rows, ~(size_t)0, first.data(), matches);
+    work6[0] += hr.total;
+    sample_zero(mq, d.C, strings, copies, carriers);
+    if (hr.total == 0) return RSBWT_OK;
+    std::vector<uint32_t> group_of(S, 0), local(S, 0);
+    for (size_t gi = 0; gi < G; ++gi)
+        for (size_t j = 0; j < s->groups[gi]->idx.size(); ++j) {
+            group_of[s->groups[gi]->idx[j]] = (uint32_t)gi;
+            local[s->groups[gi]->idx[j]] = (uint32_t)j;
+        }
+    struct share_t {
+        std::vector<uint64_t> first, rows, carriers;
+        std::vector<uint32_t> shard, strings;
+        std::vector<int64_t> copies;
+        uint64_t work[6] = {0, 0, 0, 0, 0, 0};
+    };
+    std::vector<share_t> sh(G);
+    for (share_t &x : sh) x.first.assign(mq + 1, 0);
+    for (size_t q = 0; q < mq; ++q) {
+        for (size_t gi = 0; gi < G; ++gi) sh[gi].first[q] = sh[gi].rows.size();
+        for (uint64_t t = first[q]; t < first[q + 1]; ++t) {
+            share_t &x = sh[group_of[hr.shard_of[t]]];
+            x.shard.push_back(local[hr.shard_of[t]]);
+            x.rows.push_back(hr.rows[t]);
+        }
+    }
+    for (size_t gi = 0; gi < G; ++gi) sh[gi].first[mq] = sh[gi].rows.size();
+    rc = for_each_group(s, [&](size_t gi) -> int {
+        share_t &x = sh[gi];
+        const size_t m = x.rows.size();
+        if (m == 0) return RSBWT_OK;
+        if (strings) x.strings.resize(cells);
+        if (copies) x.copies.resize(cells);
+        x.carriers.resize(mq);
+        group_call gc(s->groups[gi], true);
+        if (gc.rc) return gc.rc;
+        return sample_group_counts(
+            gc.g, gc, mq, nullptr, x.first.data(), m, d, tight, max_steps,
+            [&](uint8_t *d_sh, uint8_t *d_rows) -> int {
+                HIP_OK(hipMemcpyAsync(d_sh, x.shard.data(), m * 4, hipMemcpyHostToDevice, gc.st));
+                HIP_OK(hipMemcpyAsync(d_rows, x.rows.data(), m * 8, hipMemcpyHostToDevice, gc.st));
+                return RSBWT_OK;
+            },
+            strings ? x.strings.data() : nullptr, copies ? x.copies.data() : nullptr, x.carriers.data(), x.work);
+    });
+    if (rc) return rc;
+    for (const share_t &x : sh) {
+        if (x.rows.empty()) continue;
+        for (size_t i = 0; i < cells; ++i) {
+            if (strings) strings[i] += x.strings[i];
+            if (copies) copies[i] += x.copies[i];
+        }
+        if (carriers)
+            for (size_t q = 0; q < mq; ++q) carriers[q] += x.carriers[q];
+        for (int i = 1; i < 6; ++i) work6[i] += x.work[i];
+    }
+    return RSBWT_OK;
+}
+
+int set_sample_counts_body(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint8_t *codes, size_t C, uint32_t size_of_sample,
+                           int has_other, uint64_t max_rows, uint32_t max_steps, uint32_t *strings, int64_t *copies, uint64_t *matches,
+                           uint64_t *carriers) {
+    int rc = sample_set_ok(s);
+    if (rc) return rc;
+    sample_dict d;
+    if ((rc = sample_dict_make(codes, C, size_of_sample, has_other, &d)) != RSBWT_OK) return rc;
+    if (!strings && !copies && !matches && !carriers) return fail(RSBWT_EINVAL, "null argument: no output array");
+    if (Q == 0) return RSBWT_OK;
+    if (!off || (!text && off[Q] != off[0])) return fail(RSBWT_EINVAL, "null argument");
+    // slices: a query number of the set's keys has 24 bits, and a slice's matrices (12 bytes a cell) stay under 1.5 GiB of HBM
+    const size_t width = C + 1, SLICE = std::min<size_t>((size_t)1 << 24, std::max<size_t>(1, ((size_t)1 << 27) / width));
+    const bool tight = sample_tight_set(), on_device = s->groups.size() == 1 && s->shards.size() <= 1024;
+    for (size_t q0 = 0; q0 < Q; q0 += SLICE) {
+        const size_t mq = std::min(SLICE, Q - q0);
+        uint32_t *st = strings ? strings + q0 * width : nullptr;
+        int64_t *cp = copies ? copies + q0 * width : nullptr;
+        uint64_t *mt = matches ? matches + q0 : nullptr, *ca = carriers ? carriers + q0 : nullptr;
+        rc = on_device ? sample_counts_device(s, text, off + q0, mq, d, tight, max_rows, max_steps, st, cp, mt, ca, sample_last_work)
+                       : sample_counts_groups(s, text, off + q0, mq, d, tight, max_rows, max_steps, st, cp, mt, ca, sample_last_work);
+        if (rc) return rc;
+    }
+    return RSBWT_OK;
+}
+
 int read_file(const char *path, std::string *out) {
     FILE *f = fopen(path, "rb");
     if (!f) return fail(RSBWT_EIO, "cannot open %s", path);
@@ -2843,6 +3126,7 @@ int read_file(const char *path, std::string *out) {
 static void meta_free(rsbwt_set_t *s) {
     meta_free_tables(s, s->meta);
     s->meta_bytes = 0;
+    s->meta_head_bytes = 0;
 }
 
 namespace {
@@ -2952,6 +3236,103 @@ int rsbwt_set_read_meta_var(rsbwt_set_t *s, const char *text, const uint64_t *of
 
 void rsbwt_set_meta_last_work(uint64_t *work4) {
     if (work4) memcpy(work4, meta_last_work, sizeof meta_last_work);
+}
+
+int rsbwt_set_sample_counts(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint8_t *codes, size_t C, uint32_t size_of_sample,
+                            int has_other_meta_data, uint64_t max_rows, uint32_t max_steps, uint32_t *strings, int64_t *copies, uint64_t *matches,
+                            uint64_t *carriers) {
+    return guarded("rsbwt_set_sample_counts", [&]() -> int {
+        for (uint64_t &w : sample_last_work) w = 0;
+        return set_sample_counts_body(s, text, off, Q, codes, C, size_of_sample, has_other_meta_data, max_rows, max_steps, strings, copies, matches,
+                                      carriers);
+    });
+}
+
+// one-device set, the caller's buffers and stream, nothing synchronised
+int rsbwt_set_sample_counts_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, uint32_t max_len, const void *d_keys, size_t C,
+                                uint32_t size_of_sample, int has_other_meta_data, uint64_t max_rows, uint32_t max_steps, size_t cap_rows,
+                                void *d_strings, void *d_copies, void *d_matches, void *d_carriers, void *d_status8, void *stream) {
+    return guarded("rsbwt_set_sample_counts_dev", [&]() -> int {
+        dev_group *g = nullptr;
+        int rc = one_device_group(s, &g);
+        if (rc) return rc;
+        if ((rc = sample_set_ok(s)) != RSBWT_OK) return rc;
+        if ((rc = sample_shape_ok(C, size_of_sample)) != RSBWT_OK) return rc;
+        if (!d_keys || !d_status8) return fail(RSBWT_EINVAL, "null argument");
+        if (!d_strings && !d_copies && !d_matches && !d_carriers) return fail(RSBWT_EINVAL, "null argument: no output array");
+        hipStream_t st = (hipStream_t)stream;
+        if (Q == 0) {
+            HIP_OK(hipMemsetAsync(d_status8, 0, 64, st));
+            return RSBWT_OK;
+        }
+        if (!d_text || !d_off) return fail(RSBWT_EINVAL, "null argument");
+        if (Q > ((size_t)1 << 24)) return fail(RSBWT_EINVAL, "%zu queries: the device form takes at most 2^24 per call", Q);
+        if (max_len == 0 || max_len > 65535u) return fail(RSBWT_EINVAL, "max_len %u: 1 to 65,535 symbols", max_len);
+        if (cap_rows >= ((size_t)1 << 38)) return fail(RSBWT_ERANGE, "room for %zu rows: at most 2^38 per call", cap_rows);
+        const uint32_t S = (uint32_t)g->idx.size(), wpq = words_per_kmer(max_len);
+        if (S > 1024) return fail(RSBWT_EINVAL, "%u shards: the device form takes at most 1,024", S);
+        sample_dict d;
+        d.C = (uint32_t)C;
+        d.size_of_sample = size_of_sample;
+        d.has_other = has_other_meta_data ? 1u : 0u;
+        const size_t a_pk = al256(Q * wpq * 8), a_ok = al256(Q), a_len = al256(Q * 4), a_rec = al256((size_t)S * Q * 16), a_q = al256((Q + 1) * 8),
+                     tmp_bytes = interval_rows_scan_bytes(Q + 1), a8 = al256(cap_rows * 8), a4 = al256(cap_rows * 4);
+        scratch_cache::lease mem;
+        hipError_t e = g->scratch.take(a_pk + a_ok + a_len + 2 * a_rec + 3 * a_q + 512 + tmp_bytes + 256 + 2 * a8 + a4 + sample_tally_scratch(S, cap_rows),
+                                       st, &mem);
+        if (e != hipSuccess) return fail_hip(e, "scratch for sample counts");
+        uint8_t *d_pk = (uint8_t *)mem.p, *d_ok = d_pk + a_pk, *d_len = d_ok + a_ok, *d_rec = d_len + a_len, *d_pairs = d_rec + a_rec,
+                *d_mt = d_pairs + a_rec, *d_kept = d_mt + a_q, *d_first = d_kept + a_q, *d_over = d_first + a_q, *d_wk = d_over + 256,
+                *d_tmp = d_wk + 256, *d_rows = d_tmp + tmp_bytes + 256, *d_od = d_rows + a8, *d_sh = d_od + a8, *d_scratch = d_sh + a4;
+        void *matches = d_matches ? d_matches : (void *)d_mt;
+        rc = [&]() -> int {
+            if ((e = launch_pack_var(d_text, d_off, Q, wpq, d_pk, d_ok, d_len, st)) != hipSuccess) return fail_hip(e, "pack kernel launch");
+            if ((e = launch_search_init_var(g->d_views, S, d_pk, d_ok, d_len, Q, wpq, d_rec, st)) != hipSuccess)
+                return fail_hip(e, "start-record kernel launch");
+            search_extra ex;
+            ex.narrow = group_is_narrow(s, g, max_len);
+            ex.d_init = d_rec;
+            ex.pairs = true;
+            const int rs = search_launch(*g, g->d_views, S, g->num_cus, d_pk, d_ok, Q, max_len, d_pairs, nullptr, false, st, &ex);
+            if (rs) return rs;
+            if ((e = launch_interval_totals(g->d_views, S, d_pairs, Q, max_rows, matches, d_kept, d_first, d_over, d_tmp, tmp_bytes, st)) != hipSuccess)
+                return fail_hip(e, "interval-rows kernels");
+            if (cap_rows) {
+                // (rows past first[Q], and every row when first[Q] > cap_rows, name no shard: the walk leaves them alone)
+                HIP_OK(hipMemsetAsync(d_sh, 0xFF, cap_rows * 4, st));
+                HIP_OK(hipMemsetAsync(d_od, 0xFF, cap_rows * 8, st));
+                if ((e = launch_interval_fill(g->d_views, S, d_pairs, Q, d_first, cap_rows, d_sh, d_rows, nullptr, nullptr, nullptr, st)) != hipSuccess)
+                    return fail_hip(e, "row expansion");
+                HIP_OK(hipMemsetAsync(d_wk, 0, 16, st));
+                e = launch_locate(g->scratch, g->d_views, S, d_sh, d_rows, cap_rows, max_steps, nullptr, d_od, nullptr, (unsigned long long *)d_wk,
+                                  g->num_cus, st);
+                if (e != hipSuccess) return fail_hip(e, "locate kernel launch");
+            } else {
+                HIP_OK(hipMemsetAsync(d_wk, 0, 16, st));
+            }
+            return sample_tally_enqueue(g, st, d_scratch, d_first, Q, d_sh, d_od, cap_rows, d_keys, d, sample_tight_set(), d_wk, d_strings, d_copies,
+                                        d_carriers, d_status8);
+        }();
+        g->scratch.give(mem, st);
+        return rc;
+    });
+}
+
+void rsbwt_set_sample_last_work(uint64_t *work6) {
+    if (work6) memcpy(work6, sample_last_work, sizeof sample_last_work);
+}
+
+uint64_t rsbwt_set_meta_head_bytes(const rsbwt_set_t *s) { return s ? s->meta_head_bytes : 0; }
+
+int rsbwt_sample_keys(const uint8_t *codes, size_t C, uint32_t size_of_sample, uint64_t *keys) {
+    return guarded("rsbwt_sample_keys", [&]() -> int {
+        sample_dict d;
+        const int rc = sample_dict_make(codes, C, size_of_sample, 0, &d);
+        if (rc) return rc;
+        if (!keys) return fail(RSBWT_EINVAL, "null argument");
+        memcpy(keys, d.keys.data(), C * 8);
+        return RSBWT_OK;
+    });
 }
 
 int rsbwt_rccl_available(void) { return rccl().ok ? 1 : 0; }

@@ -548,7 +548,10 @@ void rsbwt_set_kmer_last_times(double *ms3);
  *                                       then left;
  *   tile COVERING it:                   leg 1 grows right only, leg 2 left only.
  * A leg that would need a < 0 or b > L has no answer and is left out (the reference loops forever or throws
- * std::out_of_range there); the tile's other leg still counts.  Every row j of a leg's interval is a candidate; with the
+ * std::out_of_range there); the tile's other leg still counts.  An empty leg carries the (lower, upper) the reference's
+ * search ends with: lower = upper + 1, or -- on a shard where no '$' row lies before the rows that begin with A -- the
+ * reference's (0, 2^64 - 1), which does not end a search and from which the next symbol c gives (C[c], C[c] - 1); neither
+ * holds a row.  Every row j of a leg's interval is a candidate; with the
  * reference's start = a + 1 and end = b the span filter keeps it iff
  *   LEFT:   pos - end <= (|extractPostfix(j)| - k) + 4        RIGHT:   start - pos <= |extractPrefix(j)| + 4
  * (the differences in unsigned 64-bit arithmetic as the reference takes them: a leg lengthened past pos keeps no row;

@@ -138,6 +138,19 @@ gt_narrow_kernel(const shard_view *__restrict__ shards, const gt_batch bt, gt_le
             if (!complete) {
                 if ((!fresh && lo > hi) || j < (int32_t)a) {
                     complete = true;
+                } else if (lo == 0ull && hi == ~0ull) {
+                    // the reference's (0, 2^64 - 1): a symbol that is absent (initInterval), or an A that no row of the
+                    // interval sees before it, on a shard where no '$' row lies before the rows that begin with A
+                    // (C[A] == 0).  query.cpp:35 does not end the search there (0 > 2^64 - 1 is false) and the next
+                    // updateInterval takes getOcc(c, -1) = 0 on both sides: (C[c], C[c] - 1), an LF step that reads no
+                    // position -- the search ends on it, or stays in the corner where C[c] == 0
+                    c = gt_rank(text[j]);
+                    lo = sv->C[c];
+                    hi = lo - 1ull;
+                    --j;
+                    fresh = false;
+                    steps += stage_grow;
+                    continue;
                 } else {
                     c = gt_rank(text[j]);
                     occ_lo = 0;
@@ -199,7 +212,11 @@ gt_narrow_kernel(const shard_view *__restrict__ shards, const gt_batch bt, gt_le
         if (pending) {
             p = phase ? hi : lo - 1ull;
             if (p >= n) {
-                bad = true;  // (never for an interval of this shard's rows)
+                // a defensive end, unreachable: a search is ranked only while lo <= hi (or before initInterval's first
+                // update, where hi = C[c] + total[c] - 1 < n unless it is the corner), every interval an update or a
+                // table entry of this shard gives has hi < n or is (0, 2^64 - 1), the corner is stepped above without a
+                // rank, and lo == 0 takes Occ(., -1) = 0 without one.  Nothing is read at p; the leg has no answer
+                bad = true;
             } else {
                 uint32_t pin;
                 w = fast_window(p, S, inv, pin);

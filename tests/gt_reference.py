@@ -51,10 +51,17 @@ def _wide(iv, M):
     return ((iv[1] - iv[0] + 1) & U64) > M
 
 
-def find_gt_reads(sh, w, index, kmers, skip, pos, M=M_DEFAULT, count=None):
-    """one tile: (legs, kept) -- legs = [(leg, a, b, lower, upper)], kept = {read string: its lowest identity row}"""
+def find_gt_reads(sh, w, index, kmers, skip, pos, M=M_DEFAULT, count=None, grown=None):
+    """one tile: (legs, kept) -- legs = [(leg, a, b, lower, upper)], kept = {read string: its lowest identity row};
+    grown (a list) takes every lengthening as (leg, "L" or "R", a, b): the side the symbol was taken in on and the longer
+    string w[a:b) that was searched"""
     C = count if count is not None else Counter()
     legs, kept = [], {}
+
+    def longer(leg, side, start, size):
+        if grown is not None:
+            grown.append((leg, side, start - 1, start - 1 + size))
+        return find(w[start - 1:start - 1 + size])
     length = len(w)
     kmer = w[(skip + 1) * index:(skip + 1) * index + kmers]
     if set(kmer) - set("ACGT"):  # don't bother with N (:513)
@@ -99,7 +106,7 @@ def find_gt_reads(sh, w, index, kmers, skip, pos, M=M_DEFAULT, count=None):
                     C["noleg.end>L"] += 1
                     ok = False
                     break
-                interval = find(w[start - 1:start - 1 + kmers + cnt])
+                interval = longer(1, "R", start, kmers + cnt)
                 end += 1
             if ok:
                 rows(1, start, end, interval, "left")
@@ -109,19 +116,21 @@ def find_gt_reads(sh, w, index, kmers, skip, pos, M=M_DEFAULT, count=None):
                 end = start + kmers - 1
                 cnt, ok = 1, True
                 start -= 1
-                interval = find(w[start - 1:start - 1 + kmers + cnt])
+                interval = longer(2, "L", start, kmers + cnt)
                 while _wide(interval, M):
                     cnt += 1
+                    side = "L"
                     if start > 1:
                         start -= 1
                     else:  # reach left most, continue to extend to the right (:560)
+                        side = "R"
                         C["left.leg2.turn"] += 1
                         if end + 1 > length:
                             C["noleg.end>L"] += 1
                             ok = False
                             break
                         end += 1
-                    interval = find(w[start - 1:start - 1 + kmers + cnt])
+                    interval = longer(2, side, start, kmers + cnt)
                 if ok:
                     rows(2, start, end, interval, "left")
         else:
@@ -138,7 +147,7 @@ def find_gt_reads(sh, w, index, kmers, skip, pos, M=M_DEFAULT, count=None):
                     ok = False
                     break
                 start -= 1
-                interval = find(w[start - 1:start - 1 + kmers + cnt])
+                interval = longer(1, "L", start, kmers + cnt)
             if ok:
                 rows(1, start, end, interval, "right")
             if end < length:  # not ending at the right most (:616)
@@ -147,19 +156,21 @@ def find_gt_reads(sh, w, index, kmers, skip, pos, M=M_DEFAULT, count=None):
                 end = start + kmers - 1
                 cnt, ok = 1, True
                 end += 1
-                interval = find(w[start - 1:start - 1 + kmers + cnt])
+                interval = longer(2, "R", start, kmers + cnt)
                 while _wide(interval, M):
                     cnt += 1
+                    side = "R"
                     if end < length:
                         end += 1
                     else:  # reach right most, continue to extend to the left (:630)
+                        side = "L"
                         C["right.leg2.turn"] += 1
                         if start <= 1:
                             C["noleg.start<1"] += 1
                             ok = False
                             break
                         start -= 1
-                    interval = find(w[start - 1:start - 1 + kmers + cnt])
+                    interval = longer(2, side, start, kmers + cnt)
                 if ok:
                     rows(2, start, end, interval, "right")
         else:
@@ -175,7 +186,7 @@ def find_gt_reads(sh, w, index, kmers, skip, pos, M=M_DEFAULT, count=None):
                     C["noleg.end>L"] += 1
                     ok = False
                     break
-                interval = find(w[start - 1:start - 1 + kmers + cnt])
+                interval = longer(1, "R", start, kmers + cnt)
                 end += 1
             if ok:
                 rows(1, start, end, interval, "cover")
@@ -188,7 +199,7 @@ def find_gt_reads(sh, w, index, kmers, skip, pos, M=M_DEFAULT, count=None):
                 ok = False
             else:
                 start -= 1
-                interval = find(w[start - 1:start - 1 + kmers + cnt])
+                interval = longer(2, "L", start, kmers + cnt)
                 while _wide(interval, M):
                     cnt += 1
                     if start <= 1:
@@ -196,7 +207,7 @@ def find_gt_reads(sh, w, index, kmers, skip, pos, M=M_DEFAULT, count=None):
                         ok = False
                         break
                     start -= 1
-                    interval = find(w[start - 1:start - 1 + kmers + cnt])
+                    interval = longer(2, "L", start, kmers + cnt)
             if ok:
                 rows(2, start, end, interval, "cover")
         else:
@@ -205,15 +216,19 @@ def find_gt_reads(sh, w, index, kmers, skip, pos, M=M_DEFAULT, count=None):
     return legs, kept
 
 
-def gt_query(sh, w, pos, k, skip, M=0, count=None):
+def gt_query(sh, w, pos, k, skip, M=0, count=None, grown=None):
     """GtTask::run's loop over the tiles (:1048-1072) in one shard: (legs as (tile, leg, a, b, lower, upper), ordered by
-    (tile, leg); reads as [(identity row, string)] ascending, a string once at its lowest row)"""
+    (tile, leg); reads as [(identity row, string)] ascending, a string once at its lowest row); grown (a list) takes the
+    lengthenings as (tile, leg, side, a, b)"""
     M = M if M else M_DEFAULT
     legs, kept = [], {}
     if k <= 0 or skip < 0 or len(w) < k or pos > len(w):
         return legs, []
     for i in range((len(w) - k) // (skip + 1) + 1):
-        lg, kp = find_gt_reads(sh, w, i, k, skip, pos, M, count)
+        mine = [] if grown is not None else None
+        lg, kp = find_gt_reads(sh, w, i, k, skip, pos, M, count, mine)
+        if grown is not None:
+            grown += [(i,) + x for x in mine]
         legs += [(i,) + x for x in sorted(lg)]
         for s, ident in kp.items():
             kept[s] = min(kept.get(s, ident), ident)

@@ -8,7 +8,8 @@ Half of a stream's queries are spelled from the stream itself (LF walks with the
 backward searches stay alive for tens of steps on a stream where a random string dies after a few.
 
 tests/test_stream_reference.py shows on the CPU what these inputs reach; tests/test_gpu_match_streams.py and
-tests/test_gpu_overlap_streams.py run them on the GPU."""
+tests/test_gpu_overlap_streams.py run them on the GPU.  The SiteMatch batches of the same sources (gt_queries, GT_PARAMS,
+gt_expected, gt_narrow_steps) are further down: tests/test_gt_stream_reference.py and tests/test_gpu_gt_streams.py."""
 import random
 
 import numpy as np
@@ -270,6 +271,182 @@ def overlap_lf_steps(srcs, batch_key, qs, max_overlap):
             _STEPS[at] = O.total_lf_steps([s.orc], qs, max_overlap)
         out.append(_STEPS[at])
     return out
+
+
+# ---- SiteMatch candidates (gt_reference) beyond the gt fixture: tests/test_gt_stream_reference.py shows on the CPU what
+# these batches reach, tests/test_gpu_gt_streams.py runs them on the GPU
+
+# (M, k, skip).  A run stream has 10^5 symbols at the most, where an 8-mer is nearly unique: lengthening needs k of 3 to 4,
+# and k below the table depth of 6 makes right growth cross it.  A read set is a BWT of reads, where the gt fixture's k do.
+# (k = 3 at skip = 1: at skip = 2 a batch of 60 queries of 70 symbols at the most has under 384 tiles, and the item grid of
+# the smallest k would not reach a fourth workgroup of 256 lanes)
+GT_PARAMS = {"stream": [(1, 8, 0), (8, 4, 0), (50, 3, 1), (3, 12, 3)], "reads": [(1, 8, 0), (3, 12, 3), (8, 20, 1)]}
+GT_SHORT = "AC"  # shorter than every k used
+
+
+def gt_params(src):
+    return GT_PARAMS["reads" if src.reads is not None else "stream"]
+
+
+def _gt_pos(rng, i, L):
+    """the site cycles through 1, the middle, L, 0 (every tile on the right), L + 1 (past the end: no tiles), a random one"""
+    return (1, L // 2, L, 0, L + 1, rng.randint(0, L))[i % 6]
+
+
+def _gt_corner_queries(src, rng):
+    """two symbols in front of a string whose interval touches an end of the rows that begin with a base, for all 16 pairs:
+    where the first step leaves the reference's (0, 2^64 - 1), the search has symbols left; three of them inside a spelled
+    query, where LEFT, RIGHT and COVERING tiles hold them"""
+    oix, n = src.orc.oix, src.n
+    xs = [suffix_at(oix, oix.pc("A"), 7), suffix_at(oix, n - 1, 7)]
+    out = []
+    for x in xs:
+        for i, (c1, c2) in enumerate((c1, c2) for c1 in ACGT for c2 in ACGT):
+            w = c2 + c1 + x
+            out.append((w, 1 if i % 2 == 0 else len(w)))
+    depth = src.depths()
+    host = spell(oix, int(np.argmax(depth)), 60)
+    host = (host + _rand(rng, 60))[:60]
+    for c2, c1, x in (("C", "A", xs[0]), ("G", "A", xs[0]), ("T", "A", xs[1])):
+        w = host[:26] + c2 + c1 + x + host[26:]
+        out.append((w[:70], 30))
+    return out
+
+
+def _gt_stream_queries(src):
+    rng = random.Random(f"gt/{src.name}/small")
+    oix = src.orc.oix
+    depth = src.depths()
+    deep = np.argsort(-depth, kind="stable")[:64]
+    body = []
+    for i in range(6):  # spelled, every third with a substitution
+        w = ""
+        for _ in range(8):  # (where a walk meets '$' early: several spellings end to end, 70 symbols in all)
+            w += spell(oix, int(deep[rng.randrange(len(deep))]), 70 - len(w))
+        w = (w + _rand(rng, 70))[:70]
+        body.append(_substituted(rng, w) if i % 3 == 0 else w)
+    body += [_rand(rng, rng.randint(40, 70)) for _ in range(2)] + [_rand(rng, 70, "ACGTNNNN")]
+    body = [(w, _gt_pos(rng, i, len(w))) for i, w in enumerate(body)]
+    body += _gt_corner_queries(src, rng)
+    if src.name == "single":
+        body += [("CCCCCCCCA", 1), ("ACCCCCCCC", 9), ("CCCCACCCC", 5)]
+    w = spell(oix, int(deep[0]), 70) or "ACGT" * 10
+    w = (w + _rand(rng, 40))[:max(len(w), 40)]
+    h = len(w) // 2
+    # an N in a tile; a lengthening that runs into an N: a spelled (hence frequent) stretch with an N on either side of it
+    body += [(GT_SHORT, 1), (w[:h] + "N" + w[h + 1:], h), (w[:4] + "N" + w[5:h] + "N" + w[h + 1:], 1)]
+    return body
+
+
+def _gt_read_queries(src):
+    rng = random.Random(f"gt/{src.name}/small")
+    fx = F.fixture(src.name)
+    body = []
+    for i in range(12):  # windows of the sources, every fifth with a substitution
+        s = fx.sources[rng.randrange(len(fx.sources))]
+        ln = rng.randint(30, MAX_QUERY)
+        at = rng.randrange(len(s) - ln)
+        body.append(_substituted(rng, s[at:at + ln]) if i % 5 == 0 else s[at:at + ln])
+    for s in fx.extra[-6:] if src.name == "repeat" else ():  # the tandem repeats: intervals far above every M
+        body.append(s[:MAX_QUERY])
+    reads = sorted({r for r in src.reads if len(r) <= 80})
+    body += [reads[rng.randrange(len(reads))] for _ in range(8)]
+    if src.name == "repeat":  # whole reads that the shard holds twice
+        twice = sorted({r for r in reads if src.reads.count(r) >= 2})
+        body += [twice[rng.randrange(len(twice))] for _ in range(6)]
+    if src.name == "ragged":  # from the inside of the reads of 256 to 600 symbols: the kept reads include those
+        for r in sorted(fx.longs, key=len)[::4]:
+            at = rng.randrange(20, len(r) - 90)
+            body.append(r[at:at + rng.randint(40, 70)])
+    body = [(w, _gt_pos(rng, i, len(w))) for i, w in enumerate(body)]
+    w = fx.sources[0][200:280]
+    body += [(GT_SHORT, 1), (w[:40] + "N" + w[41:], 40), (w[:10] + "N" + w[11:50] + "N" + w[51:], 1)]
+    return body
+
+
+_GT_QUERIES = {}
+
+
+def gt_queries(src, batch="small"):
+    """[(w, pos)]: the batch of SiteMatch queries of a source, runs of empty queries at its start, middle and end"""
+    assert batch == "small", batch
+    if src.name not in _GT_QUERIES:
+        body = (_gt_read_queries if src.reads is not None else _gt_stream_queries)(src)
+        random.Random(f"gt/{src.name}/{batch}/order").shuffle(body)
+        mid = len(body) // 2
+        _GT_QUERIES[src.name] = [("", 0)] * 3 + body[:mid] + [("", 0)] * 3 + body[mid:] + [("", 0)] * 4
+    return _GT_QUERIES[src.name]
+
+
+class LegsOnly:
+    """a run stream's side of gt_reference: the oracle's intervals, and rows without reads -- a stream that is no BWT of
+    reads has no read to extract (a walk need not meet '$'), and only its legs are compared"""
+
+    def __init__(self, orc):
+        self.orc = orc
+        self.find = orc.find
+
+    def extract(self, row):
+        return "", ""
+
+    def identity(self, row):
+        return row
+
+
+def gt_side(src, legs_only=False):
+    return LegsOnly(src.orc) if legs_only or src.reads is None else src.orc
+
+
+def gt_expected(srcs, key, qs, k, skip, M, count=None, legs_only=False):
+    """[query][shard] -> gt_reference.gt_query's (legs, reads) over the sources' oracle sides, once per key and triple; a run
+    stream's reads, and every shard's with legs_only, are meaningless (LegsOnly)"""
+    per = [G.expected([gt_side(s, legs_only)], ("gt", s.name, key, legs_only or s.reads is None), qs, k, skip, M, count) for s in srcs]
+    return [[per[p][q][0] for p in range(len(srcs))] for q in range(len(qs))]
+
+
+_GT_GROWN, _FIND_STEPS = {}, {}
+
+
+def gt_grown(src, qs, k, skip, M):
+    """the lengthenings of every query in this shard: [q] -> [(tile, leg, "L" or "R", a, b)]"""
+    at = (src.name, tuple(qs), k, skip, M)
+    if at not in _GT_GROWN:
+        out = []
+        for w, pos in qs:
+            grown = []
+            G.gt_query(gt_side(src), w, pos, k, skip, M, None, grown)
+            out.append(grown)
+        _GT_GROWN[at] = out
+    return _GT_GROWN[at]
+
+
+def find_steps(src, x):
+    """the LF steps findInterval(x) takes in the oracle"""
+    if (src.name, x) not in _FIND_STEPS:
+        st = src.orc.oix.find_intervals(np.frombuffer(x.encode(), np.uint8).reshape(1, -1), want_steps=True)[2]
+        _FIND_STEPS[(src.name, x)] = int(st[0])
+    return _FIND_STEPS[(src.name, x)]
+
+
+def gt_narrow_steps(src, qs, k, skip, M):
+    """the LF steps the lengthenings cost without a table, from the definition -- a left lengthening is one more step from
+    an interval that is wide, hence proper (none if the symbol taken in is outside ACGT); a right lengthening is a fresh
+    search of the longer string (none if it holds a symbol outside ACGT); the tile's own search is not counted"""
+    steps = 0
+    for (w, _), grown in zip(qs, gt_grown(src, qs, k, skip, M)):
+        for _, _, side, a, b in grown:
+            if side == "L":
+                steps += int(w[a] in ACGT)
+            elif not set(w[a:b]) - set(ACGT):
+                steps += find_steps(src, w[a:b])
+    return steps
+
+
+def gt_right_lengthenings(src, qs, k, skip, M, depth):
+    """the right lengthenings whose string has `depth` symbols or more, all of them ACGT: each may start from a table of
+    that depth, which saves depth - 1 steps at the most"""
+    return sum(1 for (w, _), grown in zip(qs, gt_grown(src, qs, k, skip, M)) for _, _, side, a, b in grown
+               if side == "R" and b - a >= depth and not set(w[a:b]) - set(ACGT))
 
 
 class ScanCounts(M.PlainCounts):

@@ -693,6 +693,63 @@ int rsbwt_set_overlap_reads(rsbwt_set_t *s, const char *text, const uint64_t *of
                             uint64_t max_reads, uint64_t *first, char *reads, uint32_t read_stride, uint32_t *read_len, uint32_t *overlap,
                             uint64_t *ordinal, size_t cap_reads, size_t *nreads, uint64_t *matches);
 void rsbwt_set_overlap_last_work(uint64_t *work6);
+/* Extensions and walks: "what do the reads say comes next?" -- local assembly round a k-mer, the haplotypes either side of a
+ * site, the gap between two anchors.  Queries (seeds) arrive as in the _var calls: text, off[Q + 1].
+ *   ctx    the context length, 1 <= ctx <= 255
+ *   flags  bit 0 RSBWT_WALK_LEFT: walk to the left; bit 1 RSBWT_WALK_BOTH_STRANDS: count the reverse complement too
+ * W_p(x) = the rows of findInterval(x) in shard p by this header's rule (lower <= upper && upper < bwlen ? upper - lower + 1
+ * : 0), so the wrapped (0, 2^64-1) counts 0; rc(x) = the reverse complement of x.  For a string s with |s| >= ctx whose
+ * context is all ACGT the four CANDIDATES are
+ *   x_c = s[-ctx:] + c   walking right
+ *   x_c = c + s[:ctx]    walking left          c = A, C, G, T in that order
+ * the EXTENSION COUNT is E_p(s, c) = W_p(x_c), plus W_p(rc(x_c)) with both strands, and the SUPPORT is sup(s, c) = the sum of
+ * E_p(s, c) over every shard of the set.  A seed shorter than ctx, or with a symbol outside ACGT in its context (the ctx
+ * symbols a candidate holds: an N elsewhere does not matter), is INVALID: its counts are all 0.
+ *   rsbwt_set_extensions  counts u64[S][Q][4]: counts[(p*Q + q)*4 + c] = E_p(query q, c).  The one-step primitive; any set,
+ *                         device groups side by side like the other set calls.
+ *   rsbwt_extensions      one handle = a set of one: counts u64[Q][4]
+ *   rsbwt_set_walk        walks every seed: m = max(min_count, 1); s = seed; repeat
+ *                           1. max_steps symbols appended: stop with RSBWT_WALK_LIMIT
+ *                           2. evaluate the four supports;  live = {c : sup(s, c) >= m}
+ *                           3. live empty: stop with RSBWT_WALK_DEAD_END;  two or more: stop with RSBWT_WALK_BRANCH
+ *                           4. else append the one live symbol to s on the walking side and note its support
+ *                         An invalid seed stops with RSBWT_WALK_INVALID at 0 steps.
+ *                           ext      char[Q][max_steps]: the appended symbols in the order they were appended (a left walk's
+ *                                    sequence is reverse(ext) + seed); bytes past steps[q] are 0
+ *                           steps    u32[Q]
+ *                           stop     u8[Q], one of RSBWT_WALK_*; 0 is never written
+ *                           support  u32[Q][max_steps], may be NULL: the support of each appended symbol, saturated at
+ *                                    2^32 - 1; 0 past steps[q]
+ *                           last     u64[Q][4], may be NULL: the four supports of the evaluation that stopped the walk,
+ *                                    zeros for LIMIT and INVALID
+ *                         On a set on one device the whole walk is ONE launch; over several device groups each group
+ *                         evaluates one step of the seeds still walking (rsbwt_set_extensions' kernel), the host sums,
+ *                         applies the rule and goes again: the same outputs, one round trip per step.
+ *   rsbwt_set_walk_dev    a set on ONE device (several: RSBWT_EINVAL); d_text, d_off (u64[Q + 1], d_off[0] = 0, d_off[Q] = N)
+ *                         and the outputs in HBM (d_support, d_last may be NULL); every byte of every output is written;
+ *                         enqueues on `stream`, synchronises nothing
+ * Q = 0 succeeds and touches nothing.  ctx outside 1..255, max_steps 0 or above 65,535 and unknown flag bits are RSBWT_EINVAL;
+ * Q x max_steps >= 2^31 is RSBWT_ERANGE; no device RSBWT_ENODEV.  No call needs RSBWT_OPEN_READS or a k-mer table; they build
+ * nothing and write nothing a search reads, and are re-entrant like the other set calls.  A candidate's search may start from
+ * the shard's k-mer table entry of its last T symbols when T >= 2 and ctx + 1 >= T (a refused entry starts over from
+ * initInterval): same answers with any table or none.  A search ends at the step that empties it and looks at nothing past
+ * that step.
+ * rsbwt_set_walk_last_work: the calling thread's last host-buffer walk or extensions call: {seeds, appended symbols,
+ * candidate searches, LF steps, lane-passes that fetched a line, starts from a k-mer table entry}. */
+#define RSBWT_WALK_LEFT 1u
+#define RSBWT_WALK_BOTH_STRANDS 2u
+#define RSBWT_WALK_DEAD_END 1
+#define RSBWT_WALK_BRANCH 2
+#define RSBWT_WALK_LIMIT 3
+#define RSBWT_WALK_INVALID 4
+int rsbwt_set_extensions(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint32_t flags, uint64_t *counts);
+int rsbwt_extensions(rsbwt_t *h, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint32_t flags, uint64_t *counts);
+int rsbwt_set_walk(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint64_t min_count, uint32_t max_steps,
+                   uint32_t flags, char *ext, uint32_t *steps, uint8_t *stop, uint32_t *support, uint64_t *last);
+int rsbwt_set_walk_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, size_t N, uint32_t ctx, uint64_t min_count,
+                       uint32_t max_steps, uint32_t flags, void *d_ext, void *d_steps, void *d_stop, void *d_support, void *d_last,
+                       void *stream);
+void rsbwt_set_walk_last_work(uint64_t *work6);
 /* The per-read sample table: "which samples carry this read".  Replaces, for the return types All and Samples, the
  * RocksDB lookups of the reference -- sdb->Get(read, &value) in QueryTask::run (src/service/service.cpp:1292-1348), KmerTask::run
  * (:917-975) and DbTask::run (:816-845) -- by a table in HBM keyed by the read's ordinal: per shard off u64[num_strings + 1]

@@ -208,6 +208,12 @@ SIGNATURES = {
     "rsbwt_set_overlap_reads": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, _vp, _vp, _vp,
                                           C.c_size_t, C.POINTER(C.c_size_t), _vp]),
     "rsbwt_set_overlap_last_work": (None, [_u64p]),
+    "rsbwt_set_extensions": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, C.c_uint32, _vp]),
+    "rsbwt_extensions": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, C.c_uint32, _vp]),
+    "rsbwt_set_walk": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "rsbwt_set_walk_dev": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp,
+                                     _vp, _vp]),
+    "rsbwt_set_walk_last_work": (None, [_u64p]),
     "rsbwt_service_kmer_requests": (C.c_uint64, [_vp]),
     "rsbwt_set_meta_build": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "rsbwt_set_meta_load": (C.c_int, [_vp, C.c_char_p, _vp]),

@@ -21,6 +21,14 @@ def _ptr(a):
     return C.c_void_p(a.ctypes.data)
 
 
+# rsbwt_set_walk's stop codes and the flag word of the walk / extension calls (include/rsbwt.h)
+WALK_DEAD_END, WALK_BRANCH, WALK_LIMIT, WALK_INVALID = 1, 2, 3, 4
+
+
+def _walk_flags(left, both_strands):
+    return (1 if left else 0) | (2 if both_strands else 0)
+
+
 def _kmer_matrix(kmers):
     """list of equal-length str/bytes, or a (Q, k) uint8 array -> (contiguous uint8 (Q, k), k)."""
     if isinstance(kmers, np.ndarray):
@@ -212,6 +220,16 @@ class GpuBWT:
         check(lib().rsbwt_overlaps(self.handle, _ptr(text), _ptr(off), len(queries), min_overlap, max_overlap, _ptr(cnt),
                                    _ptr(od) if ordinals else None))
         return (cnt, od) if ordinals else cnt
+
+    def extensions(self, queries, ctx, left=False, both_strands=False):
+        """Extension counts of this shard (rsbwt_extensions): a uint64 array of shape (Q, 4) -- the rows of the query's
+        context of ctx symbols with A, C, G, T put behind it (left=True: in front of it), the reverse complement's rows
+        added with both_strands; zeros for a query shorter than ctx or with a symbol outside ACGT in its context.
+        ShardSet.walk_last_work() tells the work."""
+        text, off = ShardSet._var_text(queries)
+        cnt = np.zeros((len(queries), 4), np.uint64)
+        check(lib().rsbwt_extensions(self.handle, _ptr(text), _ptr(off), len(queries), ctx, _walk_flags(left, both_strands), _ptr(cnt)))
+        return cnt
 
     @property
     def exactmatch_by_search(self):
@@ -749,6 +767,46 @@ class ShardSet:
         w = np.zeros(6, np.uint64)
         lib().rsbwt_set_overlap_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
         return dict(zip(("items", "lf_steps", "passes", "table_starts", "dollar_only_passes", "entries"), (int(x) for x in w)))
+
+    # -- extension counts and walks (csrc/walk.hip): rsbwt_set_extensions / rsbwt_set_walk
+    def extensions(self, queries, ctx, left=False, both_strands=False):
+        """counts of shape (shards, Q, 4): counts[p, q, c] = the rows in shard p of query q's context of ctx symbols with
+        "ACGT"[c] put behind it (left=True: in front of it), the reverse complement's rows added with both_strands; zeros
+        for a query shorter than ctx or with a symbol outside ACGT in its context (rsbwt_set_extensions)"""
+        text, off = self._var_text(queries)
+        cnt = np.zeros((len(self.shards), len(queries), 4), np.uint64)
+        check(lib().rsbwt_set_extensions(self._s, _ptr(text), _ptr(off), len(queries), ctx, _walk_flags(left, both_strands), _ptr(cnt)))
+        return cnt
+
+    def walk(self, seeds, ctx, min_count=1, max_steps=256, left=False, both_strands=False, supports=False):
+        """Walks every seed through the reads' k-mer graph (rsbwt_set_walk): while exactly one of the four extensions of
+        the seed's context has a support -- its count summed over every shard -- of max(min_count, 1) or more, that symbol
+        is appended (left=True: put in front).  Returns a list of (ext, stop, last) per seed: ext the appended symbols in
+        the order they were appended (a left walk's sequence is ext[::-1] + seed), stop one of WALK_DEAD_END, WALK_BRANCH,
+        WALK_LIMIT (max_steps symbols appended), WALK_INVALID (a seed shorter than ctx or with a symbol outside ACGT in its
+        context), last the four supports of the evaluation that stopped the walk (zeros for LIMIT and INVALID);
+        supports=True: (ext, stop, last, support) with the support of every appended symbol (saturated at 2^32 - 1)."""
+        text, off = self._var_text(seeds)
+        Q = len(seeds)
+        ext = np.zeros((Q, max_steps), np.uint8)
+        steps, stop = np.zeros(Q, np.uint32), np.zeros(Q, np.uint8)
+        sup = np.zeros((Q, max_steps), np.uint32) if supports else None
+        last = np.zeros((Q, 4), np.uint64)
+        check(lib().rsbwt_set_walk(self._s, _ptr(text), _ptr(off), Q, ctx, min_count, max_steps, _walk_flags(left, both_strands), _ptr(ext),
+                                   _ptr(steps), _ptr(stop), _ptr(sup) if supports else None, _ptr(last)))
+        out = []
+        for q in range(Q):
+            n = int(steps[q])
+            one = (ext[q, :n].tobytes().decode(), int(stop[q]), tuple(int(x) for x in last[q]))
+            out.append(one + (tuple(int(x) for x in sup[q, :n]),) if supports else one)
+        return out
+
+    @staticmethod
+    def walk_last_work():
+        """{seeds, appended, searches, lf_steps, passes, table_starts} of this thread's last walk or extensions call"""
+        w = np.zeros(6, np.uint64)
+        lib().rsbwt_set_walk_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return dict(zip(("seeds", "appended", "searches", "lf_steps", "passes", "table_starts"), (int(x) for x in w)))
 
     # -- the per-read sample table (csrc/read_meta.hip): rsbwt_set_meta_* / rsbwt_set_read_meta_var
     @staticmethod

@@ -2006,6 +2006,37 @@ int rsbwt_overlaps(rsbwt_t *h, const char *text, const uint64_t *off, size_t Q, 
     });
 }
 
+// ---- extension counts (walk.hip): one handle = a set of one ------------------------------------
+
+int rsbwt_extensions(rsbwt_t *h, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint32_t flags, uint64_t *counts) {
+    return guarded("rsbwt_extensions", [&]() -> int {
+        walk_set_last_work(nullptr);
+        if (!h && rsbwt_device_count() == 0) return fail(RSBWT_ENODEV, "no HIP device is visible: the popBWT engine has no CPU fallback");
+        if (!h) return fail(RSBWT_EINVAL, "null handle");
+        int rc = walk_check_args(ctx, flags, nullptr, Q);
+        if (rc) return rc;
+        std::vector<uint64_t> rel;
+        size_t N = 0;
+        if ((rc = match_check_batch(text, off, Q, &rel, &N)) != RSBWT_OK) return rc;
+        if (Q == 0) return RSBWT_OK;
+        if (!counts) return fail(RSBWT_EINVAL, "null argument");
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index");
+        if ((rc = use_device(h->device)) != RSBWT_OK) return rc;
+        call_ctx *c = h->pool.acquire();
+        if (!c) return fail(RSBWT_EHIP, "cannot create a HIP stream");
+        struct release_t {
+            rsbwt_t *h;
+            call_ctx *c;
+            ~release_t() { h->pool.release(c); }
+        } release{h, c};
+        uint64_t work6[6] = {Q, 0, 0, 0, 0, 0};
+        rc = extension_host_views(h->scratch, c->st[0], h->d_view, 1, N ? text + off[0] : nullptr, rel.data(), Q, N, ctx, flags, counts, work6);
+        if (rc) return rc;
+        walk_set_last_work(work6);
+        return RSBWT_OK;
+    });
+}
+
 // ---- synthetic data ---------------------------------------------------------------------------
 
 int rsbwt_synth_runs_dev(void *d_runs, uint64_t num_runs, uint64_t seed, int device, void *stream) {

@@ -139,6 +139,21 @@ int overlap_host_views(scratch_cache &scratch, hipStream_t st, const shard_view 
                        size_t N, uint32_t min_overlap, uint32_t max_overlap, uint64_t *pairs, std::vector<rsbwt_overlap> *recs, uint64_t *work5);
 void overlap_set_last_work(const uint64_t work6[6]);
 void overlap_get_last_work(uint64_t work6[6]);
+// walk.hip: what the host-buffer extension and walk calls share (capi.hip: one handle; sets.hip: a set); batches are
+// checked by match_check_batch and walk_check_args (ctx, flags and -- where max_steps is given -- max_steps and Q x max_steps).
+//   extension_host_views  one device's share on `st` (synchronised before it returns): counts u64[S][Q][4]; work6[2..5] += the
+//                         launch's counters
+//   walk_host_views       a whole walk call on one device on `st` (synchronised before it returns): support and last are
+//                         optional; work6[1..5] += the launch's counters
+//   walk_set / get_last_work: what rsbwt_set_walk_last_work reports for the calling thread
+int walk_check_args(uint32_t ctx, uint32_t flags, const uint32_t *max_steps, size_t Q);
+int extension_host_views(scratch_cache &scratch, hipStream_t st, const shard_view *d_views, uint32_t S, const char *t0, const uint64_t *rel, size_t Q,
+                         size_t N, uint32_t ctx, uint32_t flags, uint64_t *counts, uint64_t *work6);
+int walk_host_views(scratch_cache &scratch, hipStream_t st, const shard_view *d_views, uint32_t S, const char *t0, const uint64_t *rel, size_t Q,
+                    size_t N, uint32_t ctx, uint64_t min_count, uint32_t max_steps, uint32_t flags, char *ext, uint32_t *steps, uint8_t *stop,
+                    uint32_t *support, uint64_t *last, uint64_t *work6);
+void walk_set_last_work(const uint64_t work6[6]);
+void walk_get_last_work(uint64_t work6[6]);
 // 1-mismatch hit list of one shard from variants expanded once for the whole batch (sets.hip: every shard of a set
 // searches the same variants)
 size_t variants_bytes(size_t m, uint32_t k);

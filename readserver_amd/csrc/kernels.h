@@ -390,6 +390,26 @@ hipError_t launch_overlaps(const shard_view *d_shards, uint32_t nshards, const o
                            unsigned long long *d_work, hipStream_t stream);
 hipError_t launch_overlap_records(uint32_t nshards, const overlap_batch &bt, const void *d_pairs, const void *d_ivals, void *d_out,
                                   uint64_t cap_records, unsigned long long *d_counter, hipStream_t stream);
+// walk.hip: extension counts and walks (include/rsbwt.h: the definition).  A batch is its seeds' text back to back and
+// where each starts, as a match_batch's, all in HBM.
+struct walk_batch {
+    const char *text;
+    const uint64_t *off;  // [Q + 1]
+    size_t Q, N;
+    uint32_t ctx;        // 1..255
+    uint32_t max_steps;  // >= 1 (launch_extensions does not look at it)
+    uint64_t min_count;  // >= 1 (launch_extensions does not look at it)
+    uint32_t flags;      // RSBWT_WALK_LEFT | RSBWT_WALK_BOTH_STRANDS
+};
+//   launch_walk: a workgroup per 8 seeds walks them over all nshards shards: d_ext char[Q][max_steps] and d_support
+//     u32[Q][max_steps] (optional) are zeroed on `stream` and the appended symbols written; d_steps u32[Q], d_stop u8[Q]
+//     and d_last u64[Q][4] (optional) are written for every seed; d_work (optional, zeroed by the caller) [1..5] +=
+//     appended symbols, candidate searches, LF steps, lane-passes that fetched a line, starts from the k-mer table
+//   launch_extensions: a wave per (8 seeds, shard): d_counts u64[nshards][Q][4], every entry written; d_work [2..5] as above
+hipError_t launch_walk(const shard_view *d_shards, uint32_t nshards, const walk_batch &bt, void *d_ext, void *d_steps, void *d_stop, void *d_support,
+                       void *d_last, unsigned long long *d_work, hipStream_t stream);
+hipError_t launch_extensions(const shard_view *d_shards, uint32_t nshards, const walk_batch &bt, void *d_counts, unsigned long long *d_work,
+                             hipStream_t stream);
 // (SEL_SHIFT, sample_window, window_samples, window_psi_hint: line_format.h -- shared with the host-side layout test)
 // query / query_exactmatch (query.cpp:87-120) over extracted reads
 hipError_t launch_match_reads(const void *d_reads, const void *d_len, size_t n, uint32_t stride, const void *d_owner,

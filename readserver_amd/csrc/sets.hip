@@ -2337,6 +2337,205 @@ void rsbwt_set_overlap_last_work(uint64_t *work6) {
     if (work6) overlap_get_last_work(work6);
 }
 
+// ---- extension counts and walks (walk.hip): what the reads say comes next, over every shard ----
+namespace {
+int walk_set_check(rsbwt_set_t *s) {
+    // (no set can be had on a box without a GPU: the call says so instead of blaming the argument)
+    if (!s && rsbwt_device_count() == 0) return fail(RSBWT_ENODEV, "no HIP device is visible: the popBWT engine has no CPU fallback");
+    if (!s) return fail(RSBWT_EINVAL, "null set");
+    for (rsbwt_t *h : s->shards)
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
+    return RSBWT_OK;
+}
+
+// One evaluation of every seed in every shard: each device group counts its shards' rows of counts[S][Q][4], side by
+// side; the host only puts group gi's row j at row idx[j].  work6[2..5] += the launches' counters.
+int extension_groups(rsbwt_set_t *s, const char *t0, const uint64_t *rel, size_t Q, size_t N, uint32_t ctx, uint32_t flags, uint64_t *counts,
+                     uint64_t *work6) {
+    struct group_out {
+        std::vector<uint64_t> counts;
+        uint64_t work[6] = {0, 0, 0, 0, 0, 0};
+    };
+    std::vector<group_out> outs(s->groups.size());
+    const size_t row = Q * 4;
+    int rc = for_each_group(s, [&](size_t gi) -> int {
+        dev_group *g = s->groups[gi];
+        group_call gc(g);
+        if (gc.rc) return gc.rc;
+        group_out &o = outs[gi];
+        const size_t Sg = g->idx.size();
+        // (a group whose shards sit next to each other in the set answers straight into the caller's rows)
+        uint64_t *dst = counts + g->idx.front() * row;
+        if (g->idx.back() - g->idx.front() + 1 != Sg) {
+            o.counts.resize(Sg * row);
+            dst = o.counts.data();
+        }
+        return extension_host_views(g->scratch, gc.st, g->d_views, (uint32_t)Sg, t0, rel, Q, N, ctx, flags, dst, o.work);
+    });
+    if (rc) return rc;
+    for (size_t gi = 0; gi < outs.size(); ++gi) {
+        const dev_group *g = s->groups[gi];
+        const group_out &o = outs[gi];
+        for (size_t j = 0; !o.counts.empty() && j < g->idx.size(); ++j) memcpy(counts + g->idx[j] * row, o.counts.data() + j * row, row * 8);
+        for (int i = 2; i < 6; ++i) work6[i] += o.work[i];
+    }
+    return RSBWT_OK;
+}
+
+// The walk of a set over several device groups: per step the groups evaluate the seeds still walking (their contexts
+// alone are sent), the host sums over the shards, applies the rule and goes again -- walk_kernel's decision, on the host.
+int walk_by_steps(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint64_t m, uint32_t max_steps, uint32_t flags,
+                  char *ext, uint32_t *steps, uint8_t *stop, uint32_t *support, uint64_t *last, uint64_t *work6) {
+    const bool left = (flags & RSBWT_WALK_LEFT) != 0u;
+    const size_t S = s->shards.size();
+    memset(ext, 0, Q * (size_t)max_steps);
+    if (support) memset(support, 0, Q * (size_t)max_steps * 4);
+    std::vector<std::string> cur(Q);
+    std::vector<size_t> live;
+    for (size_t q = 0; q < Q; ++q) {
+        const uint64_t Lq = off[q + 1] - off[q];
+        bool valid = Lq >= ctx;
+        if (valid) {
+            cur[q].assign(left ? text + off[q] : text + off[q + 1] - ctx, ctx);
+            for (char ch : cur[q]) valid = valid && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
+        }
+        steps[q] = 0;
+        stop[q] = valid ? 0 : (uint8_t)RSBWT_WALK_INVALID;
+        if (last)
+            for (int c = 0; c < 4; ++c) last[4 * q + c] = 0;
+        if (valid) live.push_back(q);
+    }
+    std::string t;
+    std::vector<uint64_t> rel, counts;
+    while (!live.empty()) {  // (every seed of `live` has fewer than max_steps symbols appended)
+        const size_t nl = live.size();
+        t.clear();
+        rel.resize(nl + 1);
+        for (size_t i = 0; i < nl; ++i) {
+            rel[i] = (uint64_t)i * ctx;
+            t += cur[live[i]];
+        }
+        rel[nl] = (uint64_t)nl * ctx;
+        if (rel[nl] >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu seeds x %u context symbols: under 2^31 in one call", nl, ctx);
+        counts.assign(S * nl * 4, 0);
+        const int rc = extension_groups(s, t.data(), rel.data(), nl, (size_t)rel[nl], ctx, flags, counts.data(), work6);
+        if (rc) return rc;
+        std::vector<size_t> next;
+        for (size_t i = 0; i < nl; ++i) {
+            const size_t q = live[i];
+            uint64_t sup[4] = {0, 0, 0, 0};
+            uint32_t nlive = 0, pick = 0;
+            for (uint32_t c = 0; c < 4; ++c) {
+                for (size_t p = 0; p < S; ++p) sup[c] += counts[(p * nl + i) * 4 + c];
+                if (sup[c] >= m) {
+                    ++nlive;
+                    pick = c;
+                }
+            }
+            uint32_t why = 0;
+            if (nlive == 1) {
+                const size_t at = q * (size_t)max_steps + steps[q];
+                ext[at] = "ACGT"[pick];
+                if (support) support[at] = sup[pick] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)sup[pick];
+                work6[1] += 1;
+                if (left) cur[q] = std::string(1, "ACGT"[pick]) + cur[q].substr(0, ctx - 1);
+                else cur[q] = cur[q].substr(1) + "ACGT"[pick];
+                if (++steps[q] == max_steps) why = RSBWT_WALK_LIMIT;
+            } else {
+                why = nlive == 0 ? RSBWT_WALK_DEAD_END : RSBWT_WALK_BRANCH;
+            }
+            if (why == 0) {
+                next.push_back(q);
+                continue;
+            }
+            stop[q] = (uint8_t)why;
+            if (last && why != RSBWT_WALK_LIMIT)
+                for (int c = 0; c < 4; ++c) last[4 * q + c] = sup[c];
+        }
+        live.swap(next);
+    }
+    return RSBWT_OK;
+}
+}  // namespace
+
+int rsbwt_set_extensions(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint32_t flags, uint64_t *counts) {
+    return guarded("rsbwt_set_extensions", [&]() -> int {
+        walk_set_last_work(nullptr);
+        int rc = walk_set_check(s);
+        if (rc) return rc;
+        if ((rc = walk_check_args(ctx, flags, nullptr, Q)) != RSBWT_OK) return rc;
+        std::vector<uint64_t> rel;
+        size_t N = 0;
+        if ((rc = match_check_batch(text, off, Q, &rel, &N)) != RSBWT_OK) return rc;
+        if (Q == 0) return RSBWT_OK;
+        if (!counts) return fail(RSBWT_EINVAL, "null argument");
+        uint64_t work6[6] = {Q, 0, 0, 0, 0, 0};
+        rc = extension_groups(s, N ? text + off[0] : nullptr, rel.data(), Q, N, ctx, flags, counts, work6);
+        if (rc) return rc;
+        walk_set_last_work(work6);
+        return RSBWT_OK;
+    });
+}
+
+int rsbwt_set_walk(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint64_t min_count, uint32_t max_steps,
+                   uint32_t flags, char *ext, uint32_t *steps, uint8_t *stop, uint32_t *support, uint64_t *last) {
+    return guarded("rsbwt_set_walk", [&]() -> int {
+        walk_set_last_work(nullptr);
+        int rc = walk_set_check(s);
+        if (rc) return rc;
+        if ((rc = walk_check_args(ctx, flags, &max_steps, Q)) != RSBWT_OK) return rc;
+        std::vector<uint64_t> rel;
+        size_t N = 0;
+        if ((rc = match_check_batch(text, off, Q, &rel, &N)) != RSBWT_OK) return rc;
+        if (Q == 0) return RSBWT_OK;
+        if (!ext || !steps || !stop) return fail(RSBWT_EINVAL, "null argument");
+        const uint64_t m = min_count ? min_count : 1ull;
+        const char *t0 = N ? text + off[0] : nullptr;
+        uint64_t work6[6] = {Q, 0, 0, 0, 0, 0};
+        if (s->groups.size() == 1) {  // the whole walk in one launch
+            dev_group *g = s->groups[0];
+            group_call gc(g);
+            if (gc.rc) return gc.rc;
+            rc = walk_host_views(g->scratch, gc.st, g->d_views, (uint32_t)g->idx.size(), t0, rel.data(), Q, N, ctx, m, max_steps, flags, ext, steps,
+                                 stop, support, last, work6);
+        } else {
+            rc = walk_by_steps(s, t0, rel.data(), Q, ctx, m, max_steps, flags, ext, steps, stop, support, last, work6);
+        }
+        if (rc) return rc;
+        walk_set_last_work(work6);
+        return RSBWT_OK;
+    });
+}
+
+int rsbwt_set_walk_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, size_t N, uint32_t ctx, uint64_t min_count,
+                       uint32_t max_steps, uint32_t flags, void *d_ext, void *d_steps, void *d_stop, void *d_support, void *d_last,
+                       void *stream) {
+    dev_group *g = nullptr;
+    int rc = one_device_group(s, &g);
+    if (rc) return rc;
+    if ((rc = walk_check_args(ctx, flags, &max_steps, Q)) != RSBWT_OK) return rc;
+    if (Q == 0) return RSBWT_OK;
+    if (!d_text || !d_off || !d_ext || !d_steps || !d_stop) return fail(RSBWT_EINVAL, "null argument");
+    if (N >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu positions in one call: at most 2^31 - 1", N);
+    for (rsbwt_t *h : s->shards)
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
+    walk_batch bt;
+    bt.text = (const char *)d_text;
+    bt.off = (const uint64_t *)d_off;
+    bt.Q = Q;
+    bt.N = N;
+    bt.ctx = ctx;
+    bt.max_steps = max_steps;
+    bt.min_count = min_count ? min_count : 1ull;
+    bt.flags = flags;
+    const hipError_t e = launch_walk(g->d_views, (uint32_t)g->idx.size(), bt, d_ext, d_steps, d_stop, d_support, d_last, nullptr, (hipStream_t)stream);
+    return e == hipSuccess ? RSBWT_OK : fail_hip(e, "walk kernel launch");
+}
+
+void rsbwt_set_walk_last_work(uint64_t *work6) {
+    if (work6) walk_get_last_work(work6);
+}
+
 static size_t hits_1mm_scratch_one(const rsbwt_set_t *s, size_t m, uint32_t k) {
     size_t need = 0;
     for (rsbwt_t *h : s->shards) need = std::max(need, rsbwt_hits_1mm_scratch_bytes(h, m, k));

@@ -587,6 +587,89 @@ int rsbwt_set_gt_reads(rsbwt_set_t *s, const char *text, const uint64_t *off, si
 int rsbwt_set_gt_count(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, int32_t k, int32_t skip,
                        uint64_t M, uint64_t *counts);
 void rsbwt_set_gt_last_work(uint64_t *work6);
+/* SiteMatch alignment: ksw_align of the reference's src/service/ksw.c as align_gt_read calls it (src/service/service.cpp:134:
+ * KSW_XSTART, no KSW_XBYTE, so the 16-bit striped path ksw_i16) and align_gt_read itself (:105-225), the second half of
+ * GtTask::run (:1077-1108), one GPU lane per (read, target) item.  Symbols are ASCII, coded on the device by seq_nt4_table:
+ * ACGTacgt -> 0..3, anything else 4.  s(a, b) = -ambiguous where either code is 4, else +match or -mismatch.
+ * One PASS P(q, t, endsc) over columns i = 0 .. tlen-1 and rows j = 0 .. qlen-1, all values >= 0, borders 0:
+ *   H[i][j]   = max(0, H[i-1][j-1] + s(t[i], q[j]), E[i][j], F[i][j])
+ *   E[i+1][j] = max(E[i][j] - gape, H[i][j] - (gapo + gape))      F[i][j+1] = max(F[i][j] - gape, H[i][j] - (gapo + gape))
+ * (subtractions floored at 0); te = the last column whose maximum rose above every earlier column's, score = that
+ * maximum; the pass stops after the column at which it reaches endsc; qe = the row of the maximum in column te, ties to
+ * the smallest (j mod slen, j div slen) with slen = (qlen + 7) / 8 -- the order ksw.c:307-308 scans its striped vectors
+ * in.  Nothing scores: score 0, te -1, qe 0.  ksw_align is two passes: r = P(q, t, never); rr = P(reverse(q[0..qe]), t',
+ * r.score) with t' = t, its first te + 1 symbols reversed (all tlen columns stay); tb = te - rr.te and qb = qe - rr.qe
+ * when rr.score == r.score, else both -1.  score2 / te2 are not produced (the service never reads them).
+ *   rsbwt_ksw_align      pair i = qtext[qoff[i] .. qoff[i+1]) on the rows against ttext[toff[i] .. toff[i+1]) on the columns;
+ *                        out[i] = {score, te, qe, tb, qb, 0}.  p = NULL: the service's 1, 4, 1, 6, 1; each parameter in
+ *                        1..127 and each length in 1..4,096, else RSBWT_EINVAL.  A pair with match * min(qlen, tlen) >= 2^15
+ *                        is RSBWT_ERANGE: the reference's 16-bit lanes saturate there, this library's packed column would
+ *                        overflow.  n = 0 succeeds and touches nothing.  The items are ordered by length on the host so
+ *                        that a wave's lanes finish together; out is in the caller's order.
+ *   rsbwt_ksw_align_dev  the same with every array in HBM (d_qoff / d_toff u64[n + 1]); writes every byte of d_out, enqueues
+ *                        on `stream` and synchronises nothing, so it cannot refuse a length: a pair outside the rules above
+ *                        gets all five fields -1.  Items are taken in the caller's order.
+ * A lane's column lives in LDS while its longest pass has at most RSBWT_KSW_LDS_ROWS rows, else in a scratch buffer in HBM
+ * (the host call sizes it by the batch; the _dev call takes it from the stream's memory pool and gives it back there).
+ *   rsbwt_gt_align       read i = reads[roff[i] .. roff[i+1]) belongs to request item[i] < Q; request q = (w = text[off[q] ..
+ *                        off[q+1]), pos[q] 1-based, alt[q], isalt[q]) as GtTask::run hands them to align_gt_read after its
+ *                        reverse-complement and window fix-up (:1028-1040).  verdict[i] = the exit align_gt_read leaves by,
+ *                        RSBWT_GT_* in source order; KEEP_PLAIN, KEEP_RIGHT and KEEP_LEFT are its `return true`.  The
+ *                        conditions are the reference's as written, the unsigned arithmetic of :158 and :196 included.
+ *                        0 is never written.
+ *   rsbwt_gt_align_dev   the same in HBM, enqueued on `stream`, nothing synchronised; an item the host call would refuse
+ *                        gets RSBWT_GT_INVALID.
+ * Where the reference is undefined this library says what it does instead:
+ *   (a) the reference stores the raw character alt[0] into the CODED target (:126), which indexes past ksw's query
+ *       profile; here alt[q] is coded by the nt4 table like every other symbol;
+ *   (b) pos = 0 or pos > |w| writes outside the array in the reference; here it is RSBWT_GT_OFF_SITE for every read of
+ *       the request;
+ *   (c) a read or w outside 1..4,096 symbols, or item[i] >= Q, is RSBWT_EINVAL.
+ *   rsbwt_set_gt_aligned_reads  exactly rsbwt_set_gt_reads' reads for (q, p), in its order, cut down to those align_gt_read
+ *                               keeps against request q = (w, pos[q], alt[q], isalt[q]); same layout, same sizing protocol
+ *                               (cap_reads = 0: RSBWT_ERANGE, *nreads set).  The alignment runs on the device of the shard
+ *                               that produced the read, device groups side by side.  A candidate read or a w longer than
+ *                               4,096 symbols is RSBWT_EINVAL.  Known host trip: the distinct reads come back from the
+ *                               extraction and go up again for the alignment.
+ *   rsbwt_set_gt_aligned_count  counts[q*S+p] = how many reads that is.
+ * rsbwt_gt_align_last_work: the calling thread's last host-buffer verdict call (rsbwt_gt_align or a set call above):
+ * {reads aligned, reads by verdict 1..13}; a failed call leaves all 14 zero.  NULL is harmless. */
+#define RSBWT_KSW_LDS_ROWS 224
+#define RSBWT_KSW_MAX_LEN 4096
+#define RSBWT_GT_ALT_NOT_BETTER 1 /* looking for alt, ra.score >= r.score   :138 */
+#define RSBWT_GT_REF_WORSE 2      /* looking for ref, r.score < ra.score    :143 */
+#define RSBWT_GT_OFF_SITE 3       /* site outside [tb, te]                  :150 */
+#define RSBWT_GT_UNALIGNED 4      /* more than 4 read bases unaligned       :158 */
+#define RSBWT_GT_FLOOR_PLAIN 5    /* score floor, no indel                  :163-183 */
+#define RSBWT_GT_FLOOR_INS 6      /* score floor, insertion */
+#define RSBWT_GT_FLOOR_DEL 7      /* score floor, deletion */
+#define RSBWT_GT_SITE_MISMATCH 8  /* mismatch at the site                   :190 */
+#define RSBWT_GT_KEEP_PLAIN 9     /* KEEP, no indel */
+#define RSBWT_GT_RIGHT_QB 10      /* right sub-alignment, qb != 0           :203-207 */
+#define RSBWT_GT_KEEP_RIGHT 11    /* KEEP, right sub-alignment */
+#define RSBWT_GT_LEFT_QE 12       /* left sub-alignment, qe + 1 != len      :216-220 */
+#define RSBWT_GT_KEEP_LEFT 13     /* KEEP, left sub-alignment */
+#define RSBWT_GT_INVALID 255      /* (the _dev call only) */
+typedef struct rsbwt_ksw_params {
+    int32_t match, mismatch, ambiguous, gapo, gape; /* penalties as positive numbers */
+} rsbwt_ksw_params;
+typedef struct rsbwt_ksw_result {
+    int32_t score, te, qe, tb, qb, reserved;
+} rsbwt_ksw_result;
+int rsbwt_ksw_align(int device, const rsbwt_ksw_params *p, const char *qtext, const uint64_t *qoff, const char *ttext, const uint64_t *toff,
+                    size_t n, rsbwt_ksw_result *out);
+int rsbwt_ksw_align_dev(const rsbwt_ksw_params *p, const void *d_qtext, const void *d_qoff, const void *d_ttext, const void *d_toff, size_t n,
+                        void *d_out, int device, void *stream);
+int rsbwt_gt_align(int device, const char *reads, const uint64_t *roff, const uint64_t *item, size_t n, const char *text, const uint64_t *off,
+                   const uint64_t *pos, const char *alt, const uint8_t *isalt, size_t Q, uint8_t *verdict);
+int rsbwt_gt_align_dev(const void *d_reads, const void *d_roff, const void *d_item, size_t n, const void *d_text, const void *d_off,
+                       const void *d_pos, const void *d_alt, const void *d_isalt, size_t Q, void *d_verdict, int device, void *stream);
+int rsbwt_set_gt_aligned_reads(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, const char *alt,
+                               const uint8_t *isalt, int32_t k, int32_t skip, uint64_t M, uint64_t *first, char *reads, uint32_t read_stride,
+                               uint32_t *read_len, uint64_t *read_row, size_t cap_reads, size_t *nreads);
+int rsbwt_set_gt_aligned_count(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, const char *alt,
+                               const uint8_t *isalt, int32_t k, int32_t skip, uint64_t M, uint64_t *counts);
+void rsbwt_gt_align_last_work(uint64_t *work14);
 /* Matching statistics: for every END position of a batch of queries and every shard, the longest string ending there
  * that the shard still supports, and its interval -- "how much of this sequence do the reads support, and where does the
  * support break".  Queries arrive as in the _var calls: text, off[Q + 1], N = off[Q] - off[0] positions; position t in

@@ -29,4 +29,7 @@ from .bwt import (  # noqa: F401
     check_bpi2,
     encode_all_reply,
     parse_meta_file,
+    ksw_align,
+    gt_align,
+    gt_align_last_work,
 )

@@ -196,6 +196,14 @@ SIGNATURES = {
                                      C.c_size_t, C.POINTER(C.c_size_t)]),
     "rsbwt_set_gt_count": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_int32, C.c_int32, C.c_uint64, _vp]),
     "rsbwt_set_gt_last_work": (None, [_u64p]),
+    "rsbwt_ksw_align": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "rsbwt_ksw_align_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_int, _vp]),
+    "rsbwt_gt_align": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "rsbwt_gt_align_dev": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_int, _vp]),
+    "rsbwt_set_gt_aligned_reads": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_uint64, _vp, _vp, C.c_uint32,
+                                             _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rsbwt_set_gt_aligned_count": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_uint64, _vp]),
+    "rsbwt_gt_align_last_work": (None, [_u64p]),
     "rsbwt_set_match_lengths": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, C.c_uint64, _vp, _vp, _vp]),
     "rsbwt_set_match_lengths_dev": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint64, _vp, _vp, _vp]),
     "rsbwt_set_smems": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, C.c_uint64, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),

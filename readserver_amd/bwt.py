@@ -423,6 +423,59 @@ def query_exactmatch(pBWT, w):
     return bool(query_exactmatch_batch(pBWT, [w])[0])
 
 
+# ---- SiteMatch alignment (csrc/ksw_align.hip): ksw_align of src/service/ksw.c and align_gt_read over it -----------
+
+KSW_SERVICE = (1, 4, 1, 6, 1)  # match, mismatch, ambiguous, gapo, gape: what align_gt_read aligns with
+KSW_LDS_ROWS, KSW_MAX_LEN = 224, 4096
+GT_KEEP = (9, 11, 13)          # RSBWT_GT_KEEP_PLAIN / _RIGHT / _LEFT: the exits of align_gt_read that keep the read
+
+
+def _texts(seqs):
+    bs = [s if isinstance(s, (bytes, bytearray)) else str(s).encode("latin-1") for s in seqs]
+    off = np.zeros(len(bs) + 1, np.uint64)
+    off[1:] = np.cumsum([len(b) for b in bs], dtype=np.uint64)
+    return np.frombuffer(b"".join(bs) + b"\0", np.uint8).copy(), off
+
+
+def ksw_align(pairs, params=None, device=0):
+    """pairs of (query, target) -> int32 (n, 5): score, te, qe, tb, qb of ksw_align(..., KSW_XSTART, 0) with the query on
+    the rows; params = (match, mismatch, ambiguous, gapo, gape), None = the service's (rsbwt_ksw_align)"""
+    qtext, qoff = _texts([p[0] for p in pairs])
+    ttext, toff = _texts([p[1] for p in pairs])
+    n = len(pairs)
+    out = np.zeros((max(n, 1), 6), np.int32)
+    prm = None if params is None else np.ascontiguousarray(params, np.int32)
+    if prm is not None and prm.shape != (5,):
+        raise ValueError("params: (match, mismatch, ambiguous, gapo, gape)")
+    check(lib().rsbwt_ksw_align(device, None if prm is None else _ptr(prm), _ptr(qtext), _ptr(qoff), _ptr(ttext), _ptr(toff), n, _ptr(out)))
+    return out[:n, :5].copy()
+
+
+def gt_align(reads, item, requests, device=0):
+    """verdict u8[n]: the exit of align_gt_read(read i, w, pos, alt, isalt) for requests[item[i]] = (w, pos, alt, isalt),
+    one of RSBWT_GT_* (GT_KEEP = the read stays) (rsbwt_gt_align)"""
+    rtext, roff = _texts(reads)
+    text, off = _texts([r[0] for r in requests])
+    n, Q = len(reads), len(requests)
+    pos, alt, isalt = ShardSet._gt_requests([r[0] for r in requests], [r[1] for r in requests], [r[2] for r in requests],
+                                            [1 if r[3] else 0 for r in requests])
+    it = np.ascontiguousarray(item, np.uint64)
+    if len(it) != n:
+        raise ValueError("item needs one entry per read")
+    pad = lambda a: a if len(a) else np.zeros(1, a.dtype)  # noqa: E731
+    out = np.zeros(max(n, 1), np.uint8)
+    check(lib().rsbwt_gt_align(device, _ptr(rtext), _ptr(roff), _ptr(pad(it)), n, _ptr(text), _ptr(off), _ptr(pad(pos)), _ptr(pad(alt)),
+                               _ptr(pad(isalt)), Q, _ptr(out)))
+    return out[:n].copy()
+
+
+def gt_align_last_work():
+    """{reads, by_verdict: {1..13: reads}} of this thread's last host-buffer verdict call"""
+    w = np.zeros(14, np.uint64)
+    lib().rsbwt_gt_align_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
+    return dict(reads=int(w[0]), by_verdict={v: int(w[v]) for v in range(1, 14)})
+
+
 # ---- shard sets (SURVEY 8e) -----------------------------------------------------------------
 
 class ShardSet:
@@ -651,6 +704,51 @@ class ShardSet:
         w = np.zeros(6, np.uint64)
         lib().rsbwt_set_gt_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
         return dict(zip(("legs", "no_answer", "narrow_steps", "candidates", "kept", "extracted"), (int(x) for x in w)))
+
+    # -- SiteMatch reads that align_gt_read keeps (csrc/ksw_align.hip): rsbwt_set_gt_aligned_*
+    @staticmethod
+    def _gt_requests(queries, pos, alt, isalt):
+        Q = len(queries)
+        a = np.frombuffer(b"".join((x if isinstance(x, bytes) else str(x).encode("latin-1"))[:1] or b"\0" for x in alt), np.uint8).copy()
+        if len(a) != Q or len(isalt) != Q or len(pos) != Q:
+            raise ValueError("pos, alt and isalt need one entry per query")
+        return np.ascontiguousarray(pos, np.uint64), a, np.ascontiguousarray(isalt, np.uint8)
+
+    def gt_aligned_reads(self, queries, pos, alt, isalt, k, skip=0, max_interval_size=0, read_stride=256, with_rows=False):
+        """gt_reads cut down to the reads align_gt_read keeps against (query, pos, alt, isalt): [query][shard] -> reads,
+        ascending read_row (rsbwt_set_gt_aligned_reads)"""
+        text, off = self._var_text(queries)
+        Q, S = len(queries), len(self.shards)
+        p, a, ia = self._gt_requests(queries, pos, alt, isalt)
+        first = np.zeros(Q * S + 1, np.uint64)
+        n = C.c_size_t()
+        rc = lib().rsbwt_set_gt_aligned_reads(self._s, _ptr(text), _ptr(off), Q, _ptr(p), _ptr(a), _ptr(ia), k, skip, max_interval_size, _ptr(first),
+                                              None, read_stride, None, None, 0, C.byref(n))
+        if rc not in (0, -7):
+            check(rc)
+        total = n.value
+        reads = np.zeros((max(total, 1), read_stride), np.uint8)
+        ln = np.zeros(max(total, 1), np.uint32)
+        rr = np.zeros(max(total, 1), np.uint64)
+        if total:
+            check(lib().rsbwt_set_gt_aligned_reads(self._s, _ptr(text), _ptr(off), Q, _ptr(p), _ptr(a), _ptr(ia), k, skip, max_interval_size,
+                                                   _ptr(first), _ptr(reads), read_stride, _ptr(ln), _ptr(rr), total, C.byref(n)))
+            if (ln[:total] == 0xFFFFFFFF).any():
+                raise RsbwtError(-1, "a read does not fit read_stride")
+
+        def one(r):
+            t = reads[r, :ln[r]].tobytes().decode()
+            return (int(rr[r]), t) if with_rows else t
+        return [[[one(r) for r in range(int(first[q * S + s]), int(first[q * S + s + 1]))] for s in range(S)] for q in range(Q)]
+
+    def gt_aligned_count(self, queries, pos, alt, isalt, k, skip=0, max_interval_size=0):
+        """[query][shard] -> the number of those reads (rsbwt_set_gt_aligned_count)"""
+        text, off = self._var_text(queries)
+        Q, S = len(queries), len(self.shards)
+        p, a, ia = self._gt_requests(queries, pos, alt, isalt)
+        out = np.zeros(Q * S, np.uint64)
+        check(lib().rsbwt_set_gt_aligned_count(self._s, _ptr(text), _ptr(off), Q, _ptr(p), _ptr(a), _ptr(ia), k, skip, max_interval_size, _ptr(out)))
+        return out.reshape(Q, S)
 
     # -- matching statistics (csrc/match_stats.hip): rsbwt_set_match_lengths / rsbwt_set_smems
     def match_lengths(self, queries, max_len=0, min_rows=1, intervals=False):

@@ -2070,3 +2070,247 @@ int rsbwt_sample_present_kmers_dev(rsbwt_t *h, size_t Q, uint32_t k, size_t stri
 }
 
 }  // extern "C"
+
+// ---- SiteMatch alignment (ksw_align.hip): ksw_align and align_gt_read, one lane per item ------------------------------
+namespace rsb {
+namespace {
+
+thread_local uint64_t gt_align_last_work[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+// what a host-buffer alignment call holds on the device while it runs: a stream of its own (concurrent callers run side
+// by side) and ONE allocation that every array of the call is cut from, each part 256-aligned
+struct align_tmp {
+    hipStream_t st = nullptr;
+    uint8_t *d = nullptr;
+    size_t total = 0;
+    size_t part(size_t bytes) {
+        const size_t at = total;
+        total += al256(bytes);
+        return at;
+    }
+    int open() {
+        hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+        if (e != hipSuccess) return fail_hip(e, "hipStreamCreate");
+        e = hipMalloc((void **)&d, total ? total : 256);
+        return e == hipSuccess ? RSBWT_OK : fail_hip(e, "alignment buffers");
+    }
+    hipError_t up(size_t at, const void *src, size_t bytes) { return bytes ? hipMemcpyAsync(d + at, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; }
+    ~align_tmp() {
+        if (d) (void)hipFree(d);
+        if (st) (void)hipStreamDestroy(st);
+    }
+};
+
+int ksw_params_check(const rsbwt_ksw_params *p, ksw_batch *bt) {
+    const rsbwt_ksw_params v = p ? *p : rsbwt_ksw_params{1, 4, 1, 6, 1};  // service.cpp:108-114 and :84
+    const int32_t all[5] = {v.match, v.mismatch, v.ambiguous, v.gapo, v.gape};
+    for (int32_t x : all)
+        if (x < 1 || x > 127) return fail(RSBWT_EINVAL, "ksw parameter %d: each of match, mismatch, ambiguous, gapo, gape is 1 to 127", x);
+    bt->match = v.match;
+    bt->mismatch = v.mismatch;
+    bt->ambiguous = v.ambiguous;
+    bt->gapo = v.gapo;
+    bt->gape = v.gape;
+    return RSBWT_OK;
+}
+
+// off[0 .. n] ascending with every length in 1..MAX_LEN (RSBWT_EINVAL): rel = the offsets from off[0]
+int ksw_lengths(const char *what, const uint64_t *off, size_t n, std::vector<uint64_t> *rel) {
+    rel->resize(n + 1);
+    for (size_t i = 0; i <= n; ++i) {
+        if (i && (off[i] <= off[i - 1] || off[i] - off[i - 1] > (uint64_t)RSBWT_KSW_MAX_LEN))
+            return fail(RSBWT_EINVAL, "%s %zu: a length of 1 to %d symbols", what, i - 1, RSBWT_KSW_MAX_LEN);
+        (*rel)[i] = off[i] - off[0];
+    }
+    return RSBWT_OK;
+}
+
+// the items ordered by (rows, columns): a wave's lanes finish together, a block's length class fits it closely
+std::vector<uint32_t> by_length(size_t n, const std::function<uint64_t(size_t)> &key) {
+    std::vector<uint32_t> perm(n);
+    for (size_t i = 0; i < n; ++i) perm[i] = (uint32_t)i;
+    std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return key(a) < key(b); });
+    return perm;
+}
+
+}  // namespace
+
+void gt_align_set_last_work(const uint64_t *work14) {
+    for (int i = 0; i < 14; ++i) gt_align_last_work[i] = work14 ? work14[i] : 0;
+}
+
+void gt_align_get_last_work(uint64_t *work14) { memcpy(work14, gt_align_last_work, sizeof gt_align_last_work); }
+
+int gt_align_host(int device, const char *reads, const uint64_t *roff, const uint64_t *item, size_t n, const char *text, const uint64_t *off,
+                  const uint64_t *pos, const char *alt, const uint8_t *isalt, size_t Q, uint8_t *verdict, uint64_t *work14) {
+    if (n == 0) return RSBWT_OK;
+    if (!reads || !roff || !item || !text || !off || !pos || !alt || !isalt || !verdict) return fail(RSBWT_EINVAL, "null argument");
+    if (n >= (1ull << 31) || Q >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu reads of %zu requests: under 2^31 in one call", n, Q);
+    std::vector<uint64_t> rrel, wrel;
+    int rc = ksw_lengths("read", roff, n, &rrel);
+    if (rc) return rc;
+    if (Q == 0) return fail(RSBWT_EINVAL, "read 0: request %llu of 0", (unsigned long long)item[0]);
+    if ((rc = ksw_lengths("request", off, Q, &wrel)) != RSBWT_OK) return rc;
+    uint32_t lo = (uint32_t)RSBWT_KSW_MAX_LEN, hi = 0;
+    auto rows = [&](size_t i) { return (uint32_t)std::max(rrel[i + 1] - rrel[i], wrel[item[i] + 1] - wrel[item[i]]); };
+    for (size_t i = 0; i < n; ++i) {
+        if (item[i] >= Q) return fail(RSBWT_EINVAL, "read %zu: request %llu of %zu", i, (unsigned long long)item[i], Q);
+        lo = std::min(lo, rows(i));
+        hi = std::max(hi, rows(i));
+    }
+    const std::vector<uint32_t> perm = by_length(n, [&](size_t i) { return ((uint64_t)rows(i) << 16) | (rrel[i + 1] - rrel[i]); });
+    if ((rc = use_device(device)) != RSBWT_OK) return rc;
+    align_tmp t;
+    const size_t o_reads = t.part(rrel[n]), o_roff = t.part((n + 1) * 8), o_item = t.part(n * 8), o_text = t.part(wrel[Q]),
+                 o_off = t.part((Q + 1) * 8), o_pos = t.part(Q * 8), o_alt = t.part(Q), o_isalt = t.part(Q), o_perm = t.part(n * 4),
+                 o_verdict = t.part(n), o_work = t.part(14 * 8), o_scratch = t.part(ksw_scratch_bytes(hi));
+    if ((rc = t.open()) != RSBWT_OK) return rc;
+    HIP_OK(t.up(o_reads, reads + roff[0], rrel[n]));
+    HIP_OK(t.up(o_roff, rrel.data(), (n + 1) * 8));
+    HIP_OK(t.up(o_item, item, n * 8));
+    HIP_OK(t.up(o_text, text + off[0], wrel[Q]));
+    HIP_OK(t.up(o_off, wrel.data(), (Q + 1) * 8));
+    HIP_OK(t.up(o_pos, pos, Q * 8));
+    HIP_OK(t.up(o_alt, alt, Q));
+    HIP_OK(t.up(o_isalt, isalt, Q));
+    HIP_OK(t.up(o_perm, perm.data(), n * 4));
+    HIP_OK(hipMemsetAsync(t.d + o_work, 0, 14 * 8, t.st));
+    gt_align_batch bt;
+    bt.reads = (const char *)(t.d + o_reads);
+    bt.text = (const char *)(t.d + o_text);
+    bt.alt = (const char *)(t.d + o_alt);
+    bt.roff = (const uint64_t *)(t.d + o_roff);
+    bt.item = (const uint64_t *)(t.d + o_item);
+    bt.off = (const uint64_t *)(t.d + o_off);
+    bt.pos = (const uint64_t *)(t.d + o_pos);
+    bt.isalt = t.d + o_isalt;
+    bt.n = n;
+    bt.Q = Q;
+    bt.perm = (const uint32_t *)(t.d + o_perm);
+    const hipError_t e = launch_gt_align(bt, lo, hi, ksw_scratch_bytes(hi) ? t.d + o_scratch : nullptr, t.d + o_verdict,
+                                         (unsigned long long *)(t.d + o_work), t.st);
+    if (e != hipSuccess) return fail_hip(e, "gt alignment kernel launch");
+    uint64_t work[14];
+    HIP_OK(hipMemcpyAsync(verdict, t.d + o_verdict, n, hipMemcpyDeviceToHost, t.st));
+    HIP_OK(hipMemcpyAsync(work, t.d + o_work, sizeof work, hipMemcpyDeviceToHost, t.st));
+    HIP_OK(hipStreamSynchronize(t.st));
+    if (work14)
+        for (int i = 0; i < 14; ++i) work14[i] += work[i];
+    return RSBWT_OK;
+}
+
+}  // namespace rsb
+
+extern "C" {
+
+int rsbwt_ksw_align(int device, const rsbwt_ksw_params *p, const char *qtext, const uint64_t *qoff, const char *ttext, const uint64_t *toff,
+                    size_t n, rsbwt_ksw_result *out) {
+    return guarded("rsbwt_ksw_align", [&]() -> int {
+        ksw_batch bt{};
+        int rc = ksw_params_check(p, &bt);
+        if (rc) return rc;
+        if (n == 0) return RSBWT_OK;
+        if (!qtext || !qoff || !ttext || !toff || !out) return fail(RSBWT_EINVAL, "null argument");
+        if (n >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu pairs: under 2^31 in one call", n);
+        std::vector<uint64_t> qrel, trel;
+        if ((rc = ksw_lengths("query", qoff, n, &qrel)) != RSBWT_OK) return rc;
+        if ((rc = ksw_lengths("target", toff, n, &trel)) != RSBWT_OK) return rc;
+        uint32_t lo = (uint32_t)RSBWT_KSW_MAX_LEN, hi = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const uint64_t ql = qrel[i + 1] - qrel[i], tl = trel[i + 1] - trel[i];
+            if ((uint64_t)bt.match * std::min(ql, tl) >= 32768ull)
+                return fail(RSBWT_ERANGE, "pair %zu: match %d x %llu symbols reaches 2^15, where 16-bit scores saturate", i, bt.match,
+                            (unsigned long long)std::min(ql, tl));
+            lo = std::min(lo, (uint32_t)ql);
+            hi = std::max(hi, (uint32_t)ql);
+        }
+        const std::vector<uint32_t> perm = by_length(n, [&](size_t i) { return ((qrel[i + 1] - qrel[i]) << 16) | (trel[i + 1] - trel[i]); });
+        if ((rc = use_device(device)) != RSBWT_OK) return rc;
+        align_tmp t;
+        const size_t o_q = t.part(qrel[n]), o_t = t.part(trel[n]), o_qoff = t.part((n + 1) * 8), o_toff = t.part((n + 1) * 8), o_perm = t.part(n * 4),
+                     o_out = t.part(n * sizeof(rsbwt_ksw_result)), o_scratch = t.part(ksw_scratch_bytes(hi));
+        if ((rc = t.open()) != RSBWT_OK) return rc;
+        HIP_OK(t.up(o_q, qtext + qoff[0], qrel[n]));
+        HIP_OK(t.up(o_t, ttext + toff[0], trel[n]));
+        HIP_OK(t.up(o_qoff, qrel.data(), (n + 1) * 8));
+        HIP_OK(t.up(o_toff, trel.data(), (n + 1) * 8));
+        HIP_OK(t.up(o_perm, perm.data(), n * 4));
+        bt.qtext = (const char *)(t.d + o_q);
+        bt.ttext = (const char *)(t.d + o_t);
+        bt.qoff = (const uint64_t *)(t.d + o_qoff);
+        bt.toff = (const uint64_t *)(t.d + o_toff);
+        bt.n = n;
+        bt.perm = (const uint32_t *)(t.d + o_perm);
+        const hipError_t e = launch_ksw_align(bt, lo, hi, ksw_scratch_bytes(hi) ? t.d + o_scratch : nullptr, t.d + o_out, t.st);
+        if (e != hipSuccess) return fail_hip(e, "ksw alignment kernel launch");
+        HIP_OK(hipMemcpyAsync(out, t.d + o_out, n * sizeof(rsbwt_ksw_result), hipMemcpyDeviceToHost, t.st));
+        HIP_OK(hipStreamSynchronize(t.st));
+        return RSBWT_OK;
+    });
+}
+
+int rsbwt_ksw_align_dev(const rsbwt_ksw_params *p, const void *d_qtext, const void *d_qoff, const void *d_ttext, const void *d_toff, size_t n,
+                        void *d_out, int device, void *stream) {
+    ksw_batch bt{};
+    int rc = ksw_params_check(p, &bt);
+    if (rc) return rc;
+    if (n == 0) return RSBWT_OK;
+    if (!d_qtext || !d_qoff || !d_ttext || !d_toff || !d_out) return fail(RSBWT_EINVAL, "null argument");
+    if (n >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu pairs: under 2^31 in one call", n);
+    if ((rc = use_device(device)) != RSBWT_OK) return rc;
+    bt.qtext = (const char *)d_qtext;
+    bt.ttext = (const char *)d_ttext;
+    bt.qoff = (const uint64_t *)d_qoff;
+    bt.toff = (const uint64_t *)d_toff;
+    bt.n = n;
+    bt.perm = nullptr;
+    void *d_scratch = nullptr;  // the lengths are not known here: room for the longest, from the stream's pool and back to it
+    HIP_OK(hipMallocAsync(&d_scratch, ksw_scratch_bytes(RSBWT_KSW_MAX_LEN), (hipStream_t)stream));
+    const hipError_t e = launch_ksw_align(bt, 1, RSBWT_KSW_MAX_LEN, d_scratch, d_out, (hipStream_t)stream);
+    (void)hipFreeAsync(d_scratch, (hipStream_t)stream);
+    return e == hipSuccess ? RSBWT_OK : fail_hip(e, "ksw alignment kernel launch");
+}
+
+int rsbwt_gt_align(int device, const char *reads, const uint64_t *roff, const uint64_t *item, size_t n, const char *text, const uint64_t *off,
+                   const uint64_t *pos, const char *alt, const uint8_t *isalt, size_t Q, uint8_t *verdict) {
+    return guarded("rsbwt_gt_align", [&]() -> int {
+        gt_align_set_last_work(nullptr);
+        uint64_t work14[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        const int rc = gt_align_host(device, reads, roff, item, n, text, off, pos, alt, isalt, Q, verdict, work14);
+        if (rc) return rc;
+        gt_align_set_last_work(work14);
+        return RSBWT_OK;
+    });
+}
+
+int rsbwt_gt_align_dev(const void *d_reads, const void *d_roff, const void *d_item, size_t n, const void *d_text, const void *d_off,
+                       const void *d_pos, const void *d_alt, const void *d_isalt, size_t Q, void *d_verdict, int device, void *stream) {
+    if (n == 0) return RSBWT_OK;
+    if (!d_reads || !d_roff || !d_item || !d_text || !d_off || !d_pos || !d_alt || !d_isalt || !d_verdict) return fail(RSBWT_EINVAL, "null argument");
+    if (n >= (1ull << 31) || Q >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu reads of %zu requests: under 2^31 in one call", n, Q);
+    const int rc = use_device(device);
+    if (rc) return rc;
+    gt_align_batch bt;
+    bt.reads = (const char *)d_reads;
+    bt.text = (const char *)d_text;
+    bt.alt = (const char *)d_alt;
+    bt.roff = (const uint64_t *)d_roff;
+    bt.item = (const uint64_t *)d_item;
+    bt.off = (const uint64_t *)d_off;
+    bt.pos = (const uint64_t *)d_pos;
+    bt.isalt = (const uint8_t *)d_isalt;
+    bt.n = n;
+    bt.Q = Q;
+    bt.perm = nullptr;
+    void *d_scratch = nullptr;
+    HIP_OK(hipMallocAsync(&d_scratch, ksw_scratch_bytes(RSBWT_KSW_MAX_LEN), (hipStream_t)stream));
+    const hipError_t e = launch_gt_align(bt, 1, RSBWT_KSW_MAX_LEN, d_scratch, d_verdict, nullptr, (hipStream_t)stream);
+    (void)hipFreeAsync(d_scratch, (hipStream_t)stream);
+    return e == hipSuccess ? RSBWT_OK : fail_hip(e, "gt alignment kernel launch");
+}
+
+void rsbwt_gt_align_last_work(uint64_t *work14) {
+    if (work14) gt_align_get_last_work(work14);
+}
+
+}  // extern "C"

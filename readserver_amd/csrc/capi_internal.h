@@ -154,6 +154,13 @@ int walk_host_views(scratch_cache &scratch, hipStream_t st, const shard_view *d_
                     uint32_t *support, uint64_t *last, uint64_t *work6);
 void walk_set_last_work(const uint64_t work6[6]);
 void walk_get_last_work(uint64_t work6[6]);
+// ksw_align.hip behind rsbwt_gt_align (capi.hip) and the aligned set calls (sets.hip): a host batch checked (null, item < Q,
+// lengths 1..4096: RSBWT_EINVAL), ordered by length, aligned on `device` and waited for; work14 += {reads, reads by
+// verdict 1..13}.  gt_align_set / get_last_work: what rsbwt_gt_align_last_work reports for the calling thread (null: zeros)
+int gt_align_host(int device, const char *reads, const uint64_t *roff, const uint64_t *item, size_t n, const char *text, const uint64_t *off,
+                  const uint64_t *pos, const char *alt, const uint8_t *isalt, size_t Q, uint8_t *verdict, uint64_t *work14);
+void gt_align_set_last_work(const uint64_t *work14);
+void gt_align_get_last_work(uint64_t *work14);
 // 1-mismatch hit list of one shard from variants expanded once for the whole batch (sets.hip: every shard of a set
 // searches the same variants)
 size_t variants_bytes(size_t m, uint32_t k);

@@ -410,6 +410,38 @@ hipError_t launch_walk(const shard_view *d_shards, uint32_t nshards, const walk_
                        void *d_last, unsigned long long *d_work, hipStream_t stream);
 hipError_t launch_extensions(const shard_view *d_shards, uint32_t nshards, const walk_batch &bt, void *d_counts, unsigned long long *d_work,
                              hipStream_t stream);
+// ksw_align.hip: ksw_align of the reference's ksw.c and align_gt_read over it (ksw_pass.h), one lane per item.  A block is
+// one wave of 64 items and belongs to the LENGTH CLASS of its longest pass: at most 32, 64, 104, 160 or KSW_LDS_ROWS rows
+// -- the column lives in LDS, the launch's LDS sized for the class -- or more: the column lives in d_scratch
+// (ksw_scratch_bytes(max_rows): KSW_HBM_BLOCKS resident blocks).  There is one launch per class; every launch goes over
+// every block and takes the blocks that are its own, so none needs the lengths on the host.  min_rows / max_rows bound the
+// items' longest passes (1 and 4096 when the host does not know): classes outside them are not launched.  d_perm
+// (optional) names the item lane g works on -- the host orders items by length so that a wave's lanes finish together
+// and a block's class fits it closely.  Everything in HBM.
+//   ksw: pair i = qtext[qoff[i] .. qoff[i+1]) on the rows against ttext[toff[i] .. toff[i+1]) on the columns; out[i] =
+//        {score, te, qe, tb, qb, 0}, all -1 for a pair with a length outside 1..4096 or match * min(qlen, tlen) >= 2^15
+//   gt:  read i against request item[i]; verdict[i] = RSBWT_GT_*, RSBWT_GT_INVALID for a length outside 1..4096 or
+//        item[i] >= Q; d_work14 (optional, zeroed by the caller): [0] += reads, [v] += reads with verdict v
+constexpr uint32_t KSW_LDS_ROWS = 224;   // RSBWT_KSW_LDS_ROWS: 224 rows x 64 lanes x 4 B + their codes = 63 KiB of LDS
+constexpr uint32_t KSW_HBM_BLOCKS = 128;
+struct ksw_batch {
+    const char *qtext, *ttext;
+    const uint64_t *qoff, *toff;
+    size_t n;
+    const uint32_t *perm;
+    int32_t match, mismatch, ambiguous, gapo, gape;
+};
+struct gt_align_batch {
+    const char *reads, *text, *alt;
+    const uint64_t *roff, *item, *off, *pos;
+    const uint8_t *isalt;
+    size_t n, Q;
+    const uint32_t *perm;
+};
+size_t ksw_scratch_bytes(uint32_t max_rows);  // 0 while max_rows <= KSW_LDS_ROWS: d_scratch may be null then
+hipError_t launch_ksw_align(const ksw_batch &bt, uint32_t min_rows, uint32_t max_rows, void *d_scratch, void *d_out, hipStream_t stream);
+hipError_t launch_gt_align(const gt_align_batch &bt, uint32_t min_rows, uint32_t max_rows, void *d_scratch, void *d_verdict,
+                           unsigned long long *d_work14, hipStream_t stream);
 // (SEL_SHIFT, sample_window, window_samples, window_psi_hint: line_format.h -- shared with the host-side layout test)
 // query / query_exactmatch (query.cpp:87-120) over extracted reads
 hipError_t launch_match_reads(const void *d_reads, const void *d_len, size_t n, uint32_t stride, const void *d_owner,

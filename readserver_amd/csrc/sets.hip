@@ -1973,6 +1973,114 @@ void rsbwt_set_gt_last_work(uint64_t *work6) {
     if (work6) memcpy(work6, gt_last_work, sizeof gt_last_work);
 }
 
+namespace {
+// gt_call's reads cut down to those align_gt_read keeps (ksw_align.hip).  Each device group aligns the reads of its own
+// shards against their requests, the groups side by side; a group sends only the requests that have a read there.  The
+// known host trip: the reads came down from the extraction as strings and go up again here.
+int gt_aligned_call(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, const char *alt, const uint8_t *isalt,
+                    int32_t k, int32_t skip, uint64_t M, gt_reads_t *res, uint32_t stride) {
+    gt_align_set_last_work(nullptr);
+    if (Q && (!alt || !isalt)) return fail(RSBWT_EINVAL, "null argument");
+    int rc = gt_call(s, text, off, Q, pos, k, skip, M, nullptr, nullptr, res, stride);
+    if (rc) return rc;
+    const size_t S = s->shards.size(), G = s->groups.size();
+    std::vector<std::vector<uint8_t>> verdicts(G);
+    std::vector<std::vector<uint64_t>> works(G, std::vector<uint64_t>(14, 0));
+    rc = for_each_group(s, [&](size_t gi) -> int {
+        const dev_group *g = s->groups[gi];
+        std::string rbuf, wbuf, walt;
+        std::vector<uint64_t> roff{0}, item, woff{0}, wpos;
+        std::vector<uint8_t> wisalt;
+        for (size_t q = 0; q < Q; ++q) {
+            const size_t before = item.size();
+            for (size_t p : g->idx)
+                for (const auto &pr : (*res)[q * S + p]) {
+                    rbuf += pr.second;
+                    roff.push_back(rbuf.size());
+                    item.push_back(wpos.size());
+                }
+            if (item.size() == before) continue;
+            wbuf.append(text + off[q], (size_t)(off[q + 1] - off[q]));
+            woff.push_back(wbuf.size());
+            wpos.push_back(pos[q]);
+            walt.push_back(alt[q]);
+            wisalt.push_back(isalt[q]);
+        }
+        if (item.empty()) return RSBWT_OK;
+        verdicts[gi].resize(item.size());
+        return gt_align_host(g->device, rbuf.data(), roff.data(), item.data(), item.size(), wbuf.data(), woff.data(), wpos.data(), walt.data(),
+                             wisalt.data(), wpos.size(), verdicts[gi].data(), works[gi].data());
+    });
+    if (rc) return rc;
+    uint64_t work14[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (size_t gi = 0; gi < G; ++gi) {
+        size_t at = 0;  // (the order the group's batch was made in)
+        for (size_t q = 0; q < Q; ++q)
+            for (size_t p : s->groups[gi]->idx) {
+                auto &cell = (*res)[q * S + p];
+                std::vector<std::pair<uint64_t, std::string>> kept;
+                for (auto &pr : cell) {
+                    const uint8_t v = verdicts[gi][at++];
+                    if (v == RSBWT_GT_KEEP_PLAIN || v == RSBWT_GT_KEEP_RIGHT || v == RSBWT_GT_KEEP_LEFT) kept.push_back(std::move(pr));
+                }
+                cell.swap(kept);
+            }
+        for (int i = 0; i < 14; ++i) work14[i] += works[gi][i];
+    }
+    gt_align_set_last_work(work14);
+    return RSBWT_OK;
+}
+}  // namespace
+
+int rsbwt_set_gt_aligned_reads(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, const char *alt,
+                               const uint8_t *isalt, int32_t k, int32_t skip, uint64_t M, uint64_t *first, char *reads, uint32_t read_stride,
+                               uint32_t *read_len, uint64_t *read_row, size_t cap_reads, size_t *nreads) {
+    return guarded("rsbwt_set_gt_aligned_reads", [&]() -> int {
+        if (!nreads || (!first && Q)) return fail(RSBWT_EINVAL, "null argument");
+        *nreads = 0;
+        if (read_stride == 0) return fail(RSBWT_EINVAL, "read_stride must be positive");
+        gt_reads_t res;
+        // (every read is fetched whole, whatever the caller's stride: the alignment needs all of it)
+        const int rc = gt_aligned_call(s, text, off, Q, pos, alt, isalt, k, skip, M, &res, std::max<uint32_t>(read_stride, 256));
+        if (rc) return rc;
+        size_t total = 0;
+        for (size_t c = 0; c < res.size(); ++c) {
+            first[c] = total;
+            total += res[c].size();
+        }
+        if (first) first[res.size()] = total;
+        *nreads = total;
+        if (total > cap_reads) return fail(RSBWT_ERANGE, "%zu reads, room for %zu", total, cap_reads);
+        if (total == 0) return RSBWT_OK;
+        if (!reads || !read_len) return fail(RSBWT_EINVAL, "null argument");
+        size_t r = 0;
+        for (const auto &cell : res)
+            for (const auto &pr : cell) {
+                if (pr.second.size() > read_stride) {
+                    read_len[r] = 0xFFFFFFFFu;
+                } else {
+                    memcpy(reads + r * (size_t)read_stride, pr.second.data(), pr.second.size());
+                    read_len[r] = (uint32_t)pr.second.size();
+                }
+                if (read_row) read_row[r] = pr.first;
+                ++r;
+            }
+        return RSBWT_OK;
+    });
+}
+
+int rsbwt_set_gt_aligned_count(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, const char *alt,
+                               const uint8_t *isalt, int32_t k, int32_t skip, uint64_t M, uint64_t *counts) {
+    return guarded("rsbwt_set_gt_aligned_count", [&]() -> int {
+        if (!counts && Q) return fail(RSBWT_EINVAL, "null argument");
+        gt_reads_t res;
+        const int rc = gt_aligned_call(s, text, off, Q, pos, alt, isalt, k, skip, M, &res, 256);
+        if (rc) return rc;
+        for (size_t c = 0; c < res.size(); ++c) counts[c] = res[c].size();
+        return RSBWT_OK;
+    });
+}
+
 // ---- matching statistics (match_stats.hip): the longest supported match at every end position, in every shard ----
 namespace {
 // Each device group runs its shards' rows of the (position, shard) grid; answers are per (position, shard), so the host

@@ -946,6 +946,54 @@ int rsbwt_set_sample_counts_dev(rsbwt_set_t *s, const void *d_text, const void *
 int rsbwt_sample_keys(const uint8_t *codes, size_t C, uint32_t size_of_sample, uint64_t *keys);
 void rsbwt_set_sample_last_work(uint64_t *work6);
 uint64_t rsbwt_set_meta_head_bytes(const rsbwt_set_t *s);
+/* Site sample counts: which samples have reads supporting this allele, and how many -- the sum over the reads SiteMatch +
+ * All returns one by one (the reference's /gt), made on the device.  Requests are exactly rsbwt_set_gt_aligned_reads' (w =
+ * text[off[q] .. off[q+1]), pos, alt, isalt after GtTask::run's fix-up; k, skip, M); the dictionary and the record rules are
+ * exactly rsbwt_set_sample_counts' (codes, C, size_of_sample, has_other_meta_data; column C for a code the dictionary lacks,
+ * the stray tail dropped, a code listed twice adds twice, c = (signed char)byte - 33).  In terms of those calls:
+ *   R(q, p)      the reads rsbwt_set_gt_reads reports for request q in shard p
+ *   A(q, p)      those of R(q, p) that rsbwt_set_gt_aligned_reads keeps
+ *   a head       a string has a head in shard p when its FIRST ordinal there has its bit set in heads_p, that is when a pair
+ *                of the sample table named it with copies > 0
+ *   aligned[q]   the sum over p of |{r in R(q, p) with a head in p}|
+ *   carriers[q]  the sum over p of |{r in A(q, p) with a head in p}|
+ *   the sum      every whole record of every carrier's value at its head ordinal is tallied into row q of strings u32[Q][C + 1]
+ *                and copies i64[Q][C + 1], as rsbwt_set_sample_counts tallies a carrier.  A string present in two shards
+ *                counts in each.  Any output may be NULL, not all of them.  Q = 0 succeeds and touches nothing.  All
+ *                arithmetic is in integers: the answers are bit-identical from run to run.
+ * A read no pair names is neither extracted nor aligned: it could add nothing.  That is the one place where this call is
+ * cheaper than the composition by definition, and it loses nothing: every copy of a string lies in the same leg intervals at
+ * the same offsets with the same prefix and postfix lengths, so the head copy is among the rows the span filter keeps
+ * whenever any copy is.
+ * align_gt_read is the reference's as written, the isalt branch included: isalt = 1 rejects when the alt scores at least as
+ * well, so it keeps a subset of what isalt = 0 keeps.  A caller who wants the alt allele's support sends the alt window (w
+ * with the alt base at pos, alt = the reference base).
+ * RSBWT_EINVAL: shards not opened with RSBWT_OPEN_READS; a set without a sample table ("no sample table"); a dictionary
+ * rsbwt_sample_keys refuses; a shard of 2^40 strings or 2^46 symbols; a candidate row whose walk does not end; a w, or a
+ * candidate read with a head, longer than 4,096 symbols.  pos = 0 and pos > |w| behave as in rsbwt_set_gt_aligned_reads:
+ * candidates may exist and are counted in aligned[], and none is a carrier.
+ * From the narrowing to the matrices the batch stays on the device (csrc/site_counts.hip): the span filter's kept rows are
+ * deduplicated to (request, head ordinal) items in a hash set in HBM, the distinct reads among them are extracted once into
+ * a device buffer (requests that share a window share their reads), the items go to the alignment without a copy through the
+ * host, and the kept ones are tallied there.  Per device group the host receives the matrices, the two count vectors, the
+ * counters and five sizes of eight bytes (rows, items, distinct reads, reads over the first extraction's 256 bytes, the
+ * longest read); the groups' matrices are added on the host.  A call of many requests runs in slices whose matrices stay
+ * under 1.5 GiB of HBM (and under 2^24 requests: the request number is part of a 64-bit key).  Re-entrant like the other
+ * lookups; not beside build / load / clear.
+ *   rsbwt_set_site_last_work   the calling thread's last call: {legs, LF steps spent lengthening, candidate rows, rows the span
+ *       filter kept (the first four as rsbwt_set_gt_last_work counts them), of those rows on a head ordinal, distinct reads
+ *       extracted, (request, read) items aligned, items kept, records added, records with an unknown code}; a failed call
+ *       leaves all ten zero.  NULL is harmless.
+ *   rsbwt_set_site_last_times  a measurement hook: while the environment has RSBWT_SITE_TIMES=1 the call puts events around
+ *       each stage's launches on its stream (and waits for them, which costs time: not for production) and this reports the
+ *       calling thread's last call in ms, summed over device groups and slices: {narrowing + rows + walks + filter, head
+ *       test + set + compaction, sort / unique + extraction, length rule + ordering, alignment, tally}; all zero otherwise. */
+int rsbwt_set_site_sample_counts(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, const char *alt,
+                                 const uint8_t *isalt, int32_t k, int32_t skip, uint64_t M, const uint8_t *codes, size_t C,
+                                 uint32_t size_of_sample, int has_other_meta_data, uint32_t *strings, int64_t *copies, uint64_t *aligned,
+                                 uint64_t *carriers);
+void rsbwt_set_site_last_work(uint64_t *work10);
+void rsbwt_set_site_last_times(double *ms6);
 /* Device-resident forms, for a set on ONE device (one process per GPU: bench.py --mode 1mm|extract).
  * d_hits [num_shards][cap_per_shard] x 32-byte records (rsbwt_hits_1mm_dev's), d_totals u64[num_shards];
  * d_rows [num_shards][n] (row numbers are per shard), d_out [num_shards][n][stride], d_len / d_prefix_len [num_shards][n]. */

@@ -239,6 +239,10 @@ SIGNATURES = {
     "rsbwt_sample_keys": (C.c_int, [_vp, C.c_size_t, C.c_uint32, _vp]),
     "rsbwt_set_sample_last_work": (None, [_u64p]),
     "rsbwt_set_meta_head_bytes": (C.c_uint64, [_vp]),
+    "rsbwt_set_site_sample_counts": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_uint64, _vp, C.c_size_t, C.c_uint32,
+                                               C.c_int, _vp, _vp, _vp, _vp]),
+    "rsbwt_set_site_last_work": (None, [_u64p]),
+    "rsbwt_set_site_last_times": (None, [C.POINTER(C.c_double)]),
     "rsbwt_proto_encode_all_reply": (C.c_size_t, [_vp, C.c_size_t, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_char_p),
                                                   C.POINTER(C.c_size_t), C.POINTER(_vp), C.POINTER(C.c_size_t), C.c_size_t, C.c_char_p,
                                                   C.c_size_t, C.c_uint32, C.c_int]),

@@ -1035,6 +1035,48 @@ class ShardSet:
         lib().rsbwt_set_sample_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
         return dict(zip(("rows", "head_rows", "carriers", "records", "unknown", "lf_steps"), (int(x) for x in w)))
 
+    # -- site sample counts (csrc/site_counts.hip): rsbwt_set_site_sample_counts
+    def site_sample_counts(self, queries, pos, alt, isalt, k, skip=0, max_interval_size=0, *, codes, size_of_sample, has_other_meta_data=True):
+        """Which samples have reads supporting each site request, and how many (rsbwt_set_site_sample_counts).  Requests as
+        gt_aligned_reads takes them, the dictionary as sample_counts takes it.  Returns a dict of strings (Q, C + 1) uint32 and
+        copies (Q, C + 1) int64 with the columns in the caller's order and the records of unknown codes in the last column,
+        aligned (Q) -- the candidate reads with a value entry -- and carriers (Q) -- those align_gt_read keeps."""
+        cs = [bytes(c) for c in codes]
+        if any(len(c) != size_of_sample for c in cs):
+            raise ValueError("a code is not size_of_sample bytes long")
+        order = sorted(range(len(cs)), key=lambda i: cs[i])
+        flat = np.frombuffer(b"".join(cs[i] for i in order) + b"\0", np.uint8).copy()
+        text, off = self._var_text(queries)
+        Q, n = len(queries), len(cs)
+        p, a, ia = self._gt_requests(queries, pos, alt, isalt)
+        strings = np.zeros((max(Q, 1), n + 1), np.uint32)
+        copies = np.zeros((max(Q, 1), n + 1), np.int64)
+        aligned, carriers = np.zeros(max(Q, 1), np.uint64), np.zeros(max(Q, 1), np.uint64)
+        check(lib().rsbwt_set_site_sample_counts(self._s, _ptr(text), _ptr(off), Q, _ptr(p), _ptr(a), _ptr(ia), k, skip, max_interval_size, _ptr(flat), n,
+                                                 size_of_sample, 1 if has_other_meta_data else 0, _ptr(strings), _ptr(copies), _ptr(aligned),
+                                                 _ptr(carriers)))
+        back = np.empty(n + 1, np.int64)  # the caller's column -> the sorted column
+        back[np.array(order, np.int64)] = np.arange(n)
+        back[n] = n
+        return dict(strings=strings[:Q][:, back], copies=copies[:Q][:, back], aligned=aligned[:Q].copy(), carriers=carriers[:Q].copy())
+
+    @staticmethod
+    def site_last_work():
+        """{legs, narrow_steps, candidates, kept, head_rows, extracted, aligned, carriers, records, unknown} of this thread's
+        last site_sample_counts call"""
+        w = np.zeros(10, np.uint64)
+        lib().rsbwt_set_site_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return dict(zip(("legs", "narrow_steps", "candidates", "kept", "head_rows", "extracted", "aligned", "carriers", "records", "unknown"),
+                        (int(x) for x in w)))
+
+    @staticmethod
+    def site_last_times():
+        """{filter, set, reads, items, align, tally} in ms of this thread's last site_sample_counts call, from events; zeros
+        unless RSBWT_SITE_TIMES=1 (rsbwt_set_site_last_times)"""
+        t = np.zeros(6, np.float64)
+        lib().rsbwt_set_site_last_times(t.ctypes.data_as(C.POINTER(C.c_double)))
+        return dict(zip(("filter", "set", "reads", "items", "align", "tally"), (float(x) for x in t)))
+
     # -- BASELINE configs[3] / configs[4] over the set: per-shard results side by side, the way the front-end
     # concatenates its partitions' replies (src/service/server.cpp:199-261)
     def hits_1mm(self, kmers):

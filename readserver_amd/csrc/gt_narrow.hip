@@ -263,10 +263,21 @@ gt_narrow_kernel(const shard_view *__restrict__ shards, const gt_batch bt, gt_le
 // COMPACTION: a wave counts the rows it keeps, claims that many records from counters[0] with one atomic and every
 // kept row writes its record -- so only kept rows ever leave the device (in no particular order: the host sorts by
 // read).  counters[1] += rows whose walk did not end on a '$' row (locate's UINT32_MAX offset).
+// REC = gt_site_row: the record also carries the row's ordinal (launch_locate's d_ordinal) -- site_counts.hip's input.
+__device__ __forceinline__ void gt_filter_record(gt_kept_row *out, uint32_t item, uint32_t shard, uint32_t off, uint32_t pending, uint64_t read_row,
+                                                 const uint64_t *, uint64_t) {
+    *out = gt_kept_row{item, shard, off, pending, read_row};
+}
+__device__ __forceinline__ void gt_filter_record(gt_site_row *out, uint32_t item, uint32_t shard, uint32_t off, uint32_t pending, uint64_t read_row,
+                                                 const uint64_t *ordinal, uint64_t t) {
+    *out = gt_site_row{item, shard, off, pending, read_row, ordinal[t]};
+}
+
+template <class REC>
 __global__ void __launch_bounds__(256)
 gt_filter_kernel(const gt_batch bt, const gt_leg *__restrict__ legs, const uint64_t *__restrict__ first, const uint32_t *__restrict__ shard_of,
-                 const uint32_t *__restrict__ offset, const uint64_t *__restrict__ read_row, uint64_t total, gt_kept_row *__restrict__ out,
-                 unsigned long long *__restrict__ counters) {
+                 const uint32_t *__restrict__ offset, const uint64_t *__restrict__ read_row, const uint64_t *__restrict__ ordinal, uint64_t total,
+                 REC *__restrict__ out, unsigned long long *__restrict__ counters) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t f = 0, item32 = 0, shard = 0, off = 0;
@@ -306,7 +317,7 @@ gt_filter_kernel(const gt_batch bt, const gt_leg *__restrict__ legs, const uint6
         base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)base);
         if (f != 0u) {
             const uint64_t at = base + (uint64_t)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
-            if (at < total) out[at] = gt_kept_row{item32, shard, off, f == 2u ? 1u : 0u, read_row[t]};
+            if (at < total) gt_filter_record(&out[at], item32, shard, off, f == 2u ? 1u : 0u, read_row[t], ordinal, t);
         }
     }
     if (lost_mask != 0ull && lane == 0u) atomicAdd(&counters[1], (unsigned long long)__builtin_popcountll(lost_mask));
@@ -324,11 +335,18 @@ hipError_t launch_gt_narrow(const shard_view *d_shards, uint32_t nshards, const 
 }
 
 hipError_t launch_gt_filter(const gt_batch &bt, const void *d_legs, const void *d_first, const void *d_shard_of, const void *d_offset,
-                            const void *d_read_row, uint64_t total, void *d_kept_rows, unsigned long long *d_counters, hipStream_t stream) {
+                            const void *d_read_row, uint64_t total, void *d_kept_rows, unsigned long long *d_counters, hipStream_t stream,
+                            const void *d_ordinal) {
     if (total == 0) return hipSuccess;
-    hipLaunchKernelGGL(gt_filter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, bt, (const gt_leg *)d_legs,
-                       (const uint64_t *)d_first, (const uint32_t *)d_shard_of, (const uint32_t *)d_offset, (const uint64_t *)d_read_row, total,
-                       (gt_kept_row *)d_kept_rows, d_counters);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (d_ordinal)
+        hipLaunchKernelGGL(gt_filter_kernel<gt_site_row>, grid, dim3(256), 0, stream, bt, (const gt_leg *)d_legs, (const uint64_t *)d_first,
+                           (const uint32_t *)d_shard_of, (const uint32_t *)d_offset, (const uint64_t *)d_read_row, (const uint64_t *)d_ordinal, total,
+                           (gt_site_row *)d_kept_rows, d_counters);
+    else
+        hipLaunchKernelGGL(gt_filter_kernel<gt_kept_row>, grid, dim3(256), 0, stream, bt, (const gt_leg *)d_legs, (const uint64_t *)d_first,
+                           (const uint32_t *)d_shard_of, (const uint32_t *)d_offset, (const uint64_t *)d_read_row, (const uint64_t *)nullptr, total,
+                           (gt_kept_row *)d_kept_rows, d_counters);
     return hipGetLastError();
 }
 

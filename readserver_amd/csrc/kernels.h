@@ -351,8 +351,14 @@ struct gt_kept_row {
 };
 hipError_t launch_gt_narrow(const shard_view *d_shards, uint32_t nshards, const gt_batch &bt, void *d_legs, void *d_pairs,
                             unsigned long long *d_work, hipStream_t stream);
+// (d_ordinal, launch_locate's: d_kept_rows is gt_site_row[total] instead, the record with the row's ordinal behind it)
+struct gt_site_row {
+    uint32_t item, shard, offset, pending;
+    uint64_t read_row, ordinal;
+};
 hipError_t launch_gt_filter(const gt_batch &bt, const void *d_legs, const void *d_first, const void *d_shard_of, const void *d_offset,
-                            const void *d_read_row, uint64_t total, void *d_kept_rows, unsigned long long *d_counters, hipStream_t stream);
+                            const void *d_read_row, uint64_t total, void *d_kept_rows, unsigned long long *d_counters, hipStream_t stream,
+                            const void *d_ordinal = nullptr);
 // match_stats.hip: matching statistics (include/rsbwt.h: the definition).  A batch is its queries' text back to back and
 // where each starts: position t < N = off[Q] belongs to the query with off[q] <= t < off[q + 1] (off[0] = 0), all in HBM.
 struct match_batch {
@@ -437,11 +443,94 @@ struct gt_align_batch {
     const uint8_t *isalt;
     size_t n, Q;
     const uint32_t *perm;
+    // optional indirection (nullptr: the packed roff form above): item i is read rid[i], which lies at address raddr[rid[i]]
+    // (anywhere in HBM: reads extracted at two strides need not share a buffer) with rlen[rid[i]] symbols; reads / roff
+    // are not looked at.  Requests that share a read then share its bytes.
+    const uint32_t *rid = nullptr;
+    const uint64_t *raddr = nullptr;
+    const uint32_t *rlen = nullptr;
 };
 size_t ksw_scratch_bytes(uint32_t max_rows);  // 0 while max_rows <= KSW_LDS_ROWS: d_scratch may be null then
 hipError_t launch_ksw_align(const ksw_batch &bt, uint32_t min_rows, uint32_t max_rows, void *d_scratch, void *d_out, hipStream_t stream);
 hipError_t launch_gt_align(const gt_align_batch &bt, uint32_t min_rows, uint32_t max_rows, void *d_scratch, void *d_verdict,
                            unsigned long long *d_work14, hipStream_t stream);
+// site_counts.hip: rsbwt_set_site_sample_counts -- the span filter's kept rows (gt_site_row) handed to the alignment and the
+// kept reads' sample records tallied without a row, a read or a verdict leaving the device.  Everything in HBM; the stages
+// are enqueued on one stream in this order (the host reads a size back where the next stage's launch needs one):
+//   launch_site_legs     work[SITE_WORK_LEGS] += the leg records of d_legs gt_leg[cells] that hold a leg
+//   launch_site_rows     STAGE 2, one lane per kept row (d_rows gt_site_row[*d_nrows], at most cap): rows_of[shard] (u64[S],
+//                        zeroed) counted first and the regions made from it (launch_sample_regions' rule); then a row on a
+//                        head ordinal inserts (request << 40 | ordinal) into its shard's region of `set` (all ones = empty,
+//                        every access the 64-bit CAS), the winner stores set_row[slot] = read_row, and every row takes
+//                        atomicMin(set_need[slot], the read length that lets it stay): gt_span_rule.h, 0 for a row that is
+//                        not pending, capped at SITE_NEED_MAX; set_need starts all ones.
+//   launch_site_compact  STAGE 3a, one lane per slot (nslots of them): the set's entries as site_item records in any order,
+//                        work[SITE_WORK_ITEMS] of them; sort_key[i] = shard << row_bits | read_row and sort_idx[i] = i
+//   launch_site_reads    STAGE 3b over n items: sort on (shard, read_row), unique: items[i].rid = the read's number among
+//                        the distinct ones, d_rows[rid] its read_row, d_seg u64[S + 1] where each shard's reads start
+//                        (launch_extract_ragged's segments, seg_stride 1), *d_nreads (u64) how many.  d_tmp: site_reads_tmp_bytes(n).
+//   launch_site_over     after the extraction at the first stride: d_over u64[R + 1] = 1 for a read that did not fit (length
+//                        UINT32_MAX), d_ofirst its exclusive scan (d_ofirst[R] = how many); *d_longest (zeroed) = the longest
+//                        read that fit; d_tmp: meta_scan_bytes(R + 1)
+//   launch_site_wide     those reads' rows compacted in order (d_wrows) and d_wseg u64[S + 1] for the second extraction
+//   launch_site_addr     raddr[r] = where read r lies (narrow + r * stride, or wide + d_ofirst[r] * wide_stride) and rlen[r]
+//                        from the second extraction for the reads that took it (wide = nullptr: none did)
+//   launch_site_items    STAGE 4, one lane per item: the needed-length rule with the read's length; a survivor gets
+//                        req[i] = its request, the others UINT64_MAX (launch_gt_align's RSBWT_GT_INVALID: not aligned);
+//                        rid[i]; perm_key[i] = the item's longest pass (0: not aligned), perm_idx[i] = i; aligned[q] += 1 per
+//                        survivor; work: SITE_WORK_ALIGNED, SITE_WORK_TOO_LONG (a read over 4,096 symbols)
+//   launch_site_perm     perm = the items ordered by perm_key (launch_gt_align's d_perm); d_tmp: site_perm_tmp_bytes(n)
+//   launch_site_tally    STAGE 5, one lane per item whose verdict is one of the three KEEPs: its value's records into row
+//                        req[i] of the matrices (sample_records.h), carriers[q] += 1; work: SITE_WORK_KEPT, _RECORDS, _UNKNOWN
+enum { SITE_WORK_LEGS = 0, SITE_WORK_HEADS, SITE_WORK_ITEMS, SITE_WORK_ALIGNED, SITE_WORK_KEPT, SITE_WORK_RECORDS, SITE_WORK_UNKNOWN,
+       SITE_WORK_TOO_LONG, SITE_WORK_COUNTERS };
+constexpr uint32_t SITE_NEED_MAX = 0xFFFFFFFEu;
+struct site_item {
+    uint64_t ordinal, read_row;
+    uint32_t q, shard, need, rid;
+};
+struct site_set {
+    unsigned long long *keys;  // [nslots]
+    uint64_t *row;             // [nslots]
+    uint32_t *need;            // [nslots]
+    uint64_t *region;          // [S][2]: a shard's first slot and its slot count - 1
+    uint64_t nslots;           // room: 4 x cap + S
+};
+struct site_tally {
+    const site_item *items;
+    size_t n;
+    const uint64_t *req;     // [n]
+    const uint8_t *verdict;  // [n]
+    const meta_view *meta;   // [S]
+    uint32_t S;
+    const uint64_t *keys;  // [C] ascending
+    uint32_t C, size_of_sample, has_other;
+    uint32_t *strings;
+    long long *copies;
+    unsigned long long *carriers;
+    unsigned long long *work;  // SITE_WORK_COUNTERS counters TALLY_WORK_STRIDE words apart
+};
+size_t site_reads_tmp_bytes(size_t n);
+size_t site_perm_tmp_bytes(size_t n);
+hipError_t launch_site_legs(const void *d_legs, size_t cells, unsigned long long *d_work, hipStream_t stream);
+hipError_t launch_site_rows(const gt_batch &bt, const void *d_legs, const void *d_rows, const unsigned long long *d_nrows, uint64_t cap,
+                            const meta_view *d_meta, uint32_t S, bool tight, void *d_rows_of, const site_set &set, unsigned long long *d_work,
+                            hipStream_t stream);
+hipError_t launch_site_compact(const site_set &set, uint32_t S, uint32_t row_bits, void *d_items, void *d_sort_key, void *d_sort_idx, uint64_t cap,
+                               unsigned long long *d_work, hipStream_t stream);
+hipError_t launch_site_reads(void *d_items, size_t n, uint32_t S, uint32_t row_bits, void *d_sort_key, void *d_sort_idx, void *d_tmp, size_t tmp_bytes,
+                             void *d_rows, void *d_seg, void *d_nreads, hipStream_t stream);
+hipError_t launch_site_over(const void *d_rlen, size_t R, void *d_over, void *d_ofirst, unsigned long long *d_longest, void *d_tmp, size_t tmp_bytes,
+                            hipStream_t stream);
+hipError_t launch_site_wide(const void *d_rows, const void *d_seg, uint32_t S, size_t R, const void *d_over, const void *d_ofirst, void *d_wrows,
+                            void *d_wseg, hipStream_t stream);
+hipError_t launch_site_addr(const void *d_narrow, uint32_t stride, const void *d_wide, uint32_t wide_stride, const void *d_over, const void *d_ofirst,
+                            const void *d_wlen, size_t R, void *d_raddr, void *d_rlen, hipStream_t stream);
+hipError_t launch_site_items(const void *d_items, size_t n, const void *d_rlen, const void *d_off, size_t Q, void *d_req, void *d_rid,
+                             void *d_perm_key, void *d_perm_idx, unsigned long long *d_aligned, unsigned long long *d_work, hipStream_t stream);
+hipError_t launch_site_perm(void *d_perm_key, void *d_perm_idx, size_t n, void *d_key_out, void *d_perm, void *d_tmp, size_t tmp_bytes,
+                            hipStream_t stream);
+hipError_t launch_site_tally(const site_tally &a, hipStream_t stream);
 // (SEL_SHIFT, sample_window, window_samples, window_psi_hint: line_format.h -- shared with the host-side layout test)
 // query / query_exactmatch (query.cpp:87-120) over extracted reads
 hipError_t launch_match_reads(const void *d_reads, const void *d_len, size_t n, uint32_t stride, const void *d_owner,

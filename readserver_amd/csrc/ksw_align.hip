@@ -87,11 +87,19 @@ __global__ __launch_bounds__(64) void gt_align_kernel(gt_align_batch bt, uint32_
         const size_t g = blk * LANES + threadIdx.x;
         const bool active = g < bt.n;
         const size_t i = active ? (bt.perm ? (size_t)bt.perm[g] : g) : 0;
-        uint64_t r0 = 0, rl = 0, w0 = 0, wl = 0, rq = 0;
+        uint64_t rl = 0, w0 = 0, wl = 0, rq = 0;
+        const char *rp = nullptr;
         bool valid = false;
         if (active) {
-            r0 = bt.roff[i];
-            rl = bt.roff[i + 1] - r0;
+            if (bt.rid) {  // (the launch's constant: every lane takes the same side)
+                const uint32_t r = bt.rid[i];
+                rp = reinterpret_cast<const char *>((uintptr_t)bt.raddr[r]);
+                rl = bt.rlen[r];
+            } else {
+                const uint64_t r0 = bt.roff[i];
+                rp = bt.reads + r0;
+                rl = bt.roff[i + 1] - r0;
+            }
             rq = bt.item[i];
             if (rq < bt.Q) {
                 w0 = bt.off[rq];
@@ -104,7 +112,7 @@ __global__ __launch_bounds__(64) void gt_align_kernel(gt_align_batch bt, uint32_
         const ksw::column col = lane_column<HBM>(need, lo, hi, lds, scratch);
         if (col.rows != 0 && active) {
             if (valid) {
-                const int v = ksw::gt_verdict(s, bt.reads + r0, (int)rl, bt.text + w0, (int)wl, bt.pos[rq], ksw::nt4((unsigned char)bt.alt[rq]),
+                const int v = ksw::gt_verdict(s, rp, (int)rl, bt.text + w0, (int)wl, bt.pos[rq], ksw::nt4((unsigned char)bt.alt[rq]),
                                               bt.isalt[rq] != 0, col);
                 verdict[i] = (uint8_t)v;
                 if (work14) {

@@ -11,28 +11,20 @@
 //        XCD's L2 and miss the insert of another XCD; the atomic is performed where all XCDs meet.  Old value empty: the
 //        lane is the CARRIER; equal: a duplicate, done; another key: next slot.  A region has more slots than rows, so a
 //        probe always meets an empty slot.  Which of two equal rows wins does not matter: they would add the same.
-//     3. a carrier reads off[o], off[o + 1] and tallies the whole records of its value.  Up to TALLY_LANE_RECORDS = 16
-//        records its own lane parses; a longer value the whole wave takes, one holder after the other (ballot + broadcast,
-//        lanes striding over the records): read_meta.hip's division of labour.  16: a lane then runs at most 16 binary
-//        searches and 32 adds while its 63 neighbours run theirs, where a wave pass over so few records would leave
-//        three quarters of the lanes idle; above it a lone lane would hold its wave for one search per record (2,000 for
-//        a read of a common sequence) with 63 lanes idle, and the wave does the same in records / 64 passes.
-//        code -> column: binary search over the dictionary's u64 keys (sample_codes.h), in LDS while 8 C <= 32 KiB (five
-//        blocks of 256 threads still share a CU's 160 KiB), else over the copy in HBM.
-//        The adds are agent-scope atomicAdd on the u32 / i64 cells and are not combined inside the wave: lanes differ in
-//        query and column, and integer sums do not depend on the order -- the matrices are bit-identical from run to run.
+//     3. a carrier reads off[o], off[o + 1] and tallies the whole records of its value: sample_records.h (a lane up to 16
+//        records, the wave above that, the dictionary's keys in LDS while 8 C <= 32 KiB).
 //     4. carriers[q] and the work counters: one atomic per wave and distinct query / per wave and pass, the counters 256
 //        bytes apart.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "kernels.h"
+#include "sample_records.h"
 
 namespace rsb {
 
 namespace {
 
-constexpr uint32_t TALLY_LANE_RECORDS = 16;
 constexpr unsigned long long TALLY_EMPTY = ~0ull;
 
 __global__ void __launch_bounds__(256)
@@ -83,54 +75,12 @@ __global__ void sample_status_kernel(const uint64_t *__restrict__ first, size_t 
     status8[7] = 0ull;
 }
 
-struct tally_dict {
-    const uint64_t *keys;  // LDS or HBM
-    uint32_t C;
-};
-
-__device__ __forceinline__ uint32_t tally_column(const tally_dict &d, uint64_t key) {
-    uint32_t lo = 0, hi = d.C;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (d.keys[mid] < key) lo = mid + 1u;
-        else hi = mid;
-    }
-    return lo < d.C && d.keys[lo] == key ? lo : d.C;
-}
-
-// record i of a value at p: one add per matrix; returns 1 when its code is not in the dictionary
-__device__ __forceinline__ uint32_t tally_record(const sample_tally &a, const tally_dict &d, const uint8_t *p, uint64_t cell0) {
-    uint64_t key = 0;
-    for (uint32_t b = 0; b < a.size_of_sample; ++b) key = (key << 8) | p[b];
-    const uint32_t col = tally_column(d, key);
-    if (a.strings) atomicAdd(&a.strings[cell0 + col], 1u);
-    if (a.copies) {
-        const long long c = a.has_other ? (long long)(int)(signed char)p[a.size_of_sample] - 33ll : 1ll;
-        atomicAdd(reinterpret_cast<unsigned long long *>(a.copies) + cell0 + col, (unsigned long long)c);
-    }
-    return col == d.C ? 1u : 0u;
-}
-
-__device__ __forceinline__ void wave_count(unsigned long long *counter, uint32_t mine, uint32_t lane) {
-    // (the sum over the wave of a small per-lane number, one atomic)
-    uint32_t v = mine;
-    for (int s = 32; s > 0; s >>= 1) v += (uint32_t)__shfl_xor((int)v, s, 64);
-    if (lane == 0u && v) atomicAdd(counter, (unsigned long long)v);
-}
-
 template <bool KEYS_IN_LDS>
 __global__ void __launch_bounds__(256)
 sample_tally_kernel(const sample_tally a) {
     extern __shared__ uint64_t lds_keys[];
-    tally_dict d;
-    d.C = a.C;
-    if (KEYS_IN_LDS) {
-        for (uint32_t i = threadIdx.x; i < a.C; i += blockDim.x) lds_keys[i] = a.keys[i];
-        __syncthreads();
-        d.keys = lds_keys;
-    } else {
-        d.keys = a.keys;
-    }
+    const tally_dict d = tally_dict_of<KEYS_IN_LDS>(a.keys, a.C, lds_keys);
+    const tally_cells cells = {a.strings, a.copies, a.size_of_sample, a.has_other};
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t R = a.size_of_sample + (a.has_other ? 2u : 0u);
@@ -179,28 +129,9 @@ sample_tally_kernel(const sample_tally a) {
         nrec = (b1 - b0) / R;  // (the tail that is no whole record is dropped)
         val = mv.bytes + b0;
     }
-    const uint64_t width = (uint64_t)a.C + 1ull;
-    uint32_t unknown = 0;
-    if (nrec != 0ull && nrec <= TALLY_LANE_RECORDS)
-        for (uint32_t i = 0; i < (uint32_t)nrec; ++i) unknown += tally_record(a, d, val + (size_t)i * R, q * width);
-    uint64_t longs = __builtin_amdgcn_ballot_w64(nrec > TALLY_LANE_RECORDS);
-    while (longs) {
-        const int j = __builtin_ctzll(longs);
-        longs &= longs - 1ull;
-        const uint64_t wn = __shfl(nrec, j, 64), wq = __shfl(q, j, 64);
-        const uint8_t *wv = reinterpret_cast<const uint8_t *>(__shfl((uint64_t)(uintptr_t)val, j, 64));
-        for (uint64_t i = lane; i < wn; i += 64u) unknown += tally_record(a, d, wv + i * R, wq * width);
-    }
+    const uint32_t unknown = tally_values(cells, d, a.C, lane, nrec, val, q);
     // ---- carriers[q]: one add per wave and distinct query
-    uint64_t left = __builtin_amdgcn_ballot_w64(carrier);
-    const uint64_t carriers_in_wave = (uint64_t)__builtin_popcountll(left);
-    while (left) {
-        const int j = __builtin_ctzll(left);
-        const uint64_t q0 = __shfl(q, j, 64);
-        const uint64_t same = __builtin_amdgcn_ballot_w64(carrier && q == q0);
-        if (a.carriers && lane == (uint32_t)j) atomicAdd(&a.carriers[q0], (unsigned long long)__builtin_popcountll(same));
-        left &= ~same;
-    }
+    const uint64_t carriers_in_wave = wave_count_by_query(a.carriers, carrier, q, lane);
     // ---- the counters, 256 bytes apart
     const uint64_t heads = __builtin_amdgcn_ballot_w64(head), losts = __builtin_amdgcn_ballot_w64(lost);
     if (lane == 0u) {

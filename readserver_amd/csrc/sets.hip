@@ -29,6 +29,7 @@
 #include "../../include/rsbwt.h"
 #include "capi_guard.h"
 #include "capi_internal.h"
+#include "gt_span_rule.h"
 #include "meta_file.h"
 #include "sample_codes.h"
 #include "service.h"
@@ -1687,23 +1688,37 @@ int gt_make_plan(const char *text, const uint64_t *off, size_t Q, const uint64_t
     return RSBWT_OK;
 }
 
-// One device group's share: the batch goes up once, every (item, shard of the group) is narrowed by one launch, and --
-// for the read calls -- the legs' rows are made, walked and filtered where they are; what comes back is the legs and
-// the rows the filter kept.
-int gt_group_run(rsbwt_set_t *s, dev_group *g, const gt_plan &pl, const char *t0, bool want_rows, gt_group_out *out) {
-    group_call gc(g, true);
-    if (gc.rc) return gc.rc;
+// The front of a group's share, in gc.la: the batch uploaded, the narrowing launch enqueued.  d_wk: [0] lengthening steps,
+// [1] rows kept, [2] rows whose walk did not end, zeroed.  d_extra: extra_bytes more for the caller, behind everything else.
+struct gt_front {
+    gt_batch bt;
+    uint8_t *d_legs = nullptr, *d_pairs = nullptr, *d_matches = nullptr, *d_keptq = nullptr, *d_first = nullptr, *d_over = nullptr, *d_wk = nullptr,
+            *d_tmp = nullptr, *d_extra = nullptr;
+    size_t tmp_bytes = 0;
+};
+int gt_front_enqueue(dev_group *g, group_call &gc, const gt_plan &pl, const char *t0, size_t extra_bytes, gt_front *f) {
     hipStream_t st = gc.st;
     const uint32_t S = (uint32_t)g->idx.size();
     const size_t Q = pl.q_off.size(), slots = pl.slot_query.size(), N = pl.nitems, cells = (size_t)S * N;
     const size_t a_text = al256(pl.text_len + 1), a_np = al256(pl.text_len * 4 + 4), a_q8 = al256(Q * 8), a_q4 = al256(Q * 4), a_s4 = al256(slots * 4),
                  a_legs = al256(cells * sizeof(gt_leg)), a_pairs = al256(cells * 16), a_i = al256((N + 1) * 8),
                  tmp_bytes = interval_rows_scan_bytes(N + 1);
-    hipError_t e = g->scratch.take(a_text + a_np + 2 * a_q8 + a_q4 + 2 * a_s4 + a_legs + a_pairs + 3 * a_i + 512 + tmp_bytes + 256, st, &gc.la);
+    hipError_t e = g->scratch.take(a_text + a_np + 2 * a_q8 + a_q4 + 2 * a_s4 + a_legs + a_pairs + 3 * a_i + 512 + al256(tmp_bytes) + 256 + extra_bytes, st,
+                                   &gc.la);
     if (e != hipSuccess) return fail_hip(e, "scratch for the SiteMatch legs");
     uint8_t *d_text = (uint8_t *)gc.la.p, *d_np = d_text + a_text, *d_qoff = d_np + a_np, *d_qpos = d_qoff + a_q8, *d_qlen = d_qpos + a_q8,
             *d_sq = d_qlen + a_q4, *d_stile = d_sq + a_s4, *d_legs = d_stile + a_s4, *d_pairs = d_legs + a_legs, *d_matches = d_pairs + a_pairs,
             *d_keptq = d_matches + a_i, *d_first = d_keptq + a_i, *d_over = d_first + a_i, *d_wk = d_over + 256, *d_tmp = d_wk + 256;
+    f->d_legs = d_legs;
+    f->d_pairs = d_pairs;
+    f->d_matches = d_matches;
+    f->d_keptq = d_keptq;
+    f->d_first = d_first;
+    f->d_over = d_over;
+    f->d_wk = d_wk;
+    f->d_tmp = d_tmp;
+    f->tmp_bytes = tmp_bytes;
+    f->d_extra = d_tmp + al256(tmp_bytes) + 256;
     if (pl.text_len) {
         HIP_OK(hipMemcpyAsync(d_text, t0, pl.text_len, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(d_np, pl.nprev.data(), pl.text_len * 4, hipMemcpyHostToDevice, st));
@@ -1714,7 +1729,7 @@ int gt_group_run(rsbwt_set_t *s, dev_group *g, const gt_plan &pl, const char *t0
     HIP_OK(hipMemcpyAsync(d_sq, pl.slot_query.data(), slots * 4, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_stile, pl.slot_tile.data(), slots * 4, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemsetAsync(d_wk, 0, 256, st));
-    gt_batch bt;
+    gt_batch &bt = f->bt;
     bt.text = (const char *)d_text;
     bt.nprev = (const uint32_t *)d_np;
     bt.q_off = (const uint64_t *)d_qoff;
@@ -1726,9 +1741,29 @@ int gt_group_run(rsbwt_set_t *s, dev_group *g, const gt_plan &pl, const char *t0
     bt.k = pl.k;
     bt.step = pl.step;
     bt.M = pl.M;
-    unsigned long long *wk = (unsigned long long *)d_wk;  // [0] lengthening steps, [1] rows kept, [2] rows whose walk did not end
-    e = launch_gt_narrow(g->d_views, S, bt, d_legs, d_pairs, wk, st);
+    e = launch_gt_narrow(g->d_views, S, bt, d_legs, d_pairs, (unsigned long long *)d_wk, st);
     if (e != hipSuccess) return fail_hip(e, "SiteMatch narrowing kernel launch");
+    return RSBWT_OK;
+}
+
+// One device group's share: the batch goes up once, every (item, shard of the group) is narrowed by one launch, and --
+// for the read calls -- the legs' rows are made, walked and filtered where they are; what comes back is the legs and
+// the rows the filter kept.
+int gt_group_run(rsbwt_set_t *s, dev_group *g, const gt_plan &pl, const char *t0, bool want_rows, gt_group_out *out) {
+    group_call gc(g, true);
+    if (gc.rc) return gc.rc;
+    hipStream_t st = gc.st;
+    const uint32_t S = (uint32_t)g->idx.size();
+    const size_t N = pl.nitems, cells = (size_t)S * N;
+    gt_front f;
+    const int rc = gt_front_enqueue(g, gc, pl, t0, 0, &f);
+    if (rc) return rc;
+    const gt_batch &bt = f.bt;
+    uint8_t *d_legs = f.d_legs, *d_pairs = f.d_pairs, *d_matches = f.d_matches, *d_keptq = f.d_keptq, *d_first = f.d_first, *d_over = f.d_over,
+            *d_wk = f.d_wk, *d_tmp = f.d_tmp;
+    const size_t tmp_bytes = f.tmp_bytes;
+    unsigned long long *wk = (unsigned long long *)d_wk;
+    hipError_t e = hipSuccess;
     out->legs.resize(cells);
     HIP_OK(hipMemcpyAsync(out->legs.data(), d_legs, cells * sizeof(gt_leg), hipMemcpyDeviceToHost, st));
     uint64_t total = 0;
@@ -1884,8 +1919,7 @@ int gt_call(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, con
             const size_t ri = (size_t)(std::lower_bound(ids.begin(), ids.end(), std::make_pair(r.shard, r.read_row)) - ids.begin());
             const uint32_t q = pl.slot_query[r.item >> 1];
             if (r.pending) {
-                const uint64_t end = rec_of(r.shard, r.item).b, postfix = (uint64_t)str[ri].size() - r.offset;
-                if (pl.q_pos[q] - end > postfix - pl.k + 4ull) continue;
+                if (!gt_left_row_stays(pl.q_pos[q], rec_of(r.shard, r.item).b, r.offset, pl.k, (uint64_t)str[ri].size())) continue;
             }
             (*reads)[(size_t)q * S + r.shard].push_back({r.read_row, std::string()});
             (*reads)[(size_t)q * S + r.shard].back().second = str[ri];
@@ -3417,6 +3451,388 @@ int set_sample_counts_body(rsbwt_set_t *s, const char *text, const uint64_t *off
     return RSBWT_OK;
 }
 
+// ---- site sample counts (site_counts.hip): SiteMatch's kept reads reduced to per-request sample matrices ----
+// the calling thread's last call: legs, LF steps spent lengthening, candidate rows, rows the span filter kept, of those rows
+// on a head ordinal, distinct reads extracted, (request, read) items aligned, items kept, records added, records with an
+// unknown code
+thread_local uint64_t site_last_work[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+// ... and, while RSBWT_SITE_TIMES=1, the device time of its stages in ms, from events around each stage's launches on the
+// call's stream, summed over the device groups and slices: {narrowing + rows + walks + filter, head test + set + compaction,
+// sort / unique + extraction, length rule + ordering, alignment, tally}
+thread_local double site_last_ms[6] = {0, 0, 0, 0, 0, 0};
+
+struct site_marks {
+    bool on = false;
+    hipStream_t st = nullptr;
+    hipEvent_t ev[12] = {};
+    bool open_[6] = {};
+    double ms[6] = {0, 0, 0, 0, 0, 0};
+    site_marks(hipStream_t stream) : st(stream) {
+        const char *e = getenv("RSBWT_SITE_TIMES");
+        on = e && e[0] == '1' && e[1] == 0;
+    }
+    site_marks(const site_marks &) = delete;
+    void begin(int stage) {
+        if (!on || open_[stage]) return;
+        if (!ev[2 * stage] && (hipEventCreate(&ev[2 * stage]) != hipSuccess || hipEventCreate(&ev[2 * stage + 1]) != hipSuccess)) {
+            on = false;
+            return;
+        }
+        open_[stage] = hipEventRecord(ev[2 * stage], st) == hipSuccess;
+    }
+    void end(int stage) {  // (a stage enqueued twice -- the second extraction's round -- adds up)
+        if (!on || !open_[stage]) return;
+        open_[stage] = false;
+        if (hipEventRecord(ev[2 * stage + 1], st) != hipSuccess || hipEventSynchronize(ev[2 * stage + 1]) != hipSuccess) return;
+        float t = 0;
+        if (hipEventElapsedTime(&t, ev[2 * stage], ev[2 * stage + 1]) == hipSuccess) ms[stage] += t;
+    }
+    ~site_marks() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+constexpr uint32_t SITE_STRIDE = 256;          // the first extraction's stride
+constexpr uint32_t SITE_WIDE_STRIDE = 4096 + 64;  // the second's: a read of RSBWT_KSW_MAX_LEN symbols and padding
+
+struct site_requests {  // a slice's requests beside the plan
+    std::vector<uint64_t> off;  // [mq + 1], off[0] = 0
+    const char *alt = nullptr;
+    const uint8_t *isalt = nullptr;
+    uint32_t lo_w = 1, hi_w = 1;  // the shortest (at least 1) and the longest window
+};
+
+struct site_group_out {
+    std::vector<uint32_t> strings;
+    std::vector<int64_t> copies;
+    std::vector<uint64_t> aligned, carriers;
+    uint64_t work[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double ms[6] = {0, 0, 0, 0, 0, 0};
+};
+
+// a lease beyond a group_call's two: goes back when the call leaves, after the stream has drained
+struct site_lease {
+    dev_group *g;
+    hipStream_t st;
+    scratch_cache::lease l;
+    site_lease(dev_group *grp, hipStream_t stream) : g(grp), st(stream) {}
+    site_lease(const site_lease &) = delete;
+    void drop() {  // (the launches that used it are enqueued: give() asks no more)
+        if (l.slot >= 0) g->scratch.give(l, st);
+        l = scratch_cache::lease();
+    }
+    ~site_lease() {
+        if (l.slot < 0) return;
+        (void)hipStreamSynchronize(st);
+        g->scratch.give(l, st);
+    }
+};
+
+// One device group's share of a slice (site_counts.hip has the stages).  The host reads back, eight bytes each: the row
+// total, the kept rows / rows not located / items, the distinct reads, the reads over the first stride and the longest that
+// fit; then the matrices, the two count vectors and the counters.  Three leases at most are held at a time (gc.la: the
+// batch; gc.lb: rows, set and items; lc: reads and what the alignment and the tally need) plus a launch's own short one,
+// so four calls at once stay inside the cache's 16 slots.
+int site_group_run(rsbwt_set_t *s, dev_group *g, const gt_plan &pl, const char *t0, const site_requests &rq, const sample_dict &d, bool tight,
+                   uint32_t row_bits, bool want_strings, bool want_copies, site_group_out *out) {
+    group_call gc(g, true);
+    if (gc.rc) return gc.rc;
+    hipStream_t st = gc.st;
+    site_lease lc(g, st);
+    site_marks tm(st);
+    tm.begin(0);
+    const uint32_t S = (uint32_t)g->idx.size();
+    const size_t Q = pl.q_off.size(), N = pl.nitems, cells = (size_t)S * N, mcells = Q * ((size_t)d.C + 1);
+    const size_t work_bytes = SITE_WORK_COUNTERS * TALLY_WORK_STRIDE * 8;
+    const size_t a_off = al256((Q + 1) * 8), a_q1 = al256(Q), a_keys = al256((size_t)d.C * 8), a_work = al256(work_bytes);
+    gt_front f;
+    int rc = gt_front_enqueue(g, gc, pl, t0, a_off + 2 * a_q1 + a_keys + a_work + 256, &f);
+    if (rc) return rc;
+    uint8_t *d_off = f.d_extra, *d_alt = d_off + a_off, *d_isalt = d_alt + a_q1, *d_keys = d_isalt + a_q1, *d_work = d_keys + a_keys,
+            *d_sizes = d_work + a_work;  // d_sizes: [0] distinct reads, [1] the longest read that fit
+    unsigned long long *work = (unsigned long long *)d_work, *wk = (unsigned long long *)f.d_wk;
+    HIP_OK(hipMemcpyAsync(d_off, rq.off.data(), (Q + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_alt, rq.alt, Q, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_isalt, rq.isalt, Q, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_keys, d.keys.data(), (size_t)d.C * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(d_work, 0, work_bytes + 256, st));
+    hipError_t e = launch_site_legs(f.d_legs, cells, work, st);
+    if (e == hipSuccess) e = launch_interval_totals(g->d_views, S, f.d_pairs, N, 0, f.d_matches, f.d_keptq, f.d_first, f.d_over, f.d_tmp, f.tmp_bytes, st);
+    if (e != hipSuccess) return fail_hip(e, "leg count and interval-rows kernels");
+    uint64_t total = 0;
+    HIP_OK(hipMemcpyAsync(&total, f.d_first + N * 8, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (want_strings) out->strings.assign(mcells, 0);
+    if (want_copies) out->copies.assign(mcells, 0);
+    out->aligned.assign(Q, 0);
+    out->carriers.assign(Q, 0);
+    std::vector<unsigned long long> hwork(SITE_WORK_COUNTERS * TALLY_WORK_STRIDE, 0);
+    unsigned long long hwk[3] = {0, 0, 0};
+    uint64_t nreads = 0;
+    auto finish = [&]() -> int {  // the counters, once everything is enqueued
+        HIP_OK(hipMemcpyAsync(hwork.data(), d_work, work_bytes, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(hwk, f.d_wk, sizeof hwk, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        auto w = [&](int which) { return (uint64_t)hwork[(size_t)which * TALLY_WORK_STRIDE]; };
+        if (w(SITE_WORK_TOO_LONG) != 0)
+            return fail(RSBWT_EINVAL, "%llu candidate reads longer than %d symbols", (unsigned long long)w(SITE_WORK_TOO_LONG), RSBWT_KSW_MAX_LEN);
+        const uint64_t mine[10] = {w(SITE_WORK_LEGS), hwk[0], total, hwk[1], w(SITE_WORK_HEADS), nreads, w(SITE_WORK_ALIGNED), w(SITE_WORK_KEPT),
+                                   w(SITE_WORK_RECORDS), w(SITE_WORK_UNKNOWN)};
+        for (int i = 0; i < 10; ++i) out->work[i] = mine[i];
+        for (int i = 0; i < 6; ++i) {
+            tm.end(i);
+            out->ms[i] = tm.ms[i];
+        }
+        return RSBWT_OK;
+    };
+    if (total == 0) return finish();
+    if (total >= (1ull << 31)) return fail(RSBWT_ERANGE, "%llu candidate rows in one call: at most 2^31", (unsigned long long)total);
+    // ---- stage 1 (rows, walks, filter) and stages 2, 3a in gc.lb
+    const uint64_t nslots = 4 * total + S;
+    const size_t a8 = al256(total * 8), a4 = al256(total * 4), a_rec = al256(total * sizeof(gt_site_row)), a_s8 = al256((size_t)(S + 1) * 8),
+                 a_region = al256((size_t)S * 16), a_set8 = al256(nslots * 8), a_set4 = al256(nslots * 4), a_items = al256(total * sizeof(site_item)),
+                 reads_tmp = site_reads_tmp_bytes(total);
+    e = g->scratch.take(5 * a8 + 3 * a4 + a_rec + 2 * a_s8 + a_region + 2 * a_set8 + a_set4 + a_items + reads_tmp, st, &gc.lb);
+    if (e != hipSuccess)
+        return fail(RSBWT_ENOMEM, "%llu candidate rows do not fit the device's free memory: %s", (unsigned long long)total, hipGetErrorString(e));
+    uint8_t *d_rows = (uint8_t *)gc.lb.p, *d_rr = d_rows + a8, *d_od = d_rr + a8, *d_sh = d_od + a8, *d_of = d_sh + a4, *d_rec = d_of + a4,
+            *d_rows_of = d_rec + a_rec, *d_seg = d_rows_of + a_s8, *d_region = d_seg + a_s8, *d_skeys = d_region + a_region, *d_srow = d_skeys + a_set8,
+            *d_sneed = d_srow + a_set8, *d_items = d_sneed + a_set4, *d_sort_key = d_items + a_items, *d_sort_idx = d_sort_key + a8,
+            *d_drows = d_sort_idx + a4, *d_reads_tmp = d_drows + a8;
+    e = launch_interval_fill(g->d_views, S, f.d_pairs, N, f.d_first, (size_t)total, d_sh, d_rows, nullptr, nullptr, nullptr, st);
+    if (e == hipSuccess) e = launch_locate(g->scratch, g->d_views, S, d_sh, d_rows, (size_t)total, 0, d_rr, d_od, d_of, nullptr, g->num_cus, st);
+    if (e == hipSuccess) e = launch_gt_filter(f.bt, f.d_legs, f.d_first, d_sh, d_of, d_rr, total, d_rec, wk + 1, st, d_od);
+    if (e != hipSuccess) return fail_hip(e, "row expansion, locate and filter kernel launches");
+    tm.end(0);
+    tm.begin(1);
+    site_set set;
+    set.keys = (unsigned long long *)d_skeys;
+    set.row = (uint64_t *)d_srow;
+    set.need = (uint32_t *)d_sneed;
+    set.region = (uint64_t *)d_region;
+    set.nslots = nslots;
+    e = launch_site_rows(f.bt, f.d_legs, d_rec, wk + 1, total, g->d_meta, S, tight, d_rows_of, set, work, st);
+    if (e == hipSuccess) e = launch_site_compact(set, S, row_bits, d_items, d_sort_key, d_sort_idx, total, work, st);
+    if (e != hipSuccess) return fail_hip(e, "head test and set kernel launches");
+    tm.end(1);
+    uint64_t n = 0;
+    HIP_OK(hipMemcpyAsync(hwk, f.d_wk, sizeof hwk, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(&n, work + (size_t)SITE_WORK_ITEMS * TALLY_WORK_STRIDE, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (hwk[2] != 0)
+        return fail(RSBWT_EINVAL, "%llu candidate rows whose walk to their read's start does not end (a corrupt index, or a read longer than 2^20 symbols)",
+                    hwk[2]);
+    if (hwk[1] > total || n > hwk[1]) return fail(RSBWT_EHIP, "the row filter kept %llu of %llu rows, %llu items", hwk[1], (unsigned long long)total, (unsigned long long)n);
+    if (n == 0) return finish();
+    // ---- stage 3b: the distinct reads
+    tm.begin(2);
+    e = launch_site_reads(d_items, (size_t)n, S, row_bits, d_sort_key, d_sort_idx, d_reads_tmp, reads_tmp, d_drows, d_seg, d_sizes, st);
+    if (e != hipSuccess) return fail_hip(e, "sort and unique of the candidate reads");
+    tm.end(2);
+    HIP_OK(hipMemcpyAsync(&nreads, d_sizes, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    const size_t R = (size_t)nreads;
+    if (R == 0 || R > n) return fail(RSBWT_EHIP, "%zu distinct reads of %llu items", R, (unsigned long long)n);
+    if ((rc = ensure_group_xviews(s, g, st)) != RSBWT_OK) return rc;
+    // ---- the reads and everything behind them in lc; taken again with room for the second extraction if a read needs it
+    const size_t scan_tmp = meta_scan_bytes(R + 1), perm_tmp = site_perm_tmp_bytes((size_t)n);
+    const size_t a_r4 = al256(R * 4), a_r8 = al256((R + 1) * 8), a_n8 = al256((size_t)n * 8), a_n4 = al256((size_t)n * 4), a_n1 = al256((size_t)n),
+                 a_q8 = al256(Q * 8), a_str = want_strings ? al256(mcells * 4) : 0, a_cp = want_copies ? al256(mcells * 8) : 0;
+    uint64_t n_over = 0, longest = 0;
+    uint8_t *d_reads = nullptr, *d_plen = nullptr, *d_rlen = nullptr, *d_overf = nullptr, *d_ofirst = nullptr, *d_scan = nullptr, *d_raddr = nullptr,
+            *d_req = nullptr, *d_rid = nullptr, *d_pkey = nullptr, *d_pidx = nullptr, *d_pkey2 = nullptr, *d_perm = nullptr, *d_ptmp = nullptr,
+            *d_verdict = nullptr, *d_aligned = nullptr, *d_carriers = nullptr, *d_str = nullptr, *d_cp = nullptr, *d_ksw = nullptr, *d_wide = nullptr,
+            *d_wplen = nullptr, *d_wlen = nullptr, *d_wrows = nullptr, *d_wseg = nullptr;
+    size_t ksw_bytes = 0;
+    for (int round = 0; round < 2; ++round) {
+        const size_t W = (size_t)n_over;  // (0 in the first round)
+        ksw_bytes = ksw_scratch_bytes(W ? (uint32_t)RSBWT_KSW_MAX_LEN : std::max<uint32_t>(SITE_STRIDE, rq.hi_w));
+        const size_t a_reads = al256(R * (size_t)SITE_STRIDE), a_wide = al256(W * (size_t)SITE_WIDE_STRIDE), a_w4 = al256(W * 4), a_w8 = al256(W * 8);
+        lc.drop();
+        e = g->scratch.take(a_reads + 2 * a_r4 + 3 * a_r8 + al256(scan_tmp) + a_n8 + 5 * a_n4 + al256(perm_tmp) + a_n1 + 2 * a_q8 + a_str + a_cp +
+                                al256(ksw_bytes) + a_wide + 2 * a_w4 + a_w8 + al256((size_t)(S + 1) * 8) + 256,
+                            st, &lc.l);
+        if (e != hipSuccess)
+            return fail(RSBWT_ENOMEM, "%zu reads, %llu items and %zu matrix cells do not fit the device's free memory: %s", R, (unsigned long long)n, mcells,
+                        hipGetErrorString(e));
+        d_reads = (uint8_t *)lc.l.p;
+        d_plen = d_reads + a_reads;
+        d_rlen = d_plen + a_r4;
+        d_overf = d_rlen + a_r4;
+        d_ofirst = d_overf + a_r8;
+        d_raddr = d_ofirst + a_r8;
+        d_scan = d_raddr + a_r8;
+        d_req = d_scan + al256(scan_tmp);
+        d_rid = d_req + a_n8;
+        d_pkey = d_rid + a_n4;
+        d_pidx = d_pkey + a_n4;
+        d_pkey2 = d_pidx + a_n4;
+        d_perm = d_pkey2 + a_n4;
+        d_ptmp = d_perm + a_n4;
+        d_verdict = d_ptmp + al256(perm_tmp);
+        d_aligned = d_verdict + a_n1;
+        d_carriers = d_aligned + a_q8;
+        d_str = d_carriers + a_q8;
+        d_cp = d_str + a_str;
+        d_ksw = d_cp + a_cp;
+        d_wide = d_ksw + al256(ksw_bytes);
+        d_wplen = d_wide + a_wide;
+        d_wlen = d_wplen + a_w4;
+        d_wrows = d_wlen + a_w4;
+        d_wseg = d_wrows + a_w8;
+        tm.begin(2);
+        HIP_OK(hipMemsetAsync(d_sizes + 8, 0, 8, st));
+        e = launch_extract_ragged(g->scratch, g->d_xviews, S, d_drows, R, d_seg, 1, d_reads, SITE_STRIDE, d_plen, d_rlen, g->num_cus, st);
+        if (e == hipSuccess) e = launch_site_over(d_rlen, R, d_overf, d_ofirst, (unsigned long long *)(d_sizes + 8), d_scan, scan_tmp, st);
+        if (e != hipSuccess) return fail_hip(e, "extraction of the candidate reads");
+        tm.end(2);
+        HIP_OK(hipMemcpyAsync(&n_over, d_ofirst + R * 8, 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(&longest, d_sizes + 8, 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        if (n_over > R) return fail(RSBWT_EHIP, "%llu of %zu reads over the stride", (unsigned long long)n_over, R);
+        if (n_over == W) break;  // (none, or the room is there now)
+        if (round == 1) return fail(RSBWT_EHIP, "the second extraction of the same rows counts other lengths");
+    }
+    tm.begin(2);
+    if (n_over != 0) {
+        e = launch_site_wide(d_drows, d_seg, S, R, d_overf, d_ofirst, d_wrows, d_wseg, st);
+        if (e == hipSuccess)
+            e = launch_extract_ragged(g->scratch, g->d_xviews, S, d_wrows, (size_t)n_over, d_wseg, 1, d_wide, SITE_WIDE_STRIDE, d_wplen, d_wlen, g->num_cus, st);
+        if (e != hipSuccess) return fail_hip(e, "second extraction of the long candidate reads");
+    }
+    e = launch_site_addr(d_reads, SITE_STRIDE, n_over ? d_wide : nullptr, SITE_WIDE_STRIDE, d_overf, d_ofirst, d_wlen, R, d_raddr, d_rlen, st);
+    if (e != hipSuccess) return fail_hip(e, "read address kernel launch");
+    tm.end(2);
+    tm.begin(3);
+    // ---- stage 4: the length rule, the alignment's batch and its order
+    HIP_OK(hipMemsetAsync(d_aligned, 0, 2 * a_q8 + a_str + a_cp, st));  // (aligned, carriers and the matrices lie back to back)
+    HIP_OK(hipMemsetAsync(d_verdict, 0, (size_t)n, st));                 // (0 is no verdict: nothing is kept that the alignment did not answer)
+    e = launch_site_items(d_items, (size_t)n, d_rlen, d_off, Q, d_req, d_rid, d_pkey, d_pidx, (unsigned long long *)d_aligned, work, st);
+    if (e == hipSuccess) e = launch_site_perm(d_pkey, d_pidx, (size_t)n, d_pkey2, d_perm, d_ptmp, perm_tmp, st);
+    if (e != hipSuccess) return fail_hip(e, "length rule and ordering kernel launches");
+    tm.end(3);
+    tm.begin(4);
+    gt_align_batch ab;
+    ab.reads = nullptr;
+    ab.text = f.bt.text;
+    ab.alt = (const char *)d_alt;
+    ab.roff = nullptr;
+    ab.item = (const uint64_t *)d_req;
+    ab.off = (const uint64_t *)d_off;
+    ab.pos = f.bt.q_pos;
+    ab.isalt = d_isalt;
+    ab.n = (size_t)n;
+    ab.Q = Q;
+    ab.perm = (const uint32_t *)d_perm;
+    ab.rid = (const uint32_t *)d_rid;
+    ab.raddr = (const uint64_t *)d_raddr;
+    ab.rlen = (const uint32_t *)d_rlen;
+    const uint32_t hi_rows = n_over ? (uint32_t)RSBWT_KSW_MAX_LEN : std::max<uint32_t>((uint32_t)longest, rq.hi_w);
+    e = launch_gt_align(ab, std::min(rq.lo_w, hi_rows), hi_rows, ksw_scratch_bytes(hi_rows) ? d_ksw : nullptr, d_verdict, nullptr, st);
+    if (e != hipSuccess) return fail_hip(e, "gt alignment kernel launch");
+    tm.end(4);
+    tm.begin(5);
+    // ---- stage 5: the kept reads' records
+    site_tally ta;
+    ta.items = (const site_item *)d_items;
+    ta.n = (size_t)n;
+    ta.req = (const uint64_t *)d_req;
+    ta.verdict = d_verdict;
+    ta.meta = g->d_meta;
+    ta.S = S;
+    ta.keys = (const uint64_t *)d_keys;
+    ta.C = d.C;
+    ta.size_of_sample = d.size_of_sample;
+    ta.has_other = d.has_other;
+    ta.strings = want_strings ? (uint32_t *)d_str : nullptr;
+    ta.copies = want_copies ? (long long *)d_cp : nullptr;
+    ta.carriers = (unsigned long long *)d_carriers;
+    ta.work = work;
+    if ((e = launch_site_tally(ta, st)) != hipSuccess) return fail_hip(e, "site tally kernel launch");
+    tm.end(5);
+    if (want_strings) HIP_OK(hipMemcpyAsync(out->strings.data(), d_str, mcells * 4, hipMemcpyDeviceToHost, st));
+    if (want_copies) HIP_OK(hipMemcpyAsync(out->copies.data(), d_cp, mcells * 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(out->aligned.data(), d_aligned, Q * 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(out->carriers.data(), d_carriers, Q * 8, hipMemcpyDeviceToHost, st));
+    return finish();
+}
+
+int set_site_counts_body(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, const char *alt, const uint8_t *isalt,
+                         int32_t k, int32_t skip, uint64_t M, const uint8_t *codes, size_t C, uint32_t size_of_sample, int has_other, uint32_t *strings,
+                         int64_t *copies, uint64_t *aligned, uint64_t *carriers) {
+    for (uint64_t &w : site_last_work) w = 0;
+    for (double &t : site_last_ms) t = 0;
+    int rc = sample_set_ok(s);
+    if (rc) return rc;
+    sample_dict d;
+    if ((rc = sample_dict_make(codes, C, size_of_sample, has_other, &d)) != RSBWT_OK) return rc;
+    if (!strings && !copies && !aligned && !carriers) return fail(RSBWT_EINVAL, "null argument: no output array");
+    if (Q == 0) return RSBWT_OK;
+    if (!off || !pos || !alt || !isalt || (!text && off[Q] != off[0])) return fail(RSBWT_EINVAL, "null argument");
+    for (size_t q = 0; q < Q; ++q) {
+        if (off[q] > off[q + 1]) return fail(RSBWT_EINVAL, "query %zu: offsets not ascending", q);
+        if (off[q + 1] - off[q] > (uint64_t)RSBWT_KSW_MAX_LEN)
+            return fail(RSBWT_EINVAL, "query %zu: %llu symbols, at most %d", q, (unsigned long long)(off[q + 1] - off[q]), RSBWT_KSW_MAX_LEN);
+    }
+    const size_t S = s->shards.size(), G = s->groups.size(), width = C + 1;
+    if (S > 65535) return fail(RSBWT_EINVAL, "%zu shards: at most 65535", S);
+    uint32_t row_bits = 1;
+    for (rsbwt_t *h : s->shards) {
+        if (!rsbwt_opened_for_reads(h)) return fail(RSBWT_EINVAL, "site sample counts need shards opened with RSBWT_OPEN_READS");
+        while (row_bits < 64 && (h->view.n >> row_bits) != 0) ++row_bits;
+    }
+    if (row_bits > 46) return fail(RSBWT_EINVAL, "a shard of 2^%u symbols: site sample counts take fewer than 2^46", row_bits);
+    // slices: a request number of the set's keys has 24 bits, and a slice's matrices (12 bytes a cell) stay under 1.5 GiB of HBM
+    const size_t SLICE = std::min<size_t>((size_t)1 << 24, std::max<size_t>(1, ((size_t)1 << 27) / width));
+    const bool tight = sample_tight_set();
+    uint64_t work10[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (size_t q0 = 0; q0 < Q; q0 += SLICE) {
+        const size_t mq = std::min(SLICE, Q - q0), mcells = mq * width;
+        uint32_t *st = strings ? strings + q0 * width : nullptr;
+        int64_t *cp = copies ? copies + q0 * width : nullptr;
+        uint64_t *al = aligned ? aligned + q0 : nullptr, *ca = carriers ? carriers + q0 : nullptr;
+        gt_plan pl;
+        if ((rc = gt_make_plan(text, off + q0, mq, pos + q0, k, skip, M, &pl)) != RSBWT_OK) return rc;
+        if (st) memset(st, 0, mcells * 4);
+        if (cp) memset(cp, 0, mcells * 8);
+        if (al) memset(al, 0, mq * 8);
+        if (ca) memset(ca, 0, mq * 8);
+        if (pl.nitems == 0) continue;
+        site_requests rq;
+        rq.off.resize(mq + 1);
+        rq.lo_w = (uint32_t)RSBWT_KSW_MAX_LEN;
+        for (size_t q = 0; q <= mq; ++q) rq.off[q] = off[q0 + q] - off[q0];
+        for (size_t q = 0; q < mq; ++q) {
+            const uint32_t wl = (uint32_t)(rq.off[q + 1] - rq.off[q]);
+            rq.hi_w = std::max(rq.hi_w, wl);
+            if (wl) rq.lo_w = std::min(rq.lo_w, wl);
+        }
+        rq.alt = alt + q0;
+        rq.isalt = isalt + q0;
+        std::vector<site_group_out> outs(G);
+        rc = for_each_group(s, [&](size_t gi) -> int {
+            return site_group_run(s, s->groups[gi], pl, text + off[q0], rq, d, tight, row_bits, st != nullptr, cp != nullptr, &outs[gi]);
+        });
+        if (rc) return rc;
+        for (const site_group_out &o : outs) {
+            for (size_t i = 0; i < mcells; ++i) {
+                if (st) st[i] += o.strings[i];
+                if (cp) cp[i] += o.copies[i];
+            }
+            for (size_t q = 0; q < mq; ++q) {
+                if (al) al[q] += o.aligned[q];
+                if (ca) ca[q] += o.carriers[q];
+            }
+            for (int i = 0; i < 10; ++i) work10[i] += o.work[i];
+            for (int i = 0; i < 6; ++i) site_last_ms[i] += o.ms[i];
+        }
+    }
+    memcpy(site_last_work, work10, sizeof work10);
+    return RSBWT_OK;
+}
+
 int read_file(const char *path, std::string *out) {
     FILE *f = fopen(path, "rb");
     if (!f) return fail(RSBWT_EIO, "cannot open %s", path);
@@ -3640,6 +4056,26 @@ int rsbwt_sample_keys(const uint8_t *codes, size_t C, uint32_t size_of_sample, u
         memcpy(keys, d.keys.data(), C * 8);
         return RSBWT_OK;
     });
+}
+
+int rsbwt_set_site_sample_counts(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, const char *alt,
+                                 const uint8_t *isalt, int32_t k, int32_t skip, uint64_t M, const uint8_t *codes, size_t C, uint32_t size_of_sample,
+                                 int has_other_meta_data, uint32_t *strings, int64_t *copies, uint64_t *aligned, uint64_t *carriers) {
+    return guarded("rsbwt_set_site_sample_counts", [&]() -> int {
+        const int rc = set_site_counts_body(s, text, off, Q, pos, alt, isalt, k, skip, M, codes, C, size_of_sample, has_other_meta_data, strings, copies,
+                                            aligned, carriers);
+        if (rc)
+            for (uint64_t &w : site_last_work) w = 0;
+        return rc;
+    });
+}
+
+void rsbwt_set_site_last_work(uint64_t *work10) {
+    if (work10) memcpy(work10, site_last_work, sizeof site_last_work);
+}
+
+void rsbwt_set_site_last_times(double *ms6) {
+    if (ms6) memcpy(ms6, site_last_ms, sizeof site_last_ms);
 }
 
 int rsbwt_rccl_available(void) { return rccl().ok ? 1 : 0; }

@@ -833,6 +833,62 @@ int rsbwt_set_walk_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, si
                        uint32_t max_steps, uint32_t flags, void *d_ext, void *d_steps, void *d_stop, void *d_support, void *d_last,
                        void *stream);
 void rsbwt_set_walk_last_work(uint64_t *work6);
+/* Unitigs: the maximal unbranched stretch of the reads' k-mer graph through a seed.  A walk follows out-edges only and
+ * runs through a node that two paths enter; a unitig stops on both sides where the graph forks onward, where another path
+ * JOINS, or where the path ends.  W_p, rc, the candidates, E_p, sup, "invalid" and m = max(min_count, 1) are the walk
+ * section's above.
+ * Every seed s has two SIDES: side 0 walks right, side 1 walks left.  Each side is independent of the other and both start
+ * from the seed as given: the right side looks at s[-ctx:] only, the left side at s[:ctx] only.  A side whose own context
+ * is missing (|s| < ctx) or holds a symbol outside ACGT stops with RSBWT_WALK_INVALID at 0 steps; the other side may still
+ * be valid.  One side, with t = s, repeats
+ *   1. max_steps symbols appended on this side: stop with RSBWT_WALK_LIMIT; no evaluation is made
+ *   2. the ONWARD evaluation: the four supports of t in the side's direction, exactly the walk's step;
+ *      live = {c : sup(t, c) >= m}
+ *   3. live empty: stop with RSBWT_WALK_DEAD_END;  two or more: stop with RSBWT_WALK_BRANCH
+ *   4. else c = the one live symbol, t' = t + c walking right, c + t walking left, and v = the NODE entered: t'[-ctx:]
+ *      walking right, t'[:ctx] walking left.  The RETURN evaluation: the four supports of the string v in the OPPOSITE
+ *      direction -- walking right the candidates b + v, walking left v + b; all four are searched, the known one (b0 =
+ *      t[-ctx] walking right, t[ctx-1] walking left: the same string as c's onward candidate, so its support is
+ *      sup(t, c)) included.  Two or more return supports >= m: stop with RSBWT_WALK_JOIN; c is NOT appended, the
+ *      unitig ends at the node before the join
+ *   5. else append c, note its onward support saturated at 2^32 - 1, t = t', go to 1
+ * A seed's interior is taken as given and is not checked; a cycle ends with LIMIT.  The unitig's sequence is
+ * reverse(ext of side 1) + seed + (ext of side 0).
+ *   rsbwt_set_unitigs      with i = 2 * q + side:
+ *                            ext      char[Q][2][max_steps]: the symbols appended on that side in the order they were
+ *                                     appended; 0 past steps[i]
+ *                            steps    u32[Q][2]
+ *                            stop     u8[Q][2], one of RSBWT_WALK_*; 0 is never written
+ *                            support  u32[Q][2][max_steps], may be NULL; 0 past steps[i]
+ *                            last     u64[Q][2][8], may be NULL: [0..3] the onward supports of the evaluation that stopped
+ *                                     the side, [4..7] the return supports when the stop is JOIN, zeros otherwise; all eight
+ *                                     zero for LIMIT and INVALID
+ *                          On a set on one device both sides of every seed advance in ONE launch (the unit of work is the
+ *                          item (seed, side), so a dependent chain is one side long); over several device groups each group
+ *                          evaluates with rsbwt_set_extensions' kernel -- the onward contexts of the items still walking,
+ *                          grouped by direction, then the nodes entered in the opposite direction -- and the host sums and
+ *                          decides: the same outputs and counters, round trips per step.
+ *   rsbwt_set_unitigs_dev  a set on ONE device (several: RSBWT_EINVAL); inputs and outputs in HBM as for
+ *                          rsbwt_set_walk_dev; every byte of every output is written; enqueues on `stream`, synchronises
+ *                          nothing
+ * flags accepts RSBWT_WALK_BOTH_STRANDS only: RSBWT_WALK_LEFT and unknown bits are RSBWT_EINVAL.  ctx outside 1..255,
+ * max_steps (per side) 0 or above 65,535, a NULL required pointer with Q > 0 and offsets that run backwards are
+ * RSBWT_EINVAL; 2 x Q x max_steps >= 2^31 is RSBWT_ERANGE, refused before anything is read; Q = 0 succeeds and touches
+ * nothing; no device RSBWT_ENODEV.  The calls need neither RSBWT_OPEN_READS nor a k-mer table (same answers with any table
+ * or none), build nothing, write nothing a search reads and are re-entrant.  There is no single-handle form: a set of one
+ * serves.
+ * rsbwt_set_unitig_last_work: the calling thread's last host-buffer call: {seeds, appended symbols, candidate searches, LF
+ * steps, lane-passes that fetched a line, starts from a k-mer table entry, onward evaluations, return evaluations}.
+ * Measured on one MI355X (tools/unitig_probe.py, profiles/unitig_probe.json): 10^4 seeds of 31, ctx 30, 200 steps
+ * a side, both strands, on a popBWT of 3.0e7 symbols: 116 ms as one shard, 1,069 ms dealt to eight (the call is its launch);
+ * rsbwt_set_walk right plus left on the same seeds takes 100 and 481 ms, a host loop of rsbwt_set_extensions 637 and 1,364 ms. */
+#define RSBWT_WALK_JOIN 5
+int rsbwt_set_unitigs(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint64_t min_count, uint32_t max_steps,
+                      uint32_t flags, char *ext, uint32_t *steps, uint8_t *stop, uint32_t *support, uint64_t *last);
+int rsbwt_set_unitigs_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, size_t N, uint32_t ctx, uint64_t min_count,
+                          uint32_t max_steps, uint32_t flags, void *d_ext, void *d_steps, void *d_stop, void *d_support, void *d_last,
+                          void *stream);
+void rsbwt_set_unitig_last_work(uint64_t *work8);
 /* The per-read sample table: "which samples carry this read".  Replaces, for the return types All and Samples, the
  * RocksDB lookups of the reference -- sdb->Get(read, &value) in QueryTask::run (src/service/service.cpp:1292-1348), KmerTask::run
  * (:917-975) and DbTask::run (:816-845) -- by a table in HBM keyed by the read's ordinal: per shard off u64[num_strings + 1]

@@ -32,4 +32,5 @@ from .bwt import (  # noqa: F401
     ksw_align,
     gt_align,
     gt_align_last_work,
+    unitig_sequence,
 )

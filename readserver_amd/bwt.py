@@ -23,6 +23,12 @@ def _ptr(a):
 
 # rsbwt_set_walk's stop codes and the flag word of the walk / extension calls (include/rsbwt.h)
 WALK_DEAD_END, WALK_BRANCH, WALK_LIMIT, WALK_INVALID = 1, 2, 3, 4
+WALK_JOIN = 5  # rsbwt_set_unitigs alone: another path enters the node the side would enter
+
+
+def unitig_sequence(seed, right_ext, left_ext):
+    """the sequence of a unitig of ShardSet.unitigs: the left side's symbols are in the order they were appended"""
+    return left_ext[::-1] + seed + right_ext
 
 
 def _walk_flags(left, both_strands):
@@ -905,6 +911,42 @@ class ShardSet:
         w = np.zeros(6, np.uint64)
         lib().rsbwt_set_walk_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
         return dict(zip(("seeds", "appended", "searches", "lf_steps", "passes", "table_starts"), (int(x) for x in w)))
+
+    # -- unitigs (csrc/walk.hip, unitig_kernel): rsbwt_set_unitigs
+    def unitigs(self, seeds, ctx, min_count=1, max_steps=256, both_strands=False, supports=False):
+        """The maximal unitig through every seed (rsbwt_set_unitigs): both sides walk from the seed as given, the right
+        side from its last ctx symbols and the left side from its first, and a side stops where the graph forks onward
+        (WALK_BRANCH), where another path joins the node it would enter (WALK_JOIN: the symbol is not appended), where the
+        path ends (WALK_DEAD_END), after max_steps symbols on that side (WALK_LIMIT) or at once where its own context is
+        missing or holds a symbol outside ACGT (WALK_INVALID).  Returns, per seed, (right, left), each (ext, stop, last):
+        ext the symbols in the order they were appended, last a tuple of 8 -- the four onward supports of the evaluation
+        that stopped the side, then the four return supports when the stop is WALK_JOIN (zeros otherwise; all zeros for
+        LIMIT and INVALID); supports=True: (ext, stop, last, support).  unitig_sequence spells the sequence."""
+        text, off = self._var_text(seeds)
+        Q = len(seeds)
+        ext = np.zeros((Q, 2, max_steps), np.uint8)
+        steps, stop = np.zeros((Q, 2), np.uint32), np.zeros((Q, 2), np.uint8)
+        sup = np.zeros((Q, 2, max_steps), np.uint32) if supports else None
+        last = np.zeros((Q, 2, 8), np.uint64)
+        check(lib().rsbwt_set_unitigs(self._s, _ptr(text), _ptr(off), Q, ctx, min_count, max_steps, _walk_flags(False, both_strands), _ptr(ext),
+                                      _ptr(steps), _ptr(stop), _ptr(sup) if supports else None, _ptr(last)))
+        out = []
+        for q in range(Q):
+            sides = []
+            for d in range(2):
+                n = int(steps[q, d])
+                one = (ext[q, d, :n].tobytes().decode(), int(stop[q, d]), tuple(int(x) for x in last[q, d]))
+                sides.append(one + (tuple(int(x) for x in sup[q, d, :n]),) if supports else one)
+            out.append(tuple(sides))
+        return out
+
+    @staticmethod
+    def unitigs_last_work():
+        """{seeds, appended, searches, lf_steps, passes, table_starts, onward, back} of this thread's last unitigs call:
+        onward and back count the onward and the return evaluations"""
+        w = np.zeros(8, np.uint64)
+        lib().rsbwt_set_unitig_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return dict(zip(("seeds", "appended", "searches", "lf_steps", "passes", "table_starts", "onward", "back"), (int(x) for x in w)))
 
     # -- the per-read sample table (csrc/read_meta.hip): rsbwt_set_meta_* / rsbwt_set_read_meta_var
     @staticmethod

@@ -154,6 +154,16 @@ int walk_host_views(scratch_cache &scratch, hipStream_t st, const shard_view *d_
                     uint32_t *support, uint64_t *last, uint64_t *work6);
 void walk_set_last_work(const uint64_t work6[6]);
 void walk_get_last_work(uint64_t work6[6]);
+//   unitig_check_args     ctx, flags (RSBWT_WALK_BOTH_STRANDS only), max_steps and 2 x Q x max_steps
+//   unitig_host_views     a whole unitig call on one device on `st` (synchronised before it returns): support and last
+//                         are optional; work8[1..7] += the launch's counters
+//   unitig_set / get_last_work: what rsbwt_set_unitig_last_work reports for the calling thread
+int unitig_check_args(uint32_t ctx, uint32_t flags, uint32_t max_steps, size_t Q);
+int unitig_host_views(scratch_cache &scratch, hipStream_t st, const shard_view *d_views, uint32_t S, const char *t0, const uint64_t *rel, size_t Q,
+                      size_t N, uint32_t ctx, uint64_t min_count, uint32_t max_steps, uint32_t flags, char *ext, uint32_t *steps, uint8_t *stop,
+                      uint32_t *support, uint64_t *last, uint64_t *work8);
+void unitig_set_last_work(const uint64_t work8[8]);
+void unitig_get_last_work(uint64_t work8[8]);
 // ksw_align.hip behind rsbwt_gt_align (capi.hip) and the aligned set calls (sets.hip): a host batch checked (null, item < Q,
 // lengths 1..4096: RSBWT_EINVAL), ordered by length, aligned on `device` and waited for; work14 += {reads, reads by
 // verdict 1..13}.  gt_align_set / get_last_work: what rsbwt_gt_align_last_work reports for the calling thread (null: zeros)

@@ -416,6 +416,13 @@ hipError_t launch_walk(const shard_view *d_shards, uint32_t nshards, const walk_
                        void *d_last, unsigned long long *d_work, hipStream_t stream);
 hipError_t launch_extensions(const shard_view *d_shards, uint32_t nshards, const walk_batch &bt, void *d_counts, unsigned long long *d_work,
                              hipStream_t stream);
+//   launch_unitigs: a workgroup per 8 items (4 seeds x 2 sides; item i = 2 * seed + side, side 1 walks left) walks them over
+//     all nshards shards, stopping where another path joins; bt.flags holds RSBWT_WALK_BOTH_STRANDS at the most.  d_ext
+//     char[2Q][max_steps] and d_support u32[2Q][max_steps] (optional) are zeroed on `stream`; d_steps u32[2Q], d_stop u8[2Q]
+//     and d_last u64[2Q][8] (optional) are written for every item; d_work [1..5] as launch_walk's, [6..7] += onward and
+//     return evaluations
+hipError_t launch_unitigs(const shard_view *d_shards, uint32_t nshards, const walk_batch &bt, void *d_ext, void *d_steps, void *d_stop,
+                          void *d_support, void *d_last, unsigned long long *d_work, hipStream_t stream);
 // ksw_align.hip: ksw_align of the reference's ksw.c and align_gt_read over it (ksw_pass.h), one lane per item.  A block is
 // one wave of 64 items and belongs to the LENGTH CLASS of its longest pass: at most 32, 64, 104, 160 or KSW_LDS_ROWS rows
 // -- the column lives in LDS, the launch's LDS sized for the class -- or more: the column lives in d_scratch

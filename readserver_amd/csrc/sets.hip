@@ -33,6 +33,7 @@
 #include "meta_file.h"
 #include "sample_codes.h"
 #include "service.h"
+#include "unitig_rule.h"
 
 using namespace rsb;
 
@@ -2598,6 +2599,111 @@ int walk_by_steps(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t 
     }
     return RSBWT_OK;
 }
+
+// The unitigs of a set over several device groups: per step the groups evaluate the onward contexts of the items still
+// walking, the right-walking ones in one call and the left-walking ones in another (a call has one direction); the host
+// sums over the shards and applies unitig_rule.h's onward half; the nodes entered are then evaluated in the opposite
+// direction, and the host sums and decides -- unitig_kernel's step, on the host.  work8 as unitig_host_views'.
+int unitigs_by_steps(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint64_t m, uint32_t max_steps, uint32_t flags,
+                     char *ext, uint32_t *steps, uint8_t *stop, uint32_t *support, uint64_t *last, uint64_t *work8) {
+    const size_t S = s->shards.size(), items = 2 * Q;
+    memset(ext, 0, items * (size_t)max_steps);
+    if (support) memset(support, 0, items * (size_t)max_steps * 4);
+    if (last) memset(last, 0, items * 64);
+    std::vector<std::string> cur(items);  // an item's context
+    std::vector<size_t> live;
+    for (size_t i = 0; i < items; ++i) {
+        const size_t q = i >> 1;
+        const bool left = (i & 1) != 0;
+        bool valid = off[q + 1] - off[q] >= ctx;
+        if (valid) {
+            cur[i].assign(left ? text + off[q] : text + off[q + 1] - ctx, ctx);
+            for (char ch : cur[i]) valid = valid && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
+        }
+        steps[i] = 0;
+        stop[i] = valid ? 0 : (uint8_t)RSBWT_WALK_INVALID;
+        if (valid) live.push_back(i);
+    }
+    // sums[k][0..3] of the strings str[k] (ctx symbols each) of items `who`, in `who`'s own direction or the opposite one
+    std::string t;
+    std::vector<uint64_t> rel, counts;
+    auto evaluate = [&](const std::vector<size_t> &who, const std::vector<std::string> &str, bool opposite, std::vector<uint64_t> &sums) -> int {
+        sums.assign(who.size() * 4, 0);
+        for (int side = 0; side < 2; ++side) {
+            std::vector<size_t> part;
+            for (size_t k = 0; k < who.size(); ++k)
+                if ((int)(who[k] & 1) == side) part.push_back(k);
+            const size_t np = part.size();
+            if (np == 0) continue;
+            if ((uint64_t)np * ctx >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu sides x %u context symbols: under 2^31 in one call", np, ctx);
+            t.clear();
+            rel.resize(np + 1);
+            for (size_t j = 0; j < np; ++j) {
+                rel[j] = (uint64_t)j * ctx;
+                t += str[part[j]];
+            }
+            rel[np] = (uint64_t)np * ctx;
+            const bool left = (side != 0) != opposite;
+            counts.assign(S * np * 4, 0);
+            const int rc = extension_groups(s, t.data(), rel.data(), np, (size_t)rel[np], ctx, flags | (left ? RSBWT_WALK_LEFT : 0u), counts.data(), work8);
+            if (rc) return rc;
+            for (size_t j = 0; j < np; ++j)
+                for (uint32_t c = 0; c < 4; ++c)
+                    for (size_t p = 0; p < S; ++p) sums[part[j] * 4 + c] += counts[(p * np + j) * 4 + c];
+        }
+        return RSBWT_OK;
+    };
+    std::vector<uint64_t> onward, back;
+    std::vector<size_t> tent, tent_at, next;
+    std::vector<std::string> ctxs, nodes;
+    std::vector<uint32_t> picks;
+    while (!live.empty()) {  // (every item of `live` has fewer than max_steps symbols appended)
+        const size_t nl = live.size();
+        ctxs.clear();
+        for (size_t i : live) ctxs.push_back(cur[i]);
+        int rc = evaluate(live, ctxs, false, onward);
+        if (rc) return rc;
+        work8[6] += nl;
+        tent.clear(), tent_at.clear(), nodes.clear(), picks.clear(), next.clear();
+        for (size_t k = 0; k < nl; ++k) {
+            const size_t i = live[k];
+            uint32_t pick = 0;
+            const uint32_t why = unitig_onward(&onward[k * 4], m, steps[i], max_steps, &pick);
+            if (why != UNITIG_GO) {
+                stop[i] = (uint8_t)why;
+                if (last)
+                    for (int c = 0; c < 4; ++c) last[8 * i + c] = onward[k * 4 + c];
+                continue;
+            }
+            tent.push_back(i);
+            tent_at.push_back(k);
+            picks.push_back(pick);
+            nodes.push_back((i & 1) ? std::string(1, "ACGT"[pick]) + cur[i].substr(0, ctx - 1) : cur[i].substr(1) + "ACGT"[pick]);
+        }
+        if (tent.empty()) break;  // (every item stopped)
+        if ((rc = evaluate(tent, nodes, true, back)) != RSBWT_OK) return rc;
+        work8[7] += tent.size();
+        for (size_t k = 0; k < tent.size(); ++k) {
+            const size_t i = tent[k];
+            const uint64_t *on = &onward[tent_at[k] * 4];
+            if (unitig_return(&back[k * 4], m) != UNITIG_GO) {
+                stop[i] = (uint8_t)RSBWT_WALK_JOIN;
+                if (last)
+                    for (int c = 0; c < 4; ++c) last[8 * i + c] = on[c], last[8 * i + 4 + c] = back[k * 4 + c];
+                continue;
+            }
+            const size_t at = i * (size_t)max_steps + steps[i];
+            ext[at] = "ACGT"[picks[k]];
+            if (support) support[at] = unitig_saturate(on[picks[k]]);
+            work8[1] += 1;
+            cur[i] = nodes[k];
+            if (++steps[i] == max_steps) stop[i] = (uint8_t)RSBWT_WALK_LIMIT;
+            else next.push_back(i);
+        }
+        live.swap(next);
+    }
+    return RSBWT_OK;
+}
 }  // namespace
 
 int rsbwt_set_extensions(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint32_t flags, uint64_t *counts) {
@@ -2676,6 +2782,65 @@ int rsbwt_set_walk_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, si
 
 void rsbwt_set_walk_last_work(uint64_t *work6) {
     if (work6) walk_get_last_work(work6);
+}
+
+int rsbwt_set_unitigs(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint64_t min_count, uint32_t max_steps,
+                      uint32_t flags, char *ext, uint32_t *steps, uint8_t *stop, uint32_t *support, uint64_t *last) {
+    return guarded("rsbwt_set_unitigs", [&]() -> int {
+        unitig_set_last_work(nullptr);
+        int rc = walk_set_check(s);
+        if (rc) return rc;
+        if ((rc = unitig_check_args(ctx, flags, max_steps, Q)) != RSBWT_OK) return rc;
+        std::vector<uint64_t> rel;
+        size_t N = 0;
+        if ((rc = match_check_batch(text, off, Q, &rel, &N)) != RSBWT_OK) return rc;
+        if (Q == 0) return RSBWT_OK;
+        if (!ext || !steps || !stop) return fail(RSBWT_EINVAL, "null argument");
+        const uint64_t m = min_count ? min_count : 1ull;
+        const char *t0 = N ? text + off[0] : nullptr;
+        uint64_t work8[8] = {Q, 0, 0, 0, 0, 0, 0, 0};
+        if (s->groups.size() == 1) {  // both sides of every seed in one launch
+            dev_group *g = s->groups[0];
+            group_call gc(g);
+            if (gc.rc) return gc.rc;
+            rc = unitig_host_views(g->scratch, gc.st, g->d_views, (uint32_t)g->idx.size(), t0, rel.data(), Q, N, ctx, m, max_steps, flags, ext, steps,
+                                   stop, support, last, work8);
+        } else {
+            rc = unitigs_by_steps(s, t0, rel.data(), Q, ctx, m, max_steps, flags, ext, steps, stop, support, last, work8);
+        }
+        if (rc) return rc;
+        unitig_set_last_work(work8);
+        return RSBWT_OK;
+    });
+}
+
+int rsbwt_set_unitigs_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, size_t N, uint32_t ctx, uint64_t min_count,
+                          uint32_t max_steps, uint32_t flags, void *d_ext, void *d_steps, void *d_stop, void *d_support, void *d_last,
+                          void *stream) {
+    dev_group *g = nullptr;
+    int rc = one_device_group(s, &g);
+    if (rc) return rc;
+    if ((rc = unitig_check_args(ctx, flags, max_steps, Q)) != RSBWT_OK) return rc;
+    if (Q == 0) return RSBWT_OK;
+    if (!d_text || !d_off || !d_ext || !d_steps || !d_stop) return fail(RSBWT_EINVAL, "null argument");
+    if (N >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu positions in one call: at most 2^31 - 1", N);
+    for (rsbwt_t *h : s->shards)
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
+    walk_batch bt;
+    bt.text = (const char *)d_text;
+    bt.off = (const uint64_t *)d_off;
+    bt.Q = Q;
+    bt.N = N;
+    bt.ctx = ctx;
+    bt.max_steps = max_steps;
+    bt.min_count = min_count ? min_count : 1ull;
+    bt.flags = flags;
+    const hipError_t e = launch_unitigs(g->d_views, (uint32_t)g->idx.size(), bt, d_ext, d_steps, d_stop, d_support, d_last, nullptr, (hipStream_t)stream);
+    return e == hipSuccess ? RSBWT_OK : fail_hip(e, "unitig kernel launch");
+}
+
+void rsbwt_set_unitig_last_work(uint64_t *work8) {
+    if (work8) unitig_get_last_work(work8);
 }
 
 static size_t hits_1mm_scratch_one(const rsbwt_set_t *s, size_t m, uint32_t k) {

@@ -27,6 +27,8 @@
 //     most, whatever the data says.
 // extension_kernel is the evaluation without the decision: a wave owns (8 seeds, one shard) and writes that shard's
 // counts.  Sets over several device groups walk with it, one round trip per step (sets.hip).
+// unitig_kernel is the walk both ways with the joins looked at: the unit of work is the item (seed, side), and a step
+// evaluates onward and then, in the opposite direction, the node the one live symbol enters (unitig_rule.h: the decision).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -38,6 +40,7 @@
 #include "line_format.h"
 #include "match_lanes.h"
 #include "rank_device.h"
+#include "unitig_rule.h"
 #include "wave_lines.h"
 
 namespace rsb {
@@ -320,6 +323,156 @@ walk_kernel(const shard_view *__restrict__ shards, const uint32_t nshards, const
     walk_add_work(work, lane, tally, appended);
 }
 
+// ---- unitigs: both ways from the seed, stopping where another path joins (include/rsbwt.h) ----
+// The unit of work is the ITEM (seed, side): side 0 walks right from s[-ctx:], side 1 left from s[:ctx], each with a ring
+// of its own.  A workgroup owns 8 items = 4 seeds x 2 sides, a wave's lanes are (item, base, strand), item = lane >> 3 =
+// output index i - 8 * blockIdx.x, and the waves share the shards as in walk_kernel.  A step is two evaluations through ONE
+// call site of walk_search (the pass loop): ONWARD, the walk's own; then, for the items that found exactly one live symbol,
+// RETURN: the node entered, searched in the opposite direction.  The tentative symbol goes into the ring where the context
+// moves to, so with the head moved on the ring holds exactly that node.
+constexpr uint32_t UNITIG_ITEMS = 8;  // items of a wave's lanes: 4 seeds x 2 sides
+
+__device__ __forceinline__ void unitig_load_rings(const walk_batch &bt, size_t first_q, uint8_t (*ring)[WALK_RING], uint32_t *bad, uint32_t tid,
+                                                  uint32_t nthreads) {
+    const uint8_t *text = reinterpret_cast<const uint8_t *>(bt.text);
+    for (uint32_t it = 0; it < UNITIG_ITEMS; ++it) {
+        const size_t q = first_q + (it >> 1);
+        const uint64_t Lq = walk_seed_len(bt, q);
+        if (Lq < bt.ctx) continue;
+        const uint64_t from = (it & 1u) ? bt.off[q] : bt.off[q + 1] - bt.ctx;  // the side is the item's
+        for (uint32_t i = tid; i < bt.ctx; i += nthreads) {
+            const uint32_t r = ms_rank(text[from + i]);
+            ring[it][i] = (uint8_t)r;
+            if (r == 0u) bad[it] = 1u;
+        }
+    }
+}
+
+template <int NW>  // the waves of a workgroup, as walk_kernel's
+__global__ void __launch_bounds__(64 * NW)
+unitig_kernel(const shard_view *__restrict__ shards, const uint32_t nshards, const walk_batch bt, char *__restrict__ ext,
+              uint32_t *__restrict__ steps_out, uint8_t *__restrict__ stop_out, uint32_t *__restrict__ support, unsigned long long *__restrict__ last,
+              unsigned long long *__restrict__ work) {
+    __shared__ uint4 s_stage[NW][64 * SLOT_U4];
+    __shared__ uint8_t s_ring[UNITIG_ITEMS][WALK_RING];
+    __shared__ unsigned long long s_part[NW][UNITIG_ITEMS * 4];
+    __shared__ uint32_t s_bad[UNITIG_ITEMS];
+    __shared__ uint32_t s_live, s_tent;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint4 *stage = s_stage[wave];
+    const uint32_t stage_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_void_ptr)stage);
+    const staged_line L = {own_stage_row(stage, lane), lane & 7u};
+    const uint32_t item = lane >> 3, base = (lane >> 1) & 3u, rev = lane & 1u;
+    const bool both = (bt.flags & RSBWT_WALK_BOTH_STRANDS) != 0u, left = (item & 1u) != 0u;
+    const size_t first_q = (size_t)blockIdx.x * (UNITIG_ITEMS / 2u), q = first_q + (item >> 1);
+    const size_t i = (size_t)blockIdx.x * UNITIG_ITEMS + item;  // = 2 * q + side
+    const bool writer = wave == 0u && (lane & 7u) == 0u;        // the one lane that stores its item's answers
+
+    if (threadIdx.x < UNITIG_ITEMS) s_bad[threadIdx.x] = 0u;
+    __syncthreads();
+    unitig_load_rings(bt, first_q, s_ring, s_bad, threadIdx.x, blockDim.x);
+    __syncthreads();
+
+    // the item's state, the same in every lane of the item in every wave: a function of the sums in LDS alone
+    bool walking = q < bt.Q && walk_seed_len(bt, q) >= bt.ctx && s_bad[item] == 0u;
+    bool tent = false;  // a tentative symbol waits for its node's return evaluation
+    uint32_t nsteps = 0, head = 0, next_head = 0, pick = 0;
+    uint32_t appended = 0, n_onward = 0, n_return = 0;  // (the writer's)
+    uint64_t sums[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the step's: [0..3] onward, [4..7] return
+    walk_tally tally;
+    // the writer's stores when its item stops: LIMIT and INVALID leave zeros in last
+    auto stopped = [&](uint32_t why) {
+        steps_out[i] = nsteps;
+        stop_out[i] = (uint8_t)why;
+        if (last) {
+            const bool zeros = why == RSBWT_WALK_LIMIT || why == RSBWT_WALK_INVALID;
+            for (uint32_t b = 0; b < 8u; ++b) last[8u * i + b] = zeros || (b >= 4u && why != RSBWT_WALK_JOIN) ? 0ull : sums[b];
+        }
+    };
+    if (writer && q < bt.Q && !walking) stopped(RSBWT_WALK_INVALID);  // (a side whose sibling walks writes here, once)
+
+    for (uint32_t it = 0; it < bt.max_steps; ++it) {  // (a walking item appends one symbol per round, or stops)
+#pragma nounroll
+        for (uint32_t pass = 0; pass < 2u; ++pass) {  // 0: onward; 1: return, of the items that hold a tentative symbol
+            if (pass != 0u && s_tent == 0u) break;    // (LDS after a barrier: the same for every lane of the workgroup)
+            const walk_cand cd = {s_ring[item], pass != 0u ? next_head : head, bt.ctx, base + 1u, left != (pass != 0u), rev != 0u};
+            const bool go = walking && (pass == 0u || tent) && (both || rev == 0u);
+            unsigned long long cnt = 0;
+            for (uint32_t sid = wave; sid < nshards; sid += (uint32_t)NW) cnt += walk_search(shards + sid, go, cd, lane, stage_lds, L, tally);
+            cnt += __shfl_xor(cnt, 1, 64);  // the two strands
+            if (rev == 0u) s_part[wave][item * 4u + base] = cnt;
+            __syncthreads();
+            if (pass == 0u) {
+                if (walking) {
+                    for (uint32_t b = 0; b < 4u; ++b) {
+                        sums[b] = 0;
+                        for (uint32_t w = 0; w < (uint32_t)NW; ++w) sums[b] += s_part[w][item * 4u + b];
+                    }
+                    if (writer) ++n_onward;
+                    const uint32_t why = unitig_onward(sums, bt.min_count, nsteps, bt.max_steps, &pick);
+                    if (why == UNITIG_GO) {
+                        // the node entered: the tentative symbol where the context moves to, the head moved on
+                        tent = true;
+                        if (left) {
+                            next_head = head == 0u ? bt.ctx - 1u : head - 1u;
+                            if (writer) s_ring[item][next_head] = (uint8_t)(pick + 1u);
+                        } else {
+                            if (writer) s_ring[item][head] = (uint8_t)(pick + 1u);
+                            next_head = head + 1u == bt.ctx ? 0u : head + 1u;
+                        }
+                    } else {
+                        walking = false;
+                        if (writer) stopped(why);
+                    }
+                }
+                if (wave == 0u) {  // (every lane of wave 0 is in the ballot)
+                    const uint64_t held = __builtin_amdgcn_ballot_w64(tent && (lane & 7u) == 0u);
+                    if (lane == 0u) s_tent = (uint32_t)__builtin_popcountll(held);
+                }
+                __syncthreads();
+            }
+        }
+        if (tent) {  // (the return pass ran: s_tent counted this item)
+            tent = false;
+            for (uint32_t b = 0; b < 4u; ++b) {
+                sums[4u + b] = 0;
+                for (uint32_t w = 0; w < (uint32_t)NW; ++w) sums[4u + b] += s_part[w][item * 4u + b];
+            }
+            if (writer) ++n_return;
+            if (unitig_return(sums + 4, bt.min_count) != UNITIG_GO) {
+                walking = false;  // (the ring stays advanced: nobody reads it again)
+                if (writer) stopped(RSBWT_WALK_JOIN);
+            } else {
+                if (writer) {
+                    const size_t at = i * (size_t)bt.max_steps + nsteps;
+                    ext[at] = "ACGT"[pick];
+                    if (support) support[at] = unitig_saturate(sums[pick]);
+                    ++appended;
+                }
+                head = next_head;
+                if (++nsteps == bt.max_steps) {
+                    walking = false;
+                    if (writer) stopped(RSBWT_WALK_LIMIT);
+                }
+            }
+        }
+        if (wave == 0u) {
+            const uint64_t still = __builtin_amdgcn_ballot_w64(walking && (lane & 7u) == 0u);
+            if (lane == 0u) s_live = (uint32_t)__builtin_popcountll(still);
+        }
+        __syncthreads();
+        if (s_live == 0u) break;  // (LDS after a barrier: the same for every lane of the workgroup)
+    }
+    walk_add_work(work, lane, tally, appended);
+    if (work) {
+        const unsigned long long s6 = ms_wave_sum(n_onward), s7 = ms_wave_sum(n_return);
+        if (lane == 0u) {
+            if (s6) atomicAdd(&work[6], s6);
+            if (s7) atomicAdd(&work[7], s7);
+        }
+    }
+}
+
 // One evaluation per (seed, shard): counts[shard][q][base].  Wave u of the grid owns seeds 8 * (u / nshards) .. + 7 in
 // shard u % nshards; the four waves of a workgroup keep their own rings.
 __global__ void __launch_bounds__(64 * WG_WAVES)
@@ -356,6 +509,11 @@ extension_kernel(const shard_view *__restrict__ shards, const uint32_t nshards, 
 }
 
 thread_local uint64_t walk_last[6] = {0, 0, 0, 0, 0, 0};
+thread_local uint64_t unitig_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+static_assert(UNITIG_DEAD_END == RSBWT_WALK_DEAD_END && UNITIG_BRANCH == RSBWT_WALK_BRANCH && UNITIG_LIMIT == RSBWT_WALK_LIMIT &&
+                  UNITIG_JOIN == RSBWT_WALK_JOIN,
+              "unitig_rule.h speaks include/rsbwt.h's stop codes");
 
 #define WK_HIP(x)                                              \
     do {                                                       \
@@ -406,6 +564,83 @@ hipError_t launch_extensions(const shard_view *d_shards, uint32_t nshards, const
     hipLaunchKernelGGL(extension_kernel, dim3((unsigned)blocks), dim3(64 * WG_WAVES), 0, stream, d_shards, nshards, bt,
                        (unsigned long long *)d_counts, d_work);
     return hipGetLastError();
+}
+
+hipError_t launch_unitigs(const shard_view *d_shards, uint32_t nshards, const walk_batch &bt, void *d_ext, void *d_steps, void *d_stop,
+                          void *d_support, void *d_last, unsigned long long *d_work, hipStream_t stream) {
+    if (bt.Q == 0 || nshards == 0) return hipSuccess;
+    if (bt.ctx == 0u || bt.ctx >= WALK_RING || bt.max_steps == 0u || bt.min_count == 0ull) return hipErrorInvalidValue;
+    if ((bt.flags & ~(uint32_t)RSBWT_WALK_BOTH_STRANDS) != 0u) return hipErrorInvalidValue;  // (the side is the item's)
+    const size_t items = 2 * bt.Q, blocks = (items + UNITIG_ITEMS - 1) / UNITIG_ITEMS;
+    if (blocks > 0x7FFFFFFFull || (uint64_t)items * bt.max_steps >= (1ull << 31)) return hipErrorInvalidValue;
+    // every byte past a side's steps is 0
+    hipError_t e = hipMemsetAsync(d_ext, 0, items * (size_t)bt.max_steps, stream);
+    if (e == hipSuccess && d_support) e = hipMemsetAsync(d_support, 0, items * (size_t)bt.max_steps * 4, stream);
+    if (e != hipSuccess) return e;
+    auto go = [&](auto kernel, unsigned waves) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * waves), 0, stream, d_shards, nshards, bt, (char *)d_ext, (uint32_t *)d_steps,
+                           (uint8_t *)d_stop, (uint32_t *)d_support, (unsigned long long *)d_last, d_work);
+    };
+    if (nshards >= (uint32_t)WG_WAVES) go(unitig_kernel<WG_WAVES>, WG_WAVES);
+    else if (nshards >= 2u) go(unitig_kernel<2>, 2);
+    else go(unitig_kernel<1>, 1);
+    return hipGetLastError();
+}
+
+void unitig_set_last_work(const uint64_t work8[8]) {
+    for (int i = 0; i < 8; ++i) unitig_last[i] = work8 ? work8[i] : 0;
+}
+void unitig_get_last_work(uint64_t work8[8]) { memcpy(work8, unitig_last, sizeof unitig_last); }
+
+int unitig_check_args(uint32_t ctx, uint32_t flags, uint32_t max_steps, size_t Q) {
+    if (ctx < 1u || ctx > 255u) return fail(RSBWT_EINVAL, "ctx = %u: 1 to 255", ctx);
+    if (flags & ~(uint32_t)RSBWT_WALK_BOTH_STRANDS) return fail(RSBWT_EINVAL, "flags 0x%x: a unitig takes RSBWT_WALK_BOTH_STRANDS only", flags);
+    if (max_steps < 1u || max_steps > 65535u) return fail(RSBWT_EINVAL, "max_steps = %u: 1 to 65,535", max_steps);
+    if ((uint64_t)Q >= (1ull << 31) || 2ull * Q * max_steps >= (1ull << 31))
+        return fail(RSBWT_ERANGE, "%zu seeds x 2 sides x %u steps: under 2^31 in one call", Q, max_steps);
+    return RSBWT_OK;
+}
+
+// A unitig call on one device on `st`: the batch goes up, ONE launch walks both sides of every seed over the shards of
+// d_views, the answers come back (support and last are optional); work8[1..7] += the launch's counters.  Synchronises `st`.
+int unitig_host_views(scratch_cache &scratch, hipStream_t st, const shard_view *d_views, uint32_t S, const char *t0, const uint64_t *rel, size_t Q,
+                      size_t N, uint32_t ctx, uint64_t min_count, uint32_t max_steps, uint32_t flags, char *ext, uint32_t *steps, uint8_t *stop,
+                      uint32_t *support, uint64_t *last, uint64_t *work8) {
+    if (Q == 0 || S == 0) return RSBWT_OK;
+    const size_t items = 2 * Q, cells = items * (size_t)max_steps;
+    const size_t a_text = al256(N + 1), a_off = al256((Q + 1) * 8), a_ext = al256(cells), a_steps = al256(items * 4), a_stop = al256(items),
+                 a_sup = support ? al256(cells * 4) : 0, a_last = last ? al256(items * 64) : 0;
+    scratch_cache::lease mem;
+    hipError_t e = scratch.take(a_text + a_off + a_ext + a_steps + a_stop + a_sup + a_last + 256, st, &mem);
+    if (e != hipSuccess) return fail(RSBWT_ENOMEM, "%zu seeds x %u steps do not fit the device's free memory: %s", Q, max_steps, hipGetErrorString(e));
+    give_back give{scratch, mem, st};
+    uint8_t *d_text = (uint8_t *)mem.p, *d_off = d_text + a_text, *d_ext = d_off + a_off, *d_steps = d_ext + a_ext, *d_stop = d_steps + a_steps,
+            *d_sup = d_stop + a_stop, *d_last = d_sup + a_sup, *d_wk = d_last + a_last;
+    if (N) WK_HIP(hipMemcpyAsync(d_text, t0, N, hipMemcpyHostToDevice, st));
+    WK_HIP(hipMemcpyAsync(d_off, rel, (Q + 1) * 8, hipMemcpyHostToDevice, st));
+    WK_HIP(hipMemsetAsync(d_wk, 0, 256, st));
+    walk_batch bt;
+    bt.text = (const char *)d_text;
+    bt.off = (const uint64_t *)d_off;
+    bt.Q = Q;
+    bt.N = N;
+    bt.ctx = ctx;
+    bt.max_steps = max_steps;
+    bt.min_count = min_count ? min_count : 1ull;
+    bt.flags = flags;
+    e = launch_unitigs(d_views, S, bt, d_ext, d_steps, d_stop, support ? d_sup : nullptr, last ? d_last : nullptr, (unsigned long long *)d_wk, st);
+    if (e != hipSuccess) return fail_hip(e, "unitig kernel launch");
+    unsigned long long hwk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    WK_HIP(hipMemcpyAsync(ext, d_ext, cells, hipMemcpyDeviceToHost, st));
+    WK_HIP(hipMemcpyAsync(steps, d_steps, items * 4, hipMemcpyDeviceToHost, st));
+    WK_HIP(hipMemcpyAsync(stop, d_stop, items, hipMemcpyDeviceToHost, st));
+    if (support) WK_HIP(hipMemcpyAsync(support, d_sup, cells * 4, hipMemcpyDeviceToHost, st));
+    if (last) WK_HIP(hipMemcpyAsync(last, d_last, items * 64, hipMemcpyDeviceToHost, st));
+    WK_HIP(hipMemcpyAsync(hwk, d_wk, sizeof hwk, hipMemcpyDeviceToHost, st));
+    WK_HIP(hipStreamSynchronize(st));
+    if (work8)
+        for (int i = 1; i < 8; ++i) work8[i] += hwk[i];
+    return RSBWT_OK;
 }
 
 void walk_set_last_work(const uint64_t work6[6]) {

@@ -889,6 +889,77 @@ int rsbwt_set_unitigs_dev(rsbwt_set_t *s, const void *d_text, const void *d_off,
                           uint32_t max_steps, uint32_t flags, void *d_ext, void *d_steps, void *d_stop, void *d_support, void *d_last,
                           void *stream);
 void rsbwt_set_unitig_last_work(uint64_t *work8);
+/* Paths: every path from a seed, through the forks, depth first -- the alleles between two anchors read off the reads (a SNP
+ * is two paths of equal length, an indel two of different length).  W_p, rc, the candidates, E_p, sup, "invalid",
+ * m = max(min_count, 1) and the flags RSBWT_WALK_LEFT / RSBWT_WALK_BOTH_STRANDS are the walk section's above.
+ *   max_steps  the symbols a path may append, 1..65,535
+ *   max_paths  the paths a seed may put out, 1..256
+ *   max_evals  the evaluations (of four supports each) a seed may make, 1..2^20
+ *   ttext, toff[Q + 1]  an optional TARGET per seed, both NULL = no targets: target q = ttext[toff[q] .. toff[q+1]); a target of
+ *              no symbols = none for that seed; one longer than ctx is RSBWT_EINVAL; one holding a symbol outside ACGT never
+ *              matches
+ * Per seed, with seq = seed + path walking right and reverse(path) + seed walking left:
+ *   an invalid seed: state RSBWT_PATHS_INVALID, 0 paths
+ *   path = "", pend = {}, evals = 0, out = []
+ *   loop:
+ *     if target and len(path) >= 1 and the len(target) symbols at the walking end of seq == target:  stop = RSBWT_WALK_TARGET
+ *     elif len(path) == max_steps:                                                                    stop = RSBWT_WALK_LIMIT
+ *     elif evals == max_evals:                                                                        stop = RSBWT_WALK_BUDGET
+ *     else:
+ *        evals += 1; evaluate the four supports of seq; live = [c in A, C, G, T order : sup(seq, c) >= m]
+ *        if live is empty: stop = RSBWT_WALK_DEAD_END
+ *        else: pend[len(path)] = live[1:] (if any); path += live[0]; continue
+ *     out.append((path, stop, the least support of the path's symbols saturated at 2^32 - 1; 0 for a path of no symbols))
+ *     if stop == RSBWT_WALK_BUDGET:  state RSBWT_PATHS_BUDGET;    done
+ *     if pend is empty:              state RSBWT_PATHS_COMPLETE;  done
+ *     if len(out) == max_paths:      state RSBWT_PATHS_MORE;      done
+ *     d = the deepest depth in pend; c = its first untried symbol (removed); path = path[:d] + c
+ * The paths come depth first in pre-order with A < C < G < T at every fork: the output is a function of the supports alone.
+ * A cycle ends with LIMIT; the target is not tested at 0 steps (the seed is the source anchor); the order of the three end
+ * tests and of the three "done" tests is part of the definition (csrc/paths_rule.h states them once for device and host).
+ *   rsbwt_set_paths      ext          char[Q][max_paths][max_steps]: path j of seed q in the order its symbols were appended
+ *                                     (walking left the sequence is reverse(ext) + seed); 0 past a path's steps and in
+ *                                     unused slots
+ *                        steps        u32[Q][max_paths]; 0 in unused slots
+ *                        stop         u8[Q][max_paths]: RSBWT_WALK_DEAD_END, _LIMIT, _TARGET or _BUDGET; 0 in unused slots
+ *                        min_support  u32[Q][max_paths], may be NULL; 0 in unused slots
+ *                        npaths       u32[Q]
+ *                        state        u8[Q], one of RSBWT_PATHS_*; 0 is never written
+ *                      On a set on one device the whole search of every seed is ONE launch: a workgroup per 8 seeds, a
+ *                      seed's paths written into their own slots as they grow, its untried symbols in HBM scratch of
+ *                      min(max_steps, max_evals) x 32 bytes per seed; over several device groups each group evaluates the
+ *                      current node of the seeds still searching (rsbwt_set_extensions' kernel), the host sums, applies
+ *                      csrc/paths_rule.h and goes again: the same outputs and counters, one round trip per evaluation.
+ *   rsbwt_set_paths_dev  a set on ONE device (several: RSBWT_EINVAL); d_text, d_off (u64[Q + 1], d_off[0] = 0, d_off[Q] = N),
+ *                        d_ttext, d_toff (both NULL, or u64[Q + 1] with d_toff[0] = 0, d_toff[Q] = TN) and the outputs in HBM
+ *                        (d_min_support may be NULL); every byte of every output is written; enqueues on `stream`,
+ *                        synchronises nothing.  The lengths are not on the host here: a target longer than ctx is not
+ *                        refused, it never matches.
+ * Unknown flag bits, ctx outside 1..255, max_steps, max_paths or max_evals outside their ranges, a NULL required pointer with
+ * Q > 0 (one of ttext, toff without the other included) and offsets that run backwards are RSBWT_EINVAL;
+ * Q x max_paths x max_steps >= 2^31 is RSBWT_ERANGE, refused before anything is read; Q = 0 succeeds and touches nothing; no
+ * device RSBWT_ENODEV.  The calls need neither RSBWT_OPEN_READS nor a k-mer table (same answers with any table or none), build
+ * nothing, write nothing a search reads and are re-entrant.  There is no single-handle form: a set of one serves.
+ * rsbwt_set_paths_last_work: the calling thread's last host-buffer call: {seeds, symbols appended (every symbol put at the end
+ * of a path: the first live symbol of an evaluation and the symbol a backtrack takes up), candidate searches, LF steps,
+ * lane-passes that fetched a line, starts from a k-mer table entry, evaluations, paths}.
+ * Measured on one MI355X (tools/paths_probe.py, profiles/paths_probe.json): 10^4 seeds of 31 walking right, ctx 30,
+ * targets ending 60 symbols past the seed, max_steps 200, max_paths 8, max_evals 800, both strands, on a popBWT of 3.0e7
+ * symbols: 50 ms as one shard, 204 ms dealt to eight; a depth-first host loop of rsbwt_set_extensions that gives the same
+ * answers takes 409 and 528 ms (8.2 and 2.6 times the call). */
+#define RSBWT_WALK_TARGET 6
+#define RSBWT_WALK_BUDGET 7
+#define RSBWT_PATHS_COMPLETE 1
+#define RSBWT_PATHS_MORE 2
+#define RSBWT_PATHS_BUDGET 3
+#define RSBWT_PATHS_INVALID 4
+int rsbwt_set_paths(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const char *ttext, const uint64_t *toff, uint32_t ctx,
+                    uint64_t min_count, uint32_t max_steps, uint32_t max_paths, uint32_t max_evals, uint32_t flags, char *ext, uint32_t *steps,
+                    uint8_t *stop, uint32_t *min_support, uint32_t *npaths, uint8_t *state);
+int rsbwt_set_paths_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, size_t N, const void *d_ttext, const void *d_toff,
+                        size_t TN, uint32_t ctx, uint64_t min_count, uint32_t max_steps, uint32_t max_paths, uint32_t max_evals, uint32_t flags,
+                        void *d_ext, void *d_steps, void *d_stop, void *d_min_support, void *d_npaths, void *d_state, void *stream);
+void rsbwt_set_paths_last_work(uint64_t *work8);
 /* The per-read sample table: "which samples carry this read".  Replaces, for the return types All and Samples, the
  * RocksDB lookups of the reference -- sdb->Get(read, &value) in QueryTask::run (src/service/service.cpp:1292-1348), KmerTask::run
  * (:917-975) and DbTask::run (:816-845) -- by a table in HBM keyed by the read's ordinal: per shard off u64[num_strings + 1]

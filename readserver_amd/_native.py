@@ -226,6 +226,11 @@ SIGNATURES = {
     "rsbwt_set_unitigs_dev": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, _vp,
                                         _vp, _vp, _vp]),
     "rsbwt_set_unitig_last_work": (None, [_u64p]),
+    "rsbwt_set_paths": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                  _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsbwt_set_paths_dev": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint32,
+                                      C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsbwt_set_paths_last_work": (None, [_u64p]),
     "rsbwt_service_kmer_requests": (C.c_uint64, [_vp]),
     "rsbwt_set_meta_build": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "rsbwt_set_meta_load": (C.c_int, [_vp, C.c_char_p, _vp]),

@@ -24,6 +24,9 @@ def _ptr(a):
 # rsbwt_set_walk's stop codes and the flag word of the walk / extension calls (include/rsbwt.h)
 WALK_DEAD_END, WALK_BRANCH, WALK_LIMIT, WALK_INVALID = 1, 2, 3, 4
 WALK_JOIN = 5  # rsbwt_set_unitigs alone: another path enters the node the side would enter
+# rsbwt_set_paths alone: a path reached its seed's target / the seed's evaluations ran out; and the seed states
+WALK_TARGET, WALK_BUDGET = 6, 7
+PATHS_COMPLETE, PATHS_MORE, PATHS_BUDGET, PATHS_INVALID = 1, 2, 3, 4
 
 
 def unitig_sequence(seed, right_ext, left_ext):
@@ -947,6 +950,39 @@ class ShardSet:
         w = np.zeros(8, np.uint64)
         lib().rsbwt_set_unitig_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
         return dict(zip(("seeds", "appended", "searches", "lf_steps", "passes", "table_starts", "onward", "back"), (int(x) for x in w)))
+
+    # -- paths (csrc/paths.hip): rsbwt_set_paths
+    def paths(self, seeds, ctx, min_count=1, max_steps=256, max_paths=8, max_evals=None, left=False, both_strands=False, targets=None):
+        """Every path from every seed through the reads' k-mer graph, depth first (rsbwt_set_paths): where a walk stops at
+        a fork, the search takes A before C before G before T and comes back for the others.  A path ends where no symbol
+        has a support of max(min_count, 1) (WALK_DEAD_END), after max_steps symbols (WALK_LIMIT), where its walking end
+        spells the seed's target (WALK_TARGET; targets: one string of at most ctx symbols per seed, "" = none; not looked at
+        before the first symbol) or when the seed has made max_evals evaluations (WALK_BUDGET; default 4 * max_steps).
+        Returns, per seed, (state, [(ext, stop, min_support), ...]): state PATHS_COMPLETE (every path is there), PATHS_MORE
+        (max_paths paths are out and forks are left), PATHS_BUDGET or PATHS_INVALID (no paths); ext the symbols in the order
+        they were appended (left=True: the sequence is ext[::-1] + seed), min_support the least support of its symbols."""
+        if max_evals is None:
+            max_evals = 4 * max_steps
+        text, off = self._var_text(seeds)
+        Q = len(seeds)
+        if targets is not None and len(targets) != Q:
+            raise ValueError("one target per seed")
+        ttext, toff = self._var_text(targets) if targets is not None else (None, None)
+        ext = np.zeros((Q, max_paths, max_steps), np.uint8)
+        steps, stop, sup = np.zeros((Q, max_paths), np.uint32), np.zeros((Q, max_paths), np.uint8), np.zeros((Q, max_paths), np.uint32)
+        npaths, state = np.zeros(Q, np.uint32), np.zeros(Q, np.uint8)
+        check(lib().rsbwt_set_paths(self._s, _ptr(text), _ptr(off), Q, _ptr(ttext) if targets is not None else None,
+                                    _ptr(toff) if targets is not None else None, ctx, min_count, max_steps, max_paths, max_evals,
+                                    _walk_flags(left, both_strands), _ptr(ext), _ptr(steps), _ptr(stop), _ptr(sup), _ptr(npaths), _ptr(state)))
+        return [(int(state[q]), [(ext[q, j, :int(steps[q, j])].tobytes().decode(), int(stop[q, j]), int(sup[q, j])) for j in range(int(npaths[q]))])
+                for q in range(Q)]
+
+    @staticmethod
+    def paths_last_work():
+        """{seeds, appended, searches, lf_steps, passes, table_starts, evals, paths} of this thread's last paths call"""
+        w = np.zeros(8, np.uint64)
+        lib().rsbwt_set_paths_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return dict(zip(("seeds", "appended", "searches", "lf_steps", "passes", "table_starts", "evals", "paths"), (int(x) for x in w)))
 
     # -- the per-read sample table (csrc/read_meta.hip): rsbwt_set_meta_* / rsbwt_set_read_meta_var
     @staticmethod

@@ -164,6 +164,19 @@ int unitig_host_views(scratch_cache &scratch, hipStream_t st, const shard_view *
                       uint32_t *support, uint64_t *last, uint64_t *work8);
 void unitig_set_last_work(const uint64_t work8[8]);
 void unitig_get_last_work(uint64_t work8[8]);
+// paths.hip: what the path calls share (sets.hip).
+//   paths_check_args      ctx, flags, max_steps, max_paths, max_evals and Q x max_paths x max_steps
+//   paths_host_views      a whole paths call on one device on `st` (synchronised before it returns): trel (the targets'
+//                         offsets from toff[0], TN symbols at tt0) may be null = no targets, min_support is optional;
+//                         work8[1..7] += the launch's counters
+//   paths_set / get_last_work: what rsbwt_set_paths_last_work reports for the calling thread
+int paths_check_args(uint32_t ctx, uint32_t flags, uint32_t max_steps, uint32_t max_paths, uint32_t max_evals, size_t Q);
+int paths_host_views(scratch_cache &scratch, hipStream_t st, const shard_view *d_views, uint32_t S, const char *t0, const uint64_t *rel, size_t Q,
+                     size_t N, const char *tt0, const uint64_t *trel, size_t TN, uint32_t ctx, uint64_t min_count, uint32_t max_steps,
+                     uint32_t max_paths, uint32_t max_evals, uint32_t flags, char *ext, uint32_t *steps, uint8_t *stop, uint32_t *min_support,
+                     uint32_t *npaths, uint8_t *state, uint64_t *work8);
+void paths_set_last_work(const uint64_t work8[8]);
+void paths_get_last_work(uint64_t work8[8]);
 // ksw_align.hip behind rsbwt_gt_align (capi.hip) and the aligned set calls (sets.hip): a host batch checked (null, item < Q,
 // lengths 1..4096: RSBWT_EINVAL), ordered by length, aligned on `device` and waited for; work14 += {reads, reads by
 // verdict 1..13}.  gt_align_set / get_last_work: what rsbwt_gt_align_last_work reports for the calling thread (null: zeros)

@@ -423,6 +423,24 @@ hipError_t launch_extensions(const shard_view *d_shards, uint32_t nshards, const
 //     return evaluations
 hipError_t launch_unitigs(const shard_view *d_shards, uint32_t nshards, const walk_batch &bt, void *d_ext, void *d_steps, void *d_stop,
                           void *d_support, void *d_last, unsigned long long *d_work, hipStream_t stream);
+// paths.hip: every path from a seed, depth first (include/rsbwt.h: the definition; paths_rule.h: the decisions).  The seeds
+// are a walk_batch; the optional targets are their text back to back and where each starts, in HBM.
+struct paths_batch {
+    walk_batch seeds;
+    const char *ttext;     // nullptr: no seed has a target
+    const uint64_t *toff;  // [Q + 1], toff[0] = 0
+    size_t TN;             // the targets' symbols: toff[Q]
+    uint32_t max_paths;    // 1..256
+    uint32_t max_evals;    // 1..2^20
+};
+//   paths_frame_bytes: the bytes of d_frames, the launch's frame store (a stack of paths_frame per seed)
+//   launch_paths: a workgroup per 8 seeds searches them over all nshards shards.  d_ext char[Q][max_paths][max_steps],
+//     d_steps u32[Q][max_paths], d_stop u8[Q][max_paths] and d_min_support u32[Q][max_paths] (optional) are zeroed on
+//     `stream` and the paths written; d_npaths u32[Q] and d_state u8[Q] are written for every seed; d_work (optional,
+//     zeroed by the caller) [1..5] as launch_walk's, [6..7] += evaluations and paths
+size_t paths_frame_bytes(size_t Q, uint32_t max_steps, uint32_t max_evals);
+hipError_t launch_paths(const shard_view *d_shards, uint32_t nshards, const paths_batch &pb, void *d_frames, void *d_ext, void *d_steps, void *d_stop,
+                        void *d_min_support, void *d_npaths, void *d_state, unsigned long long *d_work, hipStream_t stream);
 // ksw_align.hip: ksw_align of the reference's ksw.c and align_gt_read over it (ksw_pass.h), one lane per item.  A block is
 // one wave of 64 items and belongs to the LENGTH CLASS of its longest pass: at most 32, 64, 104, 160 or KSW_LDS_ROWS rows
 // -- the column lives in LDS, the launch's LDS sized for the class -- or more: the column lives in d_scratch

@@ -31,6 +31,7 @@
 #include "capi_internal.h"
 #include "gt_span_rule.h"
 #include "meta_file.h"
+#include "paths_rule.h"
 #include "sample_codes.h"
 #include "service.h"
 #include "unitig_rule.h"
@@ -2704,6 +2705,109 @@ int unitigs_by_steps(rsbwt_set_t *s, const char *text, const uint64_t *off, size
     }
     return RSBWT_OK;
 }
+
+// The paths of a set over several device groups: per round the groups evaluate the current node of every seed still
+// searching (its context alone is sent), the host sums over the shards and takes the writer lane's decisions with
+// paths_rule.h -- paths_kernel's round, on the host.  tt / trel: the targets, trel null = none.  work8 as paths_host_views'.
+int paths_by_steps(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const char *tt, const uint64_t *trel, uint32_t ctx, uint64_t m,
+                   uint32_t max_steps, uint32_t max_paths, uint32_t max_evals, uint32_t flags, char *ext, uint32_t *steps, uint8_t *stop,
+                   uint32_t *min_support, uint32_t *npaths, uint8_t *state, uint64_t *work8) {
+    const bool left = (flags & RSBWT_WALK_LEFT) != 0u;
+    const size_t S = s->shards.size(), slots = Q * (size_t)max_paths;
+    memset(ext, 0, slots * max_steps);
+    memset(steps, 0, slots * 4);
+    memset(stop, 0, slots);
+    if (min_support) memset(min_support, 0, slots * 4);
+    struct search {
+        std::string seed_ctx, path, target;
+        std::vector<paths_frame> frames;
+        uint32_t nframes = 0, evals = 0, min_cur = PATHS_NO_SUPPORT;
+    };
+    std::vector<search> st(Q);
+    // the ctx symbols at the walking end of seed + path (reverse(path) + seed)
+    auto context = [&](const search &a) {
+        if (left) return (std::string(a.path.rbegin(), a.path.rend()) + a.seed_ctx).substr(0, ctx);
+        const std::string all = a.seed_ctx + a.path;
+        return all.substr(all.size() - ctx);
+    };
+    auto at_target = [&](const search &a) {
+        if (a.target.empty()) return false;
+        const std::string c = context(a);
+        return left ? c.compare(0, a.target.size(), a.target) == 0 : c.compare(ctx - a.target.size(), a.target.size(), a.target) == 0;
+    };
+    std::vector<size_t> live;
+    for (size_t q = 0; q < Q; ++q) {
+        bool valid = off[q + 1] - off[q] >= ctx;
+        if (valid) {
+            st[q].seed_ctx.assign(left ? text + off[q] : text + off[q + 1] - ctx, ctx);
+            for (char ch : st[q].seed_ctx) valid = valid && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
+        }
+        npaths[q] = 0;
+        state[q] = valid ? 0 : (uint8_t)PATHS_INVALID;
+        if (!valid) continue;
+        if (trel) st[q].target.assign(tt + trel[q], (size_t)(trel[q + 1] - trel[q]));
+        st[q].frames.resize(paths_frames(max_steps, max_evals));
+        live.push_back(q);
+    }
+    std::string t;
+    std::vector<uint64_t> rel, counts;
+    while (!live.empty()) {  // (every seed of `live` has a node to evaluate: its end test said so)
+        const size_t nl = live.size();
+        t.clear();
+        rel.resize(nl + 1);
+        for (size_t i = 0; i < nl; ++i) {
+            rel[i] = (uint64_t)i * ctx;
+            t += context(st[live[i]]);
+        }
+        rel[nl] = (uint64_t)nl * ctx;
+        if (rel[nl] >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu seeds x %u context symbols: under 2^31 in one call", nl, ctx);
+        counts.assign(S * nl * 4, 0);
+        const int rc = extension_groups(s, t.data(), rel.data(), nl, (size_t)rel[nl], ctx, flags, counts.data(), work8);
+        if (rc) return rc;
+        std::vector<size_t> next;
+        for (size_t i = 0; i < nl; ++i) {
+            const size_t q = live[i];
+            search &a = st[q];
+            uint64_t sup[4] = {0, 0, 0, 0};
+            for (uint32_t c = 0; c < 4; ++c)
+                for (size_t p = 0; p < S; ++p) sup[c] += counts[(p * nl + i) * 4 + c];
+            ++a.evals;
+            work8[6] += 1;
+            const uint32_t mask = paths_live(sup, m);
+            uint32_t why = PATHS_DEAD_END;
+            if (mask != 0u) {
+                a.path += "ACGT"[paths_advance(a.frames.data(), &a.nframes, (uint32_t)a.path.size(), mask, sup, &a.min_cur)];
+                work8[1] += 1;
+                why = paths_end(at_target(a), (uint32_t)a.path.size(), max_steps, a.evals, max_evals);
+            }
+            bool searching = true;
+            while (why != PATHS_GO) {  // (max_paths times at the most: every turn puts a path out)
+                const size_t at = q * (size_t)max_paths + npaths[q];
+                memcpy(ext + at * max_steps, a.path.data(), a.path.size());
+                steps[at] = (uint32_t)a.path.size();
+                stop[at] = (uint8_t)why;
+                if (min_support) min_support[at] = paths_min_out((uint32_t)a.path.size(), a.min_cur);
+                ++npaths[q];
+                work8[7] += 1;
+                const uint32_t done = paths_done(why, a.nframes, npaths[q], max_paths);
+                if (done != PATHS_GO) {
+                    state[q] = (uint8_t)done;
+                    searching = false;
+                    break;
+                }
+                uint32_t d = 0;
+                const uint32_t c = paths_backtrack(a.frames.data(), &a.nframes, &d, &a.min_cur);
+                a.path.resize(d);
+                a.path += "ACGT"[c];
+                work8[1] += 1;
+                why = paths_end(at_target(a), (uint32_t)a.path.size(), max_steps, a.evals, max_evals);
+            }
+            if (searching) next.push_back(q);
+        }
+        live.swap(next);
+    }
+    return RSBWT_OK;
+}
 }  // namespace
 
 int rsbwt_set_extensions(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint32_t flags, uint64_t *counts) {
@@ -2841,6 +2945,87 @@ int rsbwt_set_unitigs_dev(rsbwt_set_t *s, const void *d_text, const void *d_off,
 
 void rsbwt_set_unitig_last_work(uint64_t *work8) {
     if (work8) unitig_get_last_work(work8);
+}
+
+int rsbwt_set_paths(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const char *ttext, const uint64_t *toff, uint32_t ctx,
+                    uint64_t min_count, uint32_t max_steps, uint32_t max_paths, uint32_t max_evals, uint32_t flags, char *ext, uint32_t *steps,
+                    uint8_t *stop, uint32_t *min_support, uint32_t *npaths, uint8_t *state) {
+    return guarded("rsbwt_set_paths", [&]() -> int {
+        paths_set_last_work(nullptr);
+        int rc = walk_set_check(s);
+        if (rc) return rc;
+        if ((rc = paths_check_args(ctx, flags, max_steps, max_paths, max_evals, Q)) != RSBWT_OK) return rc;
+        std::vector<uint64_t> rel, trel;
+        size_t N = 0, TN = 0;
+        if ((rc = match_check_batch(text, off, Q, &rel, &N)) != RSBWT_OK) return rc;
+        if (Q == 0) return RSBWT_OK;
+        if (!ext || !steps || !stop || !npaths || !state) return fail(RSBWT_EINVAL, "null argument");
+        if ((ttext == nullptr) != (toff == nullptr)) return fail(RSBWT_EINVAL, "targets: ttext and toff come together or not at all");
+        const bool targets = toff != nullptr;
+        if (targets) {
+            if ((rc = match_check_batch(ttext, toff, Q, &trel, &TN)) != RSBWT_OK) return rc;
+            for (size_t q = 0; q < Q; ++q)
+                if (trel[q + 1] - trel[q] > ctx)
+                    return fail(RSBWT_EINVAL, "target %zu: %llu symbols, at most ctx = %u", q, (unsigned long long)(trel[q + 1] - trel[q]), ctx);
+        }
+        const uint64_t m = min_count ? min_count : 1ull;
+        const char *t0 = N ? text + off[0] : nullptr, *tt0 = targets ? ttext + toff[0] : nullptr;
+        uint64_t work8[8] = {Q, 0, 0, 0, 0, 0, 0, 0};
+        if (s->groups.size() == 1) {  // every seed's whole search in one launch
+            dev_group *g = s->groups[0];
+            group_call gc(g);
+            if (gc.rc) return gc.rc;
+            rc = paths_host_views(g->scratch, gc.st, g->d_views, (uint32_t)g->idx.size(), t0, rel.data(), Q, N, tt0, targets ? trel.data() : nullptr, TN,
+                                  ctx, m, max_steps, max_paths, max_evals, flags, ext, steps, stop, min_support, npaths, state, work8);
+        } else {
+            rc = paths_by_steps(s, t0, rel.data(), Q, tt0, targets ? trel.data() : nullptr, ctx, m, max_steps, max_paths, max_evals, flags, ext, steps,
+                                stop, min_support, npaths, state, work8);
+        }
+        if (rc) return rc;
+        paths_set_last_work(work8);
+        return RSBWT_OK;
+    });
+}
+
+int rsbwt_set_paths_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, size_t N, const void *d_ttext, const void *d_toff,
+                        size_t TN, uint32_t ctx, uint64_t min_count, uint32_t max_steps, uint32_t max_paths, uint32_t max_evals, uint32_t flags,
+                        void *d_ext, void *d_steps, void *d_stop, void *d_min_support, void *d_npaths, void *d_state, void *stream) {
+    dev_group *g = nullptr;
+    int rc = one_device_group(s, &g);
+    if (rc) return rc;
+    if ((rc = paths_check_args(ctx, flags, max_steps, max_paths, max_evals, Q)) != RSBWT_OK) return rc;
+    if (Q == 0) return RSBWT_OK;
+    if (!d_text || !d_off || !d_ext || !d_steps || !d_stop || !d_npaths || !d_state) return fail(RSBWT_EINVAL, "null argument");
+    if ((d_ttext == nullptr) != (d_toff == nullptr)) return fail(RSBWT_EINVAL, "targets: d_ttext and d_toff come together or not at all");
+    if (N >= (1ull << 31) || TN >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu positions in one call: at most 2^31 - 1", N > TN ? N : TN);
+    for (rsbwt_t *h : s->shards)
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
+    paths_batch pb;
+    pb.seeds.text = (const char *)d_text;
+    pb.seeds.off = (const uint64_t *)d_off;
+    pb.seeds.Q = Q;
+    pb.seeds.N = N;
+    pb.seeds.ctx = ctx;
+    pb.seeds.max_steps = max_steps;
+    pb.seeds.min_count = min_count ? min_count : 1ull;
+    pb.seeds.flags = flags;
+    pb.ttext = (const char *)d_ttext;
+    pb.toff = (const uint64_t *)d_toff;
+    pb.TN = d_toff ? TN : 0;
+    pb.max_paths = max_paths;
+    pb.max_evals = max_evals;
+    // the frame store: leased for the launch and handed back in stream order, so nothing is waited for
+    scratch_cache::lease mem;
+    hipError_t e = g->scratch.take(paths_frame_bytes(Q, max_steps, max_evals) + 256, (hipStream_t)stream, &mem);
+    if (e != hipSuccess) return fail(RSBWT_ENOMEM, "the frame store of %zu seeds does not fit the device's free memory: %s", Q, hipGetErrorString(e));
+    e = launch_paths(g->d_views, (uint32_t)g->idx.size(), pb, mem.p, d_ext, d_steps, d_stop, d_min_support, d_npaths, d_state, nullptr,
+                     (hipStream_t)stream);
+    g->scratch.give(mem, (hipStream_t)stream);
+    return e == hipSuccess ? RSBWT_OK : fail_hip(e, "paths kernel launch");
+}
+
+void rsbwt_set_paths_last_work(uint64_t *work8) {
+    if (work8) paths_get_last_work(work8);
 }
 
 static size_t hits_1mm_scratch_one(const rsbwt_set_t *s, size_t m, uint32_t k) {

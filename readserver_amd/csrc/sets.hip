@@ -4159,7 +4159,11 @@ int set_site_counts_body(rsbwt_set_t *s, const char *text, const uint64_t *off, 
             rq.hi_w = std::max(rq.hi_w, wl);
             if (wl) rq.lo_w = std::min(rq.lo_w, wl);
         }
+#ifdef RSB_SITE_MUTANT_SLICE_ALT
+        rq.alt = alt;
+#else
         rq.alt = alt + q0;
+#endif
         rq.isalt = isalt + q0;
         std::vector<site_group_out> outs(G);
         rc = for_each_group(s, [&](size_t gi) -> int {
@@ -4175,7 +4179,11 @@ int set_site_counts_body(rsbwt_set_t *s, const char *text, const uint64_t *off, 
                 if (al) al[q] += o.aligned[q];
                 if (ca) ca[q] += o.carriers[q];
             }
+#ifdef RSB_SITE_MUTANT_SLICE_WORK
+            for (int i = 0; i < 10; ++i) work10[i] = o.work[i];
+#else
             for (int i = 0; i < 10; ++i) work10[i] += o.work[i];
+#endif
             for (int i = 0; i < 6; ++i) site_last_ms[i] += o.ms[i];
         }
     }

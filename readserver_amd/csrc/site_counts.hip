@@ -101,6 +101,9 @@ site_rows_kernel(const gt_batch bt, const gt_leg *__restrict__ legs, const gt_si
             if (r.pending) {
                 need = gt_left_needed_len(bt.q_pos[q], legs[(size_t)r.shard * bt.nitems + r.item].b, r.offset, bt.k);
                 if (need > SITE_NEED_MAX) need = SITE_NEED_MAX;
+#ifdef RSB_SITE_MUTANT_NEED_ZERO_PENDING
+                need = 0;
+#endif
             }
             const unsigned long long key = ((unsigned long long)q << 40) | o;  // q < 2^24, o < num_strings < 2^40: never all ones
             const uint64_t base = set.region[2u * r.shard], mask = set.region[2u * r.shard + 1u];
@@ -217,7 +220,9 @@ site_addr_kernel(const char *__restrict__ narrow, uint32_t stride, const char *_
     if (wide && over[i]) {
         const uint64_t w = ofirst[i];
         raddr[i] = (uint64_t)(uintptr_t)(wide + w * (size_t)wide_stride);
+#ifndef RSB_SITE_MUTANT_WIDE_LEN
         rlen[i] = wlen[w];
+#endif
     } else {
         raddr[i] = (uint64_t)(uintptr_t)(narrow + i * (size_t)stride);
     }

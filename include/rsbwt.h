@@ -1121,6 +1121,32 @@ int rsbwt_set_site_sample_counts(rsbwt_set_t *s, const char *text, const uint64_
                                  uint64_t *carriers);
 void rsbwt_set_site_last_work(uint64_t *work10);
 void rsbwt_set_site_last_times(double *ms6);
+/* Site reads: rsbwt_set_gt_aligned_reads / rsbwt_set_gt_aligned_count answered without that call's host trip.  Same
+ * arguments, same layout (first[Q*S + 1], reads at read_stride, read_len, read_row), same sizing protocol (cap_reads = 0:
+ * RSBWT_ERANGE with *nreads set) and the same answer element for element: the reads of (q, p) in ascending read_row, a
+ * string once per (q, p) under the smallest read_row it has, a string present in two shards reported in each, a read
+ * longer than read_stride reported with read_len = UINT32_MAX.  No sample table is needed.
+ * RSBWT_EINVAL: shards not opened with RSBWT_OPEN_READS; a shard of 2^40 strings or 2^46 symbols; a candidate row whose
+ * walk does not end; a w or a surviving candidate read longer than 4,096 symbols.  pos = 0 or pos > |w| keeps nothing.
+ * From the narrowing to the answer the batch stays on the device (csrc/site_reads.hip over csrc/site_counts.hip's stages):
+ * every row the span filter keeps becomes a (request, ordinal) item, the distinct reads are extracted once into device
+ * buffers, equal strings are found by comparing each distinct read with its predecessor in (shard, read_row) order (the
+ * copies of a string stand on consecutive read_rows, and every copy is a candidate whenever one is), the items are aligned
+ * where they lie, and the kept ones are counted, ordered and gathered at read_stride there.  Per device group the host
+ * receives the group's first[], the reported reads' bytes, lengths and rows, the counters and seven sizes of eight bytes
+ * (rows, items, distinct reads, reads over the first extraction's 256 bytes, the longest read, classes, reads reported);
+ * with one device group the copies land in the caller's arrays, with several the host puts each group's cells at their
+ * places.  Slices of 2^24 requests; memory is bounded by the candidate rows.  Re-entrant like the other lookups.
+ *   rsbwt_set_site_read_counts     counts[q*S+p] = how many reads that is; nothing is gathered.
+ *   rsbwt_set_site_reads_last_work the calling thread's last call of either: {legs, LF steps spent lengthening, candidate
+ *       rows, rows the span filter kept, distinct reads extracted, string classes among them, (request, read) items
+ *       aligned, items kept, reads reported}; a failed call leaves all nine zero.  NULL is harmless. */
+int rsbwt_set_site_reads(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, const char *alt, const uint8_t *isalt,
+                         int32_t k, int32_t skip, uint64_t M, uint64_t *first, char *reads, uint32_t read_stride, uint32_t *read_len,
+                         uint64_t *read_row, size_t cap_reads, size_t *nreads);
+int rsbwt_set_site_read_counts(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, const char *alt,
+                               const uint8_t *isalt, int32_t k, int32_t skip, uint64_t M, uint64_t *counts);
+void rsbwt_set_site_reads_last_work(uint64_t *work9);
 /* Device-resident forms, for a set on ONE device (one process per GPU: bench.py --mode 1mm|extract).
  * d_hits [num_shards][cap_per_shard] x 32-byte records (rsbwt_hits_1mm_dev's), d_totals u64[num_shards];
  * d_rows [num_shards][n] (row numbers are per shard), d_out [num_shards][n][stride], d_len / d_prefix_len [num_shards][n]. */
@@ -1273,6 +1299,27 @@ uint64_t rsbwt_service_kmer_requests(const rsbwt_service_t *s); /* KmerMatch Cou
  * path; service.cfg `kmermatch = "on"`), 2 replies per partition on `push`, woven into the window's replies in arrival
  * order.  Needs every shard opened with RSBWT_OPEN_READS: RSBWT_EINVAL otherwise.  Default off. */
 int rsbwt_service_set_kmermatch(rsbwt_service_t *s, int enable);
+/* SiteMatch requests (`/gt`): answered in the window when on (service.cfg `sitematch = "on"`; default off: they go to the
+ * `other` handler or, under rsbwt_service_set_unserved, get empty Replies, as before).  Per request and strand the window
+ * fix-up of GtTask::run (service.cpp:1028-1046) with L = max_read_length, in signed arithmetic: the reverse strand takes
+ * rev_comp(q), pos = |q| - p + 1 and rev_comp(a); pos <= L gives w = query[0 : L + pos - 1], else w = query[pos - L :
+ * pos + L - 1] and pos = L.  pos > |w| (the reference's "ERROR" line), pos < 0 or a substr start past the end: the Reply
+ * carries rt, t and q and no sub-message.  pos = 0, an empty a, k <= 0, s < 0 or k > |w| run and keep nothing (zero
+ * count / empty list, the sub-message present).  A window's requests make one rsbwt_set_site_reads call (or
+ * _read_counts when all of them ask for Count) per distinct (k, s), both strands as items, M = 10,000.  Replies: 2 per
+ * request and partition, or 2 with counts summed and lists joined in partition order; Reply.rt = SiteMatch, Reply.t = the
+ * request's rt; Count sends ReplyCount (c = the kept reads), Reads ReplyReads, All and Samples ReplyAll (served only when
+ * rsbwt_service_set_all is on; each read with the ReadInfo records of its value, a read no pair names with none).  The
+ * reads come in ascending read_row per partition, a string once per partition -- not in the reference's unordered_set
+ * order.  A failed batch is answered with zero counts / empty lists.  RSBWT_EINVAL: a shard not opened with
+ * RSBWT_OPEN_READS; max_read_length over 2,048 (a window then passes the alignment's 4,096 symbols) -- set the lengths
+ * (rsbwt_service_set_reads) before switching this on.
+ * rsbwt_service_site_requests: the SiteMatch Count / Reads requests answered (All / Samples count in all_requests).
+ * rsbwt_proto_decode_request_site: Request.p / a / isalt (fields 6, 7, 8) beside rsbwt_proto_decode_request_ks. */
+int rsbwt_service_set_sitematch(rsbwt_service_t *s, int enable);
+uint64_t rsbwt_service_site_requests(const rsbwt_service_t *s);
+int rsbwt_proto_decode_request_site(const uint8_t *msg, size_t len, int32_t *p, int *has_p, const char **a, size_t *alen, int *has_a, int32_t *isalt,
+                                    int *has_isalt);
 /* A limit on the reads one ExactMatch-Reads query may bring (service.cfg `max_match_reads`; the reference's front-end
  * has a key of that name, src/service/server.cpp:129,413): each strand of a request is a query of its own, and a strand
  * whose rows, summed over the partitions, exceed n is answered -- in every partition's Reply, or in the one summed

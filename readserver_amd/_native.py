@@ -252,6 +252,10 @@ SIGNATURES = {
                                                C.c_int, _vp, _vp, _vp, _vp]),
     "rsbwt_set_site_last_work": (None, [_u64p]),
     "rsbwt_set_site_last_times": (None, [C.POINTER(C.c_double)]),
+    "rsbwt_set_site_reads": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_uint64, _vp, _vp, C.c_uint32, _vp, _vp,
+                                       C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rsbwt_set_site_read_counts": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_uint64, _vp]),
+    "rsbwt_set_site_reads_last_work": (None, [_u64p]),
     "rsbwt_proto_encode_all_reply": (C.c_size_t, [_vp, C.c_size_t, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_char_p),
                                                   C.POINTER(C.c_size_t), C.POINTER(_vp), C.POINTER(C.c_size_t), C.c_size_t, C.c_char_p,
                                                   C.c_size_t, C.c_uint32, C.c_int]),
@@ -264,6 +268,10 @@ SIGNATURES = {
     "rsbwt_proto_decode_request_ks": (C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_int32),
                                                 C.POINTER(C.c_int)]),
     "rsbwt_service_set_kmermatch": (C.c_int, [_vp, C.c_int]),
+    "rsbwt_service_set_sitematch": (C.c_int, [_vp, C.c_int]),
+    "rsbwt_service_site_requests": (C.c_uint64, [_vp]),
+    "rsbwt_proto_decode_request_site": (C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
+                                                  C.POINTER(C.c_int), C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
     "rsbwt_service_set_unserved": (None, [_vp, C.c_int]),
     "rsbwt_set_hits_1mm_scratch_bytes": (C.c_size_t, [_vp, C.c_size_t, C.c_uint32]),
     "rsbwt_set_hits_1mm_is_fused": (C.c_int, [_vp, C.c_size_t, C.c_uint32]),

@@ -1155,6 +1155,51 @@ class ShardSet:
         lib().rsbwt_set_site_last_times(t.ctypes.data_as(C.POINTER(C.c_double)))
         return dict(zip(("filter", "set", "reads", "items", "align", "tally"), (float(x) for x in t)))
 
+    # -- site reads (csrc/site_reads.hip): gt_aligned_reads / gt_aligned_count with the batch kept on the device
+    def site_reads(self, queries, pos, alt, isalt, k, skip=0, max_interval_size=0, read_stride=256, with_rows=False):
+        """What gt_aligned_reads returns, from the device-resident call (rsbwt_set_site_reads): [query][shard] -> reads,
+        ascending read_row, a string once"""
+        text, off = self._var_text(queries)
+        Q, S = len(queries), len(self.shards)
+        p, a, ia = self._gt_requests(queries, pos, alt, isalt)
+        first = np.zeros(Q * S + 1, np.uint64)
+        n = C.c_size_t()
+        rc = lib().rsbwt_set_site_reads(self._s, _ptr(text), _ptr(off), Q, _ptr(p), _ptr(a), _ptr(ia), k, skip, max_interval_size, _ptr(first), None,
+                                        read_stride, None, None, 0, C.byref(n))
+        if rc not in (0, -7):
+            check(rc)
+        total = n.value
+        reads = np.zeros((max(total, 1), read_stride), np.uint8)
+        ln = np.zeros(max(total, 1), np.uint32)
+        rr = np.zeros(max(total, 1), np.uint64)
+        if total:
+            check(lib().rsbwt_set_site_reads(self._s, _ptr(text), _ptr(off), Q, _ptr(p), _ptr(a), _ptr(ia), k, skip, max_interval_size, _ptr(first),
+                                             _ptr(reads), read_stride, _ptr(ln), _ptr(rr), total, C.byref(n)))
+            if (ln[:total] == 0xFFFFFFFF).any():
+                raise RsbwtError(-1, "a read does not fit read_stride")
+
+        def one(r):
+            t = reads[r, :ln[r]].tobytes().decode()
+            return (int(rr[r]), t) if with_rows else t
+        return [[[one(r) for r in range(int(first[q * S + s]), int(first[q * S + s + 1]))] for s in range(S)] for q in range(Q)]
+
+    def site_read_counts(self, queries, pos, alt, isalt, k, skip=0, max_interval_size=0):
+        """[query][shard] -> the number of those reads (rsbwt_set_site_read_counts)"""
+        text, off = self._var_text(queries)
+        Q, S = len(queries), len(self.shards)
+        p, a, ia = self._gt_requests(queries, pos, alt, isalt)
+        out = np.zeros(Q * S, np.uint64)
+        check(lib().rsbwt_set_site_read_counts(self._s, _ptr(text), _ptr(off), Q, _ptr(p), _ptr(a), _ptr(ia), k, skip, max_interval_size, _ptr(out)))
+        return out.reshape(Q, S)
+
+    @staticmethod
+    def site_reads_last_work():
+        """{legs, narrow_steps, candidates, kept, extracted, classes, aligned, items_kept, reported} of this thread's last
+        site_reads / site_read_counts call"""
+        w = np.zeros(9, np.uint64)
+        lib().rsbwt_set_site_reads_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return dict(zip(("legs", "narrow_steps", "candidates", "kept", "extracted", "classes", "aligned", "items_kept", "reported"), (int(x) for x in w)))
+
     # -- BASELINE configs[3] / configs[4] over the set: per-shard results side by side, the way the front-end
     # concatenates its partitions' replies (src/service/server.cpp:199-261)
     def hits_1mm(self, kmers):

@@ -488,7 +488,9 @@ hipError_t launch_gt_align(const gt_align_batch &bt, uint32_t min_rows, uint32_t
 //                        head ordinal inserts (request << 40 | ordinal) into its shard's region of `set` (all ones = empty,
 //                        every access the 64-bit CAS), the winner stores set_row[slot] = read_row, and every row takes
 //                        atomicMin(set_need[slot], the read length that lets it stay): gt_span_rule.h, 0 for a row that is
-//                        not pending, capped at SITE_NEED_MAX; set_need starts all ones.
+//                        not pending, capped at SITE_NEED_MAX; set_need starts all ones.  heads_only = false
+//                        (site_reads.hip): no head test, d_meta is not read and every kept row of a shard inserts; heads_only
+//                        with a null d_meta is hipErrorInvalidValue.
 //   launch_site_compact  STAGE 3a, one lane per slot (nslots of them): the set's entries as site_item records in any order,
 //                        work[SITE_WORK_ITEMS] of them; sort_key[i] = shard << row_bits | read_row and sort_idx[i] = i
 //   launch_site_reads    STAGE 3b over n items: sort on (shard, read_row), unique: items[i].rid = the read's number among
@@ -539,8 +541,8 @@ size_t site_reads_tmp_bytes(size_t n);
 size_t site_perm_tmp_bytes(size_t n);
 hipError_t launch_site_legs(const void *d_legs, size_t cells, unsigned long long *d_work, hipStream_t stream);
 hipError_t launch_site_rows(const gt_batch &bt, const void *d_legs, const void *d_rows, const unsigned long long *d_nrows, uint64_t cap,
-                            const meta_view *d_meta, uint32_t S, bool tight, void *d_rows_of, const site_set &set, unsigned long long *d_work,
-                            hipStream_t stream);
+                            const meta_view *d_meta, bool heads_only, uint32_t S, bool tight, void *d_rows_of, const site_set &set,
+                            unsigned long long *d_work, hipStream_t stream);
 hipError_t launch_site_compact(const site_set &set, uint32_t S, uint32_t row_bits, void *d_items, void *d_sort_key, void *d_sort_idx, uint64_t cap,
                                unsigned long long *d_work, hipStream_t stream);
 hipError_t launch_site_reads(void *d_items, size_t n, uint32_t S, uint32_t row_bits, void *d_sort_key, void *d_sort_idx, void *d_tmp, size_t tmp_bytes,
@@ -556,6 +558,26 @@ hipError_t launch_site_items(const void *d_items, size_t n, const void *d_rlen, 
 hipError_t launch_site_perm(void *d_perm_key, void *d_perm_idx, size_t n, void *d_key_out, void *d_perm, void *d_tmp, size_t tmp_bytes,
                             hipStream_t stream);
 hipError_t launch_site_tally(const site_tally &a, hipStream_t stream);
+// site_reads.hip: rsbwt_set_site_reads -- the same stages with launch_site_rows told heads_only = false (every kept row is
+// an entry, not the head copies alone), and instead of the tally:
+//   launch_site_classes  after launch_site_addr: d_cflag u64[R + 1] = 1 where read r begins a string class (its shard, length
+//                        or bytes differ from read r - 1's), d_cfirst its exclusive scan (d_cfirst[R] = the classes);
+//                        d_tmp: meta_scan_bytes(R + 1)
+//   launch_site_layout   after the alignment, over n items of Q <= 2^24 requests: sorts them by (request, read number) into
+//                        d_tmp (site_layout_tmp_bytes(n); d_key u64[n] and d_idx u32[n] are its unsorted input), reports an
+//                        item iff its verdict is a KEEP and the item before it is no kept item of the same request and class:
+//                        d_out_rid / d_out_row [*d_nout] in the answer's order, d_first u64[Q * S + 1] the cells' starts;
+//                        work[SITE_WORK_KEPT] += the items with a KEEP verdict
+//   launch_site_gather   16 lanes per reported read: its bytes into d_out + i * stride, the slot's rest zeroed, d_out_len[i] its
+//                        length (UINT32_MAX and a zeroed slot when it is longer than the stride)
+size_t site_layout_tmp_bytes(size_t n);
+hipError_t launch_site_classes(const void *d_raddr, const void *d_rlen, const void *d_seg, uint32_t S, size_t R, void *d_cflag, void *d_cfirst,
+                               void *d_tmp, size_t tmp_bytes, hipStream_t stream);
+hipError_t launch_site_layout(const void *d_items, size_t n, size_t Q, uint32_t S, const void *d_verdict, const void *d_cflag, const void *d_cfirst,
+                              const void *d_rows, const void *d_seg, void *d_key, void *d_idx, void *d_tmp, size_t tmp_bytes, void *d_out_rid,
+                              void *d_out_row, void *d_first, void *d_nout, unsigned long long *d_work, hipStream_t stream);
+hipError_t launch_site_gather(const void *d_out_rid, size_t n, const void *d_raddr, const void *d_rlen, void *d_out, uint32_t stride, void *d_out_len,
+                              hipStream_t stream);
 // (SEL_SHIFT, sample_window, window_samples, window_psi_hint: line_format.h -- shared with the host-side layout test)
 // query / query_exactmatch (query.cpp:87-120) over extracted reads
 hipError_t launch_match_reads(const void *d_reads, const void *d_len, size_t n, uint32_t stride, const void *d_owner,

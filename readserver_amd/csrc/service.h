@@ -23,6 +23,9 @@ struct service_request {
     std::string q;
     int32_t k = 0, s = 0;  // optional int32 k = 4, s = 5 (readserver.proto:9-10); 0 when absent, as protobuf reads them
     bool has_k = false, has_s = false;
+    // SiteMatch: optional int32 p = 6, string a = 7, int32 isalt = 8 (readserver.proto:11-13); 0 / "" when absent
+    int32_t p = 0, isalt = 0;
+    std::string a;
 };
 
 bool service_decode(const uint8_t *msg, size_t len, service_request *out);
@@ -55,6 +58,7 @@ struct reads_config {
     // (QueryTask::run's default branch, service.cpp:1292-1348; KmerTask::run, :917-975)
     bool serve_all = false;
     bool serve_reads = true;                  // rsbwt_service_set_reads' enable: off = Reads requests are not this batch's
+    bool serve_site = false;                  // rsbwt_service_set_sitematch: SiteMatch requests are answered (service_site_batch)
     std::map<std::string, std::string> hash;  // sample code -> name (service.cfg `hashfile`)
     uint32_t size_of_sample = 2;              // service.cfg `size_of_sample` (service.cpp:59,1410-1412)
     bool has_other_meta_data = true;          // service.cfg `has_other_meta_data` (:60,1413-1415)
@@ -98,6 +102,32 @@ int service_kmer_batch(rsbwt_set_t *set, const std::vector<service_request> &rq,
 // appends the 2 x rows Replies (per row: forward, reverse complement) a reference service sends for request r when it
 // finds nothing: KmerTask / QueryTask / GtTask with an empty result (service.cpp:871-960, 1260-1360, 1023-1170)
 void service_append_empty(const service_request &r, size_t rows, reply_arena *replies);
+
+// SiteMatch (GtTask::run, service.cpp:1014-1210): per request, partition (or once, joined) and strand one Reply{rt =
+// SiteMatch, t = (ReplyType) rt, q, c | r | a} with the reads align_gt_read keeps, from rsbwt_set_site_reads /
+// rsbwt_set_site_read_counts -- one call per distinct (k, s) of the batch, both strands of every request as its items.
+// The reads of a Reply come in ascending read_row per partition, not in the reference's unordered_set order.  Count and
+// Reads are taken when cfg.serve_site, All / Samples when cfg.serve_all too.
+inline bool service_takes_site(const service_request &r, const reads_config &cfg) {
+    return cfg.serve_site && r.t == 4 && (r.rt == 1 || r.rt == 2 || (cfg.serve_all && service_is_all_return(r)));
+}
+// The window fix-up of one strand (service.cpp:1028-1046) with L = max_read_length, in signed arithmetic: false = the Reply
+// carries rt, t and q and no sub-message (pos > |w|, the reference's "ERROR" line; and where the reference is undefined:
+// pos < 0, or a substr start past the end).  alt: the (reverse-complemented) a, whole.
+bool service_site_fixup(const std::string &q, int64_t p, const std::string &a, bool revcomp, size_t L, std::string *w, int64_t *pos, std::string *alt);
+// What service_site_batch reaches the engine through (sets.hip fills it in; the host harnesses link a stub): the
+// signatures of rsbwt_set_site_reads / rsbwt_set_site_read_counts
+struct site_engine {
+    int (*reads)(rsbwt_set_t *, const char *, const uint64_t *, size_t, const uint64_t *, const char *, const uint8_t *, int32_t, int32_t, uint64_t, uint64_t *,
+                 char *, uint32_t, uint32_t *, uint64_t *, size_t, size_t *);
+    int (*counts)(rsbwt_set_t *, const char *, const uint64_t *, size_t, const uint64_t *, const char *, const uint8_t *, int32_t, int32_t, uint64_t,
+                  uint64_t *);
+};
+extern site_engine site_engine_hooks;
+int service_site_batch(rsbwt_set_t *set, const std::vector<service_request> &rq, bool per_partition, const reads_config &cfg, reply_arena *replies,
+                       std::vector<char> *handled);
+// the same requests answered with zero counts / empty lists (a failed batch); header-only where the fix-up says so
+void service_site_empty(const std::vector<service_request> &rq, size_t rows, const reads_config &cfg, reply_arena *replies, std::vector<char> *handled);
 
 // What the loop needs of ZeroMQ: the SUB socket it receives Requests on (service.cpp:1495-1497) and
 // the two PUSH sockets it answers on (push for ExactMatch, push_count for CountReads: :1499-1502,1568).

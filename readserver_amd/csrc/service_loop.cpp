@@ -431,6 +431,8 @@ struct rsbwt_service {
     // KmerMatch Count / Reads (KmerTask, service.cpp:1537-1544 -> find_kmer_reads :466-502): answered here when on
     bool serve_kmer = false;
     std::atomic<uint64_t> kmer_requests{0};
+    // SiteMatch (GtTask, service.cpp:1014-1210): answered here when on (reads_cfg.serve_site); All / Samples with serve_all
+    std::atomic<uint64_t> site_requests{0};
     // ExactMatch / KmerMatch requests with return type All or Samples answered from the set's sample table
     // (rsbwt_service_set_all: reads_cfg.serve_all)
     std::atomic<uint64_t> all_requests{0};
@@ -513,16 +515,17 @@ struct rsbwt_service {
         // the window's ExactMatch-Reads requests (find_reads, service.cpp:714-797) and, when on, its KmerMatch Count / Reads
         // requests (find_kmer_reads, :466-502): their Replies are woven into the window's in arrival order.  A failed batch
         // is answered with empty read lists / zero counts, for the same reason as above.
-        bool any_kmer = false, any_unserved = false;
+        bool any_kmer = false, any_site = false, any_unserved = false;
         for (size_t i = 0; i < n; ++i) {
             if (!job.parsed[i] || job.handled[i]) continue;
             if (serve_kmer && service_takes_kmer(job.rq[i], reads_cfg)) any_kmer = true;
+            else if (service_takes_site(job.rq[i], reads_cfg)) any_site = true;
             else if (!service_takes_reads(job.rq[i], reads_cfg)) any_unserved = true;
         }
         any_unserved = any_unserved && unserved_empty && !other;
-        if (!any_reads && !any_kmer && !any_unserved) return;
-        reply_arena rr, kr;
-        std::vector<char> handled_r(n, 0), handled_k(n, 0), capped_r;
+        if (!any_reads && !any_kmer && !any_site && !any_unserved) return;
+        reply_arena rr, kr, sr;
+        std::vector<char> handled_r(n, 0), handled_k(n, 0), handled_s(n, 0), capped_r;
         if (any_reads) {
             rc = service_reads_batch(set, job.rq, per_partition, reads_cfg, &rr, &handled_r, &capped_r);
             if (rc != RSBWT_OK) {
@@ -540,13 +543,22 @@ struct rsbwt_service {
                 kmer_empty(job, rows, &kr, &handled_k);
             }
         }
+        if (any_site) {
+            rc = service_site_batch(set, job.rq, per_partition, reads_cfg, &sr, &handled_s);
+            if (rc != RSBWT_OK) {
+                note_failure(rc, n, "site");
+                service_site_empty(job.rq, rows, reads_cfg, &sr, &handled_s);
+            }
+            for (size_t i = 0; i < n; ++i)
+                if (!job.parsed[i]) handled_s[i] = 0;
+        }
         reply_arena all;
         all.off.assign(1, 0);
         all.first.assign(n + 1, 0);
-        all.bytes.reserve(job.rep.bytes.size() + rr.bytes.size() + kr.bytes.size());
+        all.bytes.reserve(job.rep.bytes.size() + rr.bytes.size() + kr.bytes.size() + sr.bytes.size());
         for (size_t i = 0; i < n; ++i) {
             all.first[i] = all.off.size() - 1;
-            const reply_arena *src = job.handled[i] ? &job.rep : handled_r[i] ? &rr : handled_k[i] ? &kr : nullptr;
+            const reply_arena *src = job.handled[i] ? &job.rep : handled_r[i] ? &rr : handled_k[i] ? &kr : handled_s[i] ? &sr : nullptr;
             if (!src) {
                 if (any_unserved && job.parsed[i] && is_unserved(job.rq[i])) {
                     note_unserved(job.rq[i]);
@@ -562,6 +574,7 @@ struct rsbwt_service {
             const bool is_all = service_is_all_return(job.rq[i]);  // (counted apart: the Reads / KmerMatch counters keep their meaning)
             if (handled_r[i]) { job.handled[i] = 2; if (is_all) all_requests++; else read_requests++; }
             if (handled_k[i]) { job.handled[i] = 3; if (is_all) all_requests++; else kmer_requests++; }
+            if (handled_s[i]) { job.handled[i] = 5; if (is_all) all_requests++; else site_requests++; }
         }
         all.first[n] = all.off.size() - 1;
         job.rep = std::move(all);
@@ -573,6 +586,7 @@ struct rsbwt_service {
         if (r.t < 2 || r.t > 4 || r.rt < 1 || r.rt > 4) return false;
         if (r.t == 2 && (r.rt == 1 || service_takes_reads(r, reads_cfg))) return false;
         if (serve_kmer && service_takes_kmer(r, reads_cfg)) return false;
+        if (service_takes_site(r, reads_cfg)) return false;
         return true;
     }
     void note_unserved(const service_request &r) {
@@ -710,6 +724,9 @@ struct rsbwt_service {
                     }
                 }  else if (serve_kmer && job.parsed[i] && service_takes_kmer(job.rq[i], reads_cfg)) {
                     job.handled[i] = 3;
+                    service_append_empty(job.rq[i], rows, &all);
+                } else if (job.parsed[i] && service_takes_site(job.rq[i], reads_cfg)) {
+                    job.handled[i] = 5;
                     service_append_empty(job.rq[i], rows, &all);
                 } else if (unserved_empty && !other && job.parsed[i] && is_unserved(job.rq[i])) {
                     job.handled[i] = 4;
@@ -1002,6 +1019,24 @@ int rsbwt_service_set_kmermatch(rsbwt_service_t *s, int enable) {
         return RSBWT_OK;
     });
 }
+
+int rsbwt_service_set_sitematch(rsbwt_service_t *s, int enable) {
+    return guarded("rsbwt_service_set_sitematch", [&]() -> int {
+        if (!s) return fail(RSBWT_EINVAL, "null service");
+        if (enable && (!site_engine_hooks.reads || !kmer_engine_hooks.opened_for_reads)) return fail(RSBWT_ENODEV, "the SiteMatch path is not part of this build");
+        if (enable) {
+            for (size_t i = 0; i < rsbwt_set_size(s->set); ++i)
+                if (!kmer_engine_hooks.opened_for_reads(rsbwt_set_shard(s->set, i)))
+                    return fail(RSBWT_EINVAL, "sitematch needs every shard opened with RSBWT_OPEN_READS; shard %zu was not", i);
+            // (a window has at most 2 x max_read_length - 1 symbols, and the alignment takes 4,096)
+            if (s->reads_cfg.max_read_length > 2048)
+                return fail(RSBWT_EINVAL, "sitematch takes a max_read_length of at most 2048; it is %zu", s->reads_cfg.max_read_length);
+        }
+        s->reads_cfg.serve_site = enable != 0;
+        return RSBWT_OK;
+    });
+}
+uint64_t rsbwt_service_site_requests(const rsbwt_service_t *s) { return s ? s->site_requests.load() : 0; }
 
 int rsbwt_service_set_max_match_reads(rsbwt_service_t *s, uint64_t n) {
     return guarded("rsbwt_service_set_max_match_reads", [&]() -> int {

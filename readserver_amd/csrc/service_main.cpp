@@ -4,7 +4,9 @@
 // requests in micro-batches (`GET /get?output=count|reads`), and KmerMatch Count / Reads when `kmermatch = "on"`;
 // with `meta = "<pairs file>"` also ExactMatch requests whose return type is All or Samples (`output=all`, what
 // scripts/client.pl asks for by default) and, with kmermatch on, KmerMatch ones: every read with its samples, from a
-// table in HBM built from the file the reference loads into RocksDB.  Requests of other types (SiteMatch; All / Samples
+// table in HBM built from the file the reference loads into RocksDB.  SiteMatch requests (`/gt`) are answered when
+// `sitematch = "on"`: Count and Reads, and All / Samples with `meta`; the reads of a Reply come in ascending read_row per
+// partition, not in the reference's unordered_set order.  Requests of other types (SiteMatch with sitematch off; All / Samples
 // without `meta`) are left unanswered unless `unserved = "empty"` (they belong to the RocksDB-backed paths of the
 // reference's service, which can run beside this process on `push`).
 //
@@ -16,6 +18,8 @@
 //   suffixes = [ "<suffix of shard 0>", ... ];    the partitions' `suffix` values (default: `suffix` for a single shard)
 //   reads = "on" | "off";                         off: ExactMatch-Reads requests are not answered here
 //   kmermatch = "on" | "off";                     on: KmerMatch Count / Reads requests are answered here (default off)
+//   sitematch = "on" | "off";                     on: SiteMatch requests are answered here (rsbwt_set_site_reads; needs
+//                                                 max_read_length <= 2048; default off)
 //   exactmatch = "extract" | "search";            how "is this tile itself a read?" is answered (Reads, KmerMatch): by extracting
 //                                                 the reads of its interval, or by backward search from the terminator
 //                                                 rows (rsbwt_exactmatch_by_search); the replies are the same (default extract)
@@ -60,6 +64,12 @@ int main(int argc, char **argv) {
         fprintf(stderr, "service.cfg: kmermatch = \"%s\": \"on\" or \"off\"\n", kmermatch);
         return EXIT_FAILURE;
     }
+    const char *sitematch = get(cfg, "sitematch", "off");
+    if (strcmp(sitematch, "on") != 0 && strcmp(sitematch, "off") != 0) {
+        fprintf(stderr, "service.cfg: sitematch = \"%s\": \"on\" or \"off\"\n", sitematch);
+        return EXIT_FAILURE;
+    }
+    const bool serve_site = strcmp(sitematch, "on") == 0;
     if (*unserved && strcmp(unserved, "empty") != 0) {
         fprintf(stderr, "service.cfg: unserved = \"%s\": the one value known is \"empty\"\n", unserved);
         return EXIT_FAILURE;
@@ -109,7 +119,7 @@ int main(int argc, char **argv) {
     // include/rsbwt.h, RSBWT_OPEN_READS)
     const bool serve_reads = strcmp(get(cfg, "reads", "on"), "off") != 0;
     if (rsbwt_set_open(cpaths.data(), cpaths.size(), devs.data(),
-                       RSBWT_OPEN_KTAB_GROUPED | (serve_reads || serve_kmer || *meta ? RSBWT_OPEN_READS : 0u), &set) != RSBWT_OK) {
+                       RSBWT_OPEN_KTAB_GROUPED | (serve_reads || serve_kmer || serve_site || *meta ? RSBWT_OPEN_READS : 0u), &set) != RSBWT_OK) {
         fprintf(stderr, "%s\n", rsbwt_last_error());
         return EXIT_FAILURE;
     }
@@ -138,6 +148,10 @@ int main(int argc, char **argv) {
     // min_read_length / max_read_length: service.cpp:1417-1420 (defaults 73 / 100, :56-57)
     rsbwt_service_set_reads(svc, serve_reads ? 1 : 0, (uint32_t)atoi(get(cfg, "min_read_length", "0")), (uint32_t)atoi(get(cfg, "max_read_length", "0")));
     if (rsbwt_service_set_kmermatch(svc, serve_kmer ? 1 : 0) != RSBWT_OK) {
+        fprintf(stderr, "%s\n", rsbwt_last_error());
+        return EXIT_FAILURE;
+    }
+    if (rsbwt_service_set_sitematch(svc, serve_site ? 1 : 0) != RSBWT_OK) {
         fprintf(stderr, "%s\n", rsbwt_last_error());
         return EXIT_FAILURE;
     }

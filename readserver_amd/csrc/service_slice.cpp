@@ -39,6 +39,10 @@ struct request_view {
     size_t qlen = 0;
     int32_t k = 0, s = 0;   // KmerMatch / SiteMatch: optional int32 k = 4, s = 5 (readserver.proto:9-10)
     bool has_t = false, has_rt = false, has_q = false, has_k = false, has_s = false;
+    int32_t p = 0, isalt = 0;  // SiteMatch: optional int32 p = 6, string a = 7, int32 isalt = 8 (readserver.proto:11-13)
+    const char *a = nullptr;
+    size_t alen = 0;
+    bool has_p = false, has_a = false, has_isalt = false;
 };
 
 bool get_varint(const uint8_t *&p, const uint8_t *end, uint64_t &v) {
@@ -64,10 +68,13 @@ bool decode_request(const uint8_t *p, size_t n, request_view &r) {
             else if (field == 2) { r.rt = (int)v; r.has_rt = true; }
             else if (field == 4) { r.k = (int32_t)(uint32_t)v; r.has_k = true; }  // (int32: a negative value arrives sign-extended)
             else if (field == 5) { r.s = (int32_t)(uint32_t)v; r.has_s = true; }
+            else if (field == 6) { r.p = (int32_t)(uint32_t)v; r.has_p = true; }
+            else if (field == 8) { r.isalt = (int32_t)(uint32_t)v; r.has_isalt = true; }
         } else if (wt == 2) {
             uint64_t len;
             if (!get_varint(p, end, len) || len > (uint64_t)(end - p)) return false;
             if (field == 3) { r.q = (const char *)p; r.qlen = (size_t)len; r.has_q = true; }
+            else if (field == 7) { r.a = (const char *)p; r.alen = (size_t)len; r.has_a = true; }
             p += len;
         } else if (wt == 1) {
             if (end - p < 8) return false;
@@ -145,6 +152,20 @@ int rsbwt_proto_decode_request_ks(const uint8_t *msg, size_t len, int32_t *k, in
     if (has_k) *has_k = r.has_k ? 1 : 0;
     if (s) *s = r.s;
     if (has_s) *has_s = r.has_s ? 1 : 0;
+    return RSBWT_OK;
+}
+
+int rsbwt_proto_decode_request_site(const uint8_t *msg, size_t len, int32_t *p, int *has_p, const char **a, size_t *alen, int *has_a, int32_t *isalt,
+                                    int *has_isalt) {
+    request_view r;
+    if (!msg || !decode_request(msg, len, r)) return RSBWT_EFORMAT;
+    if (p) *p = r.p;
+    if (has_p) *has_p = r.has_p ? 1 : 0;
+    if (a) *a = r.a;
+    if (alen) *alen = r.alen;
+    if (has_a) *has_a = r.has_a ? 1 : 0;
+    if (isalt) *isalt = r.isalt;
+    if (has_isalt) *has_isalt = r.has_isalt ? 1 : 0;
     return RSBWT_OK;
 }
 
@@ -879,6 +900,205 @@ int service_kmer_batch(rsbwt_set_t *set, const std::vector<service_request> &rq,
     return RSBWT_OK;
 }
 
+// ---- SiteMatch: GtTask::run (service.cpp:1014-1210) over rsbwt_set_site_reads ----------------------------------------
+site_engine site_engine_hooks = {nullptr, nullptr};
+
+bool service_site_fixup(const std::string &q, int64_t p, const std::string &a, bool revcomp, size_t L, std::string *w, int64_t *pos, std::string *alt) {
+    std::string query = q;
+    int64_t at = p;
+    *alt = a;
+    if (revcomp) {  // :1028-1032
+        query = rev_comp(q.data(), q.size());
+        at = (int64_t)q.size() - p + 1;
+        *alt = rev_comp(a.data(), a.size());
+    }
+    w->clear();
+    *pos = at;
+    if (at < 0) return false;  // (the reference takes pos as size_t: undefined from here on)
+    const int64_t max_len = (int64_t)L;
+    if (at <= max_len) {  // :1034-1036
+        *w = query.substr(0, (size_t)(max_len + at - 1 > 0 ? max_len + at - 1 : 0));
+    } else {  // :1037-1040
+        if ((uint64_t)(at - max_len) > query.size()) return false;  // (substr throws there)
+        *w = query.substr((size_t)(at - max_len), (size_t)(2 * max_len - 1));
+        *pos = at = max_len;
+    }
+    return (uint64_t)at <= w->size();  // :1044
+}
+
+namespace {
+
+// Reply{rt, t, q}: what GtTask::run sends after its "ERROR" line (no c / r / a sub-message)
+void append_header_reply(std::vector<uint8_t> *out, int request_type, int reply_type, const std::string &q) {
+    const size_t at = out->size();
+    out->resize(at + 1 + varint_len((uint64_t)request_type) + 1 + varint_len((uint64_t)reply_type) + 1 + varint_len(q.size()) + q.size());
+    uint8_t *p = out->data() + at;
+    *p++ = 0x08; p = put_varint(p, (uint64_t)request_type);
+    *p++ = 0x10; p = put_varint(p, (uint64_t)reply_type);
+    *p++ = 0x1A; p = put_varint(p, q.size());
+    if (!q.empty()) memcpy(p, q.data(), q.size());
+}
+
+struct site_strand {
+    size_t req = 0;
+    bool header = false, run = false;  // header: no sub-message; run: an item of an engine call (else nothing is kept)
+    std::string w, alt;
+    int64_t pos = 0;
+    std::vector<std::vector<std::string>> reads;  // [shard], ascending read_row
+    std::vector<uint64_t> count;                  // [shard]
+};
+
+}  // namespace
+
+void service_site_empty(const std::vector<service_request> &rq, size_t rows, const reads_config &cfg, reply_arena *replies, std::vector<char> *handled) {
+    const size_t n = rq.size();
+    const std::vector<const std::string *> none;
+    handled->assign(n, 0);
+    replies->bytes.clear();
+    replies->off.assign(1, 0);
+    replies->first.assign(n + 1, 0);
+    for (size_t i = 0; i < n; ++i) {
+        replies->first[i] = replies->off.size() - 1;
+        if (!service_takes_site(rq[i], cfg)) continue;
+        (*handled)[i] = 1;
+        bool header[2];
+        for (int strand = 0; strand < 2; ++strand) {
+            std::string w, alt;
+            int64_t pos;
+            header[strand] = !service_site_fixup(rq[i].q, rq[i].p, rq[i].a, strand == 1, cfg.max_read_length, &w, &pos, &alt);
+        }
+        for (size_t r = 0; r < rows; ++r)
+            for (int strand = 0; strand < 2; ++strand) {
+                if (header[strand]) append_header_reply(&replies->bytes, rq[i].t, rq[i].rt, rq[i].q);
+                else append_kmer_reply(&replies->bytes, rq[i].t, rq[i].rt, rq[i].q, strand == 1, none, 0);
+                replies->off.push_back(replies->bytes.size());
+            }
+    }
+    replies->first[n] = replies->off.size() - 1;
+}
+
+int service_site_batch(rsbwt_set_t *set, const std::vector<service_request> &rq, bool per_partition, const reads_config &cfg, reply_arena *replies,
+                       std::vector<char> *handled) {
+    const size_t n = rq.size(), S = rsbwt_set_size(set), L = cfg.max_read_length;
+    handled->assign(n, 0);
+    replies->bytes.clear();
+    replies->off.assign(1, 0);
+    replies->first.assign(n + 1, 0);
+    std::vector<site_strand> st;  // 2 per handled request: forward, reverse complement
+    std::map<std::pair<int32_t, int32_t>, std::vector<size_t>> by_ks;  // one engine call per distinct (k, s)
+    for (size_t i = 0; i < n; ++i) {
+        if (!service_takes_site(rq[i], cfg)) continue;
+        (*handled)[i] = 1;
+        for (int strand = 0; strand < 2; ++strand) {
+            site_strand x;
+            x.req = i;
+            x.header = !service_site_fixup(rq[i].q, rq[i].p, rq[i].a, strand == 1, L, &x.w, &x.pos, &x.alt);
+            // (an empty a keeps nothing; pos = 0, k <= 0, s < 0 and k > |w| are the engine's own rule: gt_make_plan, rsbwt_gt_align)
+            x.run = !x.header && !x.alt.empty();
+            x.reads.resize(S);
+            x.count.assign(S, 0);
+            if (x.run) by_ks[{rq[i].k, rq[i].s}].push_back(st.size());
+            st.push_back(std::move(x));
+        }
+    }
+    if (st.empty()) return RSBWT_OK;
+    if (!by_ks.empty() && (!site_engine_hooks.reads || !site_engine_hooks.counts)) return fail(RSBWT_ENODEV, "the SiteMatch path is not part of this build");
+    const uint32_t stride = (uint32_t)std::max<size_t>(256, (2 * L + 63) & ~(size_t)15);
+    for (auto &g : by_ks) {
+        const std::vector<size_t> &members = g.second;
+        const size_t m = members.size();
+        std::string text, alt(m, 'N');
+        std::vector<uint64_t> off(m + 1, 0), pos(m);
+        std::vector<uint8_t> isalt(m);
+        bool want_reads = false;
+        for (size_t j = 0; j < m; ++j) {
+            const site_strand &x = st[members[j]];
+            text += x.w;
+            off[j + 1] = text.size();
+            pos[j] = (uint64_t)x.pos;
+            alt[j] = x.alt[0];  // alt[q]: the first character
+            isalt[j] = rq[x.req].isalt == 1 ? 1 : 0;  // :1018
+            want_reads = want_reads || rq[x.req].rt != 1;
+        }
+        std::vector<uint64_t> first(m * S + 1, 0);
+        if (!want_reads) {
+            std::vector<uint64_t> counts(m * S, 0);
+            const int rc = site_engine_hooks.counts(set, text.data(), off.data(), m, pos.data(), alt.data(), isalt.data(), g.first.first, g.first.second, 0,
+                                                    counts.data());
+            if (rc != RSBWT_OK) return rc;
+            for (size_t j = 0; j < m; ++j)
+                for (size_t p = 0; p < S; ++p) st[members[j]].count[p] = counts[j * S + p];
+            continue;
+        }
+        size_t room = 64 * m + 256, nreads = 0;  // one call answers when the reads fit, else it says how many there are
+        std::vector<char> reads;
+        std::vector<uint32_t> rlen;
+        int rc = RSBWT_ERANGE;
+        for (int sized = 0; sized < 2 && rc == RSBWT_ERANGE; ++sized) {
+            reads.assign(room * (size_t)stride, 0);
+            rlen.assign(room, 0);
+            rc = site_engine_hooks.reads(set, text.data(), off.data(), m, pos.data(), alt.data(), isalt.data(), g.first.first, g.first.second, 0, first.data(),
+                                         reads.data(), stride, rlen.data(), nullptr, room, &nreads);
+            if (rc == RSBWT_ERANGE && nreads > room) room = nreads;
+        }
+        if (rc != RSBWT_OK) return rc;
+        for (size_t j = 0; j < m; ++j)
+            for (size_t p = 0; p < S; ++p) {
+                site_strand &x = st[members[j]];
+                x.count[p] = first[j * S + p + 1] - first[j * S + p];
+                for (uint64_t r = first[j * S + p]; r < first[j * S + p + 1]; ++r)
+                    if (rlen[r] != 0xFFFFFFFFu) x.reads[p].emplace_back(reads.data() + r * (size_t)stride, rlen[r]);  // (longer: not a read of this service)
+            }
+    }
+    // ---- the Replies: request by request, partition by partition (or the partitions' lists joined in partition order and
+    // the counts summed), forward then reverse complement
+    const size_t rows = per_partition ? S : 1;
+    std::vector<std::vector<const std::string *>> lists(st.size() * rows);
+    std::vector<std::vector<uint32_t>> lshard(lists.size());
+    std::vector<uint64_t> counts(lists.size(), 0);
+    std::vector<char> is_all(lists.size(), 0);
+    for (size_t si = 0; si < st.size(); ++si)
+        for (size_t r = 0; r < rows; ++r) {
+            const size_t li = si * rows + r;
+            for (size_t p = per_partition ? r : 0; p < (per_partition ? r + 1 : S); ++p) {
+                counts[li] += st[si].count[p];
+                for (const std::string &x : st[si].reads[p]) {
+                    lists[li].push_back(&x);
+                    lshard[li].push_back((uint32_t)p);
+                }
+            }
+            is_all[li] = !st[si].header && service_is_all_return(rq[st[si].req]) ? 1 : 0;
+        }
+    all_values vals;
+    {
+        const int rv = vals.lookup(set, lists, lshard, is_all);
+        if (rv != RSBWT_OK) return rv;
+    }
+    const sample_codec codec = codec_of(cfg);
+    size_t si = 0;
+    for (size_t i = 0; i < n; ++i) {
+        replies->first[i] = replies->off.size() - 1;
+        if (!(*handled)[i]) continue;
+        for (size_t r = 0; r < rows; ++r)
+            for (int strand = 0; strand < 2; ++strand) {
+                const size_t li = (si + strand) * rows + r;
+                if (st[si + strand].header) {
+                    append_header_reply(&replies->bytes, rq[i].t, rq[i].rt, rq[i].q);
+                } else if (is_all[li]) {
+                    const size_t at = replies->bytes.size(), len = vals.encode(nullptr, 0, li, lists[li], rq[i].t, rq[i].rt, rq[i].q, strand == 1, codec);
+                    replies->bytes.resize(at + len);
+                    vals.encode(replies->bytes.data() + at, len, li, lists[li], rq[i].t, rq[i].rt, rq[i].q, strand == 1, codec);
+                } else {
+                    append_kmer_reply(&replies->bytes, rq[i].t, rq[i].rt, rq[i].q, strand == 1, lists[li], counts[li]);
+                }
+                replies->off.push_back(replies->bytes.size());
+            }
+        si += 2;
+    }
+    replies->first[n] = replies->off.size() - 1;
+    return RSBWT_OK;
+}
+
 bool service_decode(const uint8_t *msg, size_t len, service_request *out) {
     request_view r;
     if (!decode_request(msg, len, r)) return false;
@@ -889,6 +1109,9 @@ bool service_decode(const uint8_t *msg, size_t len, service_request *out) {
     out->s = r.s;
     out->has_k = r.has_k;
     out->has_s = r.has_s;
+    out->p = r.p;
+    out->isalt = r.isalt;
+    out->a.assign(r.a ? r.a : "", r.alen);
     return true;
 }
 

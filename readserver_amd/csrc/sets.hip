@@ -3862,6 +3862,25 @@ struct site_group_out {
     double ms[6] = {0, 0, 0, 0, 0, 0};
 };
 
+// rsbwt_set_site_reads' share of a group's run (site_reads.hip): what the group answers instead of the matrices.  work[] is
+// then {legs, lengthening steps, candidate rows, rows kept, distinct reads, string classes, items aligned, items kept,
+// reads reported}.
+struct site_reads_out {
+    bool want_bytes = false;  // false: first[] alone (the count call)
+    uint32_t stride = 0;
+    // where the reads go when the group's order is the caller's (one group: the copy from the device lands there); else null
+    char *reads = nullptr;
+    uint32_t *len = nullptr;
+    uint64_t *row = nullptr;
+    size_t cap = 0;  // the reads there is room for: a group with more gathers nothing
+    bool stored = false;
+    uint64_t nout = 0;
+    std::vector<uint64_t> first;  // [Q * S_g + 1]
+    std::vector<char> bytes_v;    // (several groups: the group's reads in its own order)
+    std::vector<uint32_t> len_v;
+    std::vector<uint64_t> row_v;
+};
+
 // a lease beyond a group_call's two: goes back when the call leaves, after the stream has drained
 struct site_lease {
     dev_group *g;
@@ -3880,13 +3899,73 @@ struct site_lease {
     }
 };
 
+// The tail of a run that answers rsbwt_set_site_reads (site_reads.hip), after the alignment: the answer laid out where it
+// is.  The sort's buffers and the layout's scratch are gc.lb's, free since the distinct reads were made; the reported
+// reads' numbers and rows take the alignment's order and request arrays, which the alignment read for the last time.
+struct site_tail_args {
+    uint8_t *d_items, *d_verdict, *d_cflag, *d_cfirst, *d_drows, *d_seg, *d_sort_key, *d_sort_idx, *d_reads_tmp, *d_pkey, *d_req, *d_gfirst, *d_sizes,
+        *d_raddr, *d_rlen;
+    size_t reads_tmp, Q, R;
+    uint64_t n;
+    uint32_t S;
+    unsigned long long *work;
+};
+int site_reads_tail(dev_group *g, group_call &gc, const site_tail_args &a, site_reads_out *rd, uint64_t *classes) {
+    hipStream_t st = gc.st;
+    hipError_t e;
+    e = launch_site_layout(a.d_items, (size_t)a.n, a.Q, a.S, a.d_verdict, a.d_cflag, a.d_cfirst, a.d_drows, a.d_seg, a.d_sort_key, a.d_sort_idx,
+                           a.d_reads_tmp, a.reads_tmp, a.d_pkey, a.d_req, a.d_gfirst, a.d_sizes + 16, a.work, st);
+    if (e != hipSuccess) return fail_hip(e, "answer layout kernel launches");
+    uint64_t nout = 0;
+    HIP_OK(hipMemcpyAsync(&nout, a.d_sizes + 16, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(classes, a.d_cfirst + a.R * 8, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(rd->first.data(), a.d_gfirst, rd->first.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (nout > a.n || *classes == 0 || *classes > a.R)
+        return fail(RSBWT_EHIP, "%llu reads reported of %llu items, %llu classes of %zu reads", (unsigned long long)nout, (unsigned long long)a.n,
+                    (unsigned long long)*classes, a.R);
+    rd->nout = nout;
+    if (rd->want_bytes && nout != 0 && nout <= rd->cap) {
+        // the rows, the set and the items are done with: their lease goes back and the reads' slots take its place
+        g->scratch.give(gc.lb, st);
+        gc.lb = scratch_cache::lease();
+        const size_t a_out = al256((size_t)nout * rd->stride);
+        e = g->scratch.take(a_out + al256((size_t)nout * 4), st, &gc.lb);
+        if (e != hipSuccess)
+            return fail(RSBWT_ENOMEM, "%llu reads at stride %u do not fit the device's free memory: %s", (unsigned long long)nout, rd->stride,
+                        hipGetErrorString(e));
+        uint8_t *d_out = (uint8_t *)gc.lb.p, *d_olen = d_out + a_out;
+        if ((e = launch_site_gather(a.d_pkey, (size_t)nout, a.d_raddr, a.d_rlen, d_out, rd->stride, d_olen, st)) != hipSuccess)
+            return fail_hip(e, "read gather kernel launch");
+        char *hb = rd->reads;
+        uint32_t *hl = rd->len;
+        uint64_t *hr = rd->row;
+        if (!hb) {
+            rd->bytes_v.resize((size_t)nout * rd->stride);
+            rd->len_v.resize((size_t)nout);
+            rd->row_v.resize((size_t)nout);
+            hb = rd->bytes_v.data();
+            hl = rd->len_v.data();
+            hr = rd->row_v.data();
+        }
+        HIP_OK(hipMemcpyAsync(hb, d_out, (size_t)nout * rd->stride, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(hl, d_olen, (size_t)nout * 4, hipMemcpyDeviceToHost, st));
+        if (hr) HIP_OK(hipMemcpyAsync(hr, a.d_req, (size_t)nout * 8, hipMemcpyDeviceToHost, st));
+        rd->stored = true;
+    }
+    return RSBWT_OK;
+}
+
 // One device group's share of a slice (site_counts.hip has the stages).  The host reads back, eight bytes each: the row
 // total, the kept rows / rows not located / items, the distinct reads, the reads over the first stride and the longest that
 // fit; then the matrices, the two count vectors and the counters.  Three leases at most are held at a time (gc.la: the
 // batch; gc.lb: rows, set and items; lc: reads and what the alignment and the tally need) plus a launch's own short one,
 // so four calls at once stay inside the cache's 16 slots.
+// rd: the run answers rsbwt_set_site_reads instead (site_reads.hip): no head test, no dictionary, no tally; after the
+// alignment the answer is laid out on the device and the host reads back two more sizes (string classes, reads reported),
+// the group's first[] and the reported reads' slots, lengths and rows, which take gc.lb's place once its rows are done with.
 int site_group_run(rsbwt_set_t *s, dev_group *g, const gt_plan &pl, const char *t0, const site_requests &rq, const sample_dict &d, bool tight,
-                   uint32_t row_bits, bool want_strings, bool want_copies, site_group_out *out) {
+                   uint32_t row_bits, bool want_strings, bool want_copies, site_group_out *out, site_reads_out *rd = nullptr) {
     group_call gc(g, true);
     if (gc.rc) return gc.rc;
     hipStream_t st = gc.st;
@@ -3906,7 +3985,7 @@ int site_group_run(rsbwt_set_t *s, dev_group *g, const gt_plan &pl, const char *
     HIP_OK(hipMemcpyAsync(d_off, rq.off.data(), (Q + 1) * 8, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_alt, rq.alt, Q, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(d_isalt, rq.isalt, Q, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_keys, d.keys.data(), (size_t)d.C * 8, hipMemcpyHostToDevice, st));
+    if (d.C) HIP_OK(hipMemcpyAsync(d_keys, d.keys.data(), (size_t)d.C * 8, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemsetAsync(d_work, 0, work_bytes + 256, st));
     hipError_t e = launch_site_legs(f.d_legs, cells, work, st);
     if (e == hipSuccess) e = launch_interval_totals(g->d_views, S, f.d_pairs, N, 0, f.d_matches, f.d_keptq, f.d_first, f.d_over, f.d_tmp, f.tmp_bytes, st);
@@ -3920,7 +3999,8 @@ int site_group_run(rsbwt_set_t *s, dev_group *g, const gt_plan &pl, const char *
     out->carriers.assign(Q, 0);
     std::vector<unsigned long long> hwork(SITE_WORK_COUNTERS * TALLY_WORK_STRIDE, 0);
     unsigned long long hwk[3] = {0, 0, 0};
-    uint64_t nreads = 0;
+    uint64_t nreads = 0, classes = 0;
+    if (rd) rd->first.assign(Q * (size_t)S + 1, 0);
     auto finish = [&]() -> int {  // the counters, once everything is enqueued
         HIP_OK(hipMemcpyAsync(hwork.data(), d_work, work_bytes, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(hwk, f.d_wk, sizeof hwk, hipMemcpyDeviceToHost, st));
@@ -3931,6 +4011,10 @@ int site_group_run(rsbwt_set_t *s, dev_group *g, const gt_plan &pl, const char *
         const uint64_t mine[10] = {w(SITE_WORK_LEGS), hwk[0], total, hwk[1], w(SITE_WORK_HEADS), nreads, w(SITE_WORK_ALIGNED), w(SITE_WORK_KEPT),
                                    w(SITE_WORK_RECORDS), w(SITE_WORK_UNKNOWN)};
         for (int i = 0; i < 10; ++i) out->work[i] = mine[i];
+        if (rd) {
+            const uint64_t reads9[10] = {w(SITE_WORK_LEGS), hwk[0], total, hwk[1], nreads, classes, w(SITE_WORK_ALIGNED), w(SITE_WORK_KEPT), rd->nout, 0};
+            for (int i = 0; i < 10; ++i) out->work[i] = reads9[i];
+        }
         for (int i = 0; i < 6; ++i) {
             tm.end(i);
             out->ms[i] = tm.ms[i];
@@ -3943,7 +4027,7 @@ int site_group_run(rsbwt_set_t *s, dev_group *g, const gt_plan &pl, const char *
     const uint64_t nslots = 4 * total + S;
     const size_t a8 = al256(total * 8), a4 = al256(total * 4), a_rec = al256(total * sizeof(gt_site_row)), a_s8 = al256((size_t)(S + 1) * 8),
                  a_region = al256((size_t)S * 16), a_set8 = al256(nslots * 8), a_set4 = al256(nslots * 4), a_items = al256(total * sizeof(site_item)),
-                 reads_tmp = site_reads_tmp_bytes(total);
+                 reads_tmp = std::max(site_reads_tmp_bytes(total), rd ? site_layout_tmp_bytes(total) : (size_t)0);
     e = g->scratch.take(5 * a8 + 3 * a4 + a_rec + 2 * a_s8 + a_region + 2 * a_set8 + a_set4 + a_items + reads_tmp, st, &gc.lb);
     if (e != hipSuccess)
         return fail(RSBWT_ENOMEM, "%llu candidate rows do not fit the device's free memory: %s", (unsigned long long)total, hipGetErrorString(e));
@@ -3963,7 +4047,7 @@ int site_group_run(rsbwt_set_t *s, dev_group *g, const gt_plan &pl, const char *
     set.need = (uint32_t *)d_sneed;
     set.region = (uint64_t *)d_region;
     set.nslots = nslots;
-    e = launch_site_rows(f.bt, f.d_legs, d_rec, wk + 1, total, g->d_meta, S, tight, d_rows_of, set, work, st);
+    e = launch_site_rows(f.bt, f.d_legs, d_rec, wk + 1, total, rd ? nullptr : g->d_meta, rd == nullptr, S, tight, d_rows_of, set, work, st);
     if (e == hipSuccess) e = launch_site_compact(set, S, row_bits, d_items, d_sort_key, d_sort_idx, total, work, st);
     if (e != hipSuccess) return fail_hip(e, "head test and set kernel launches");
     tm.end(1);
@@ -3989,12 +4073,13 @@ int site_group_run(rsbwt_set_t *s, dev_group *g, const gt_plan &pl, const char *
     // ---- the reads and everything behind them in lc; taken again with room for the second extraction if a read needs it
     const size_t scan_tmp = meta_scan_bytes(R + 1), perm_tmp = site_perm_tmp_bytes((size_t)n);
     const size_t a_r4 = al256(R * 4), a_r8 = al256((R + 1) * 8), a_n8 = al256((size_t)n * 8), a_n4 = al256((size_t)n * 4), a_n1 = al256((size_t)n),
-                 a_q8 = al256(Q * 8), a_str = want_strings ? al256(mcells * 4) : 0, a_cp = want_copies ? al256(mcells * 8) : 0;
+                 a_q8 = al256(Q * 8), a_str = want_strings ? al256(mcells * 4) : 0, a_cp = want_copies ? al256(mcells * 8) : 0,
+                 a_first = rd ? al256((Q * (size_t)S + 1) * 8) : 0, a_cls = rd ? 2 * a_r8 : 0;
     uint64_t n_over = 0, longest = 0;
     uint8_t *d_reads = nullptr, *d_plen = nullptr, *d_rlen = nullptr, *d_overf = nullptr, *d_ofirst = nullptr, *d_scan = nullptr, *d_raddr = nullptr,
             *d_req = nullptr, *d_rid = nullptr, *d_pkey = nullptr, *d_pidx = nullptr, *d_pkey2 = nullptr, *d_perm = nullptr, *d_ptmp = nullptr,
             *d_verdict = nullptr, *d_aligned = nullptr, *d_carriers = nullptr, *d_str = nullptr, *d_cp = nullptr, *d_ksw = nullptr, *d_wide = nullptr,
-            *d_wplen = nullptr, *d_wlen = nullptr, *d_wrows = nullptr, *d_wseg = nullptr;
+            *d_wplen = nullptr, *d_wlen = nullptr, *d_wrows = nullptr, *d_wseg = nullptr, *d_cflag = nullptr, *d_cfirst = nullptr, *d_gfirst = nullptr;
     size_t ksw_bytes = 0;
     for (int round = 0; round < 2; ++round) {
         const size_t W = (size_t)n_over;  // (0 in the first round)
@@ -4002,7 +4087,7 @@ int site_group_run(rsbwt_set_t *s, dev_group *g, const gt_plan &pl, const char *
         const size_t a_reads = al256(R * (size_t)SITE_STRIDE), a_wide = al256(W * (size_t)SITE_WIDE_STRIDE), a_w4 = al256(W * 4), a_w8 = al256(W * 8);
         lc.drop();
         e = g->scratch.take(a_reads + 2 * a_r4 + 3 * a_r8 + al256(scan_tmp) + a_n8 + 5 * a_n4 + al256(perm_tmp) + a_n1 + 2 * a_q8 + a_str + a_cp +
-                                al256(ksw_bytes) + a_wide + 2 * a_w4 + a_w8 + al256((size_t)(S + 1) * 8) + 256,
+                                al256(ksw_bytes) + a_wide + 2 * a_w4 + a_w8 + al256((size_t)(S + 1) * 8) + a_cls + a_first + 256,
                             st, &lc.l);
         if (e != hipSuccess)
             return fail(RSBWT_ENOMEM, "%zu reads, %llu items and %zu matrix cells do not fit the device's free memory: %s", R, (unsigned long long)n, mcells,
@@ -4032,6 +4117,9 @@ int site_group_run(rsbwt_set_t *s, dev_group *g, const gt_plan &pl, const char *
         d_wlen = d_wplen + a_w4;
         d_wrows = d_wlen + a_w4;
         d_wseg = d_wrows + a_w8;
+        d_cflag = d_wseg + al256((size_t)(S + 1) * 8);
+        d_cfirst = d_cflag + a_r8;
+        d_gfirst = d_cflag + a_cls;
         tm.begin(2);
         HIP_OK(hipMemsetAsync(d_sizes + 8, 0, 8, st));
         e = launch_extract_ragged(g->scratch, g->d_xviews, S, d_drows, R, d_seg, 1, d_reads, SITE_STRIDE, d_plen, d_rlen, g->num_cus, st);
@@ -4054,6 +4142,8 @@ int site_group_run(rsbwt_set_t *s, dev_group *g, const gt_plan &pl, const char *
     }
     e = launch_site_addr(d_reads, SITE_STRIDE, n_over ? d_wide : nullptr, SITE_WIDE_STRIDE, d_overf, d_ofirst, d_wlen, R, d_raddr, d_rlen, st);
     if (e != hipSuccess) return fail_hip(e, "read address kernel launch");
+    if (rd && (e = launch_site_classes(d_raddr, d_rlen, d_seg, S, R, d_cflag, d_cfirst, d_scan, scan_tmp, st)) != hipSuccess)
+        return fail_hip(e, "string class kernel launch");
     tm.end(2);
     tm.begin(3);
     // ---- stage 4: the length rule, the alignment's batch and its order
@@ -4084,6 +4174,12 @@ int site_group_run(rsbwt_set_t *s, dev_group *g, const gt_plan &pl, const char *
     if (e != hipSuccess) return fail_hip(e, "gt alignment kernel launch");
     tm.end(4);
     tm.begin(5);
+    if (rd) {
+        const site_tail_args ta = {d_items,  d_verdict, d_cflag, d_cfirst, d_drows, d_seg,     d_sort_key, d_sort_idx, d_reads_tmp, d_pkey, d_req,
+                                   d_gfirst, d_sizes,   d_raddr, d_rlen,   reads_tmp, Q,       R,          n,          S,           work};
+        if ((rc = site_reads_tail(g, gc, ta, rd, &classes)) != RSBWT_OK) return rc;
+        return finish();
+    }
     // ---- stage 5: the kept reads' records
     site_tally ta;
     ta.items = (const site_item *)d_items;
@@ -4191,6 +4287,105 @@ int set_site_counts_body(rsbwt_set_t *s, const char *text, const uint64_t *off, 
     return RSBWT_OK;
 }
 
+// ---- site reads (site_reads.hip): rsbwt_set_gt_aligned_reads' answer with the batch kept on the device ----
+// the calling thread's last call: legs, LF steps spent lengthening, candidate rows, rows the span filter kept, distinct reads
+// extracted, string classes among them, (request, read) items aligned, items kept, reads reported
+thread_local uint64_t site_reads_last_work[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+// reads = nullptr: first[] alone (want_bytes false), or the sizing call.  *total = the reads of the answer whatever the room.
+int set_site_reads_body(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, const char *alt, const uint8_t *isalt,
+                        int32_t k, int32_t skip, uint64_t M, uint64_t *first, bool want_bytes, char *reads, uint32_t read_stride, uint32_t *read_len,
+                        uint64_t *read_row, size_t cap_reads, size_t *total) {
+    for (uint64_t &w : site_reads_last_work) w = 0;
+    *total = 0;
+    if (!s) return fail(RSBWT_EINVAL, "null set");
+    if (Q && (!off || !pos || !alt || !isalt || !first || (!text && off[Q] != off[0]))) return fail(RSBWT_EINVAL, "null argument");
+    for (size_t q = 0; q < Q; ++q) {
+        if (off[q] > off[q + 1]) return fail(RSBWT_EINVAL, "query %zu: offsets not ascending", q);
+        if (off[q + 1] - off[q] > (uint64_t)RSBWT_KSW_MAX_LEN)
+            return fail(RSBWT_EINVAL, "query %zu: %llu symbols, at most %d", q, (unsigned long long)(off[q + 1] - off[q]), RSBWT_KSW_MAX_LEN);
+    }
+    const size_t S = s->shards.size(), G = s->groups.size();
+    if (S > 65535) return fail(RSBWT_EINVAL, "%zu shards: at most 65535", S);
+    uint32_t row_bits = 1;
+    for (rsbwt_t *h : s->shards) {
+        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
+        if (!rsbwt_opened_for_reads(h)) return fail(RSBWT_EINVAL, "site reads need shards opened with RSBWT_OPEN_READS");
+        if (h->view.C[1] >= (1ull << 40)) return fail(RSBWT_EINVAL, "a shard of %llu strings: site reads take fewer than 2^40", (unsigned long long)h->view.C[1]);
+        while (row_bits < 64 && (h->view.n >> row_bits) != 0) ++row_bits;
+    }
+    if (row_bits > 46) return fail(RSBWT_EINVAL, "a shard of 2^%u symbols: site reads take fewer than 2^46", row_bits);
+    if (first) first[0] = 0;
+    if (Q == 0) return RSBWT_OK;
+    std::vector<std::pair<size_t, size_t>> where(S);  // shard of the set -> (group, shard of the group)
+    for (size_t gi = 0; gi < G; ++gi)
+        for (size_t j = 0; j < s->groups[gi]->idx.size(); ++j) where[s->groups[gi]->idx[j]] = {gi, j};
+    const size_t SLICE = (size_t)1 << 24;  // a request number of the set's keys and of the layout's has 24 bits
+    const sample_dict none;
+    uint64_t work9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    size_t at = 0;  // the reads of the slices before this one
+    for (size_t q0 = 0; q0 < Q; q0 += SLICE) {
+        const size_t mq = std::min(SLICE, Q - q0);
+        gt_plan pl;
+        int rc = gt_make_plan(text, off + q0, mq, pos + q0, k, skip, M, &pl);
+        if (rc) return rc;
+        if (pl.nitems == 0) {
+            for (size_t c = q0 * S; c < (q0 + mq) * S; ++c) first[c + 1] = at;
+            continue;
+        }
+        site_requests rq;
+        rq.off.resize(mq + 1);
+        rq.lo_w = (uint32_t)RSBWT_KSW_MAX_LEN;
+        for (size_t q = 0; q <= mq; ++q) rq.off[q] = off[q0 + q] - off[q0];
+        for (size_t q = 0; q < mq; ++q) {
+            const uint32_t wl = (uint32_t)(rq.off[q + 1] - rq.off[q]);
+            rq.hi_w = std::max(rq.hi_w, wl);
+            if (wl) rq.lo_w = std::min(rq.lo_w, wl);
+        }
+        rq.alt = alt + q0;
+        rq.isalt = isalt + q0;
+        const size_t room = cap_reads > at ? cap_reads - at : 0;
+        const bool direct = G == 1 && s->groups[0]->idx.size() == S && reads && read_len;  // (one group numbers the shards as the set does)
+        std::vector<site_group_out> outs(G);
+        std::vector<site_reads_out> rds(G);
+        for (site_reads_out &rd : rds) {
+            rd.want_bytes = want_bytes && reads && read_len;
+            rd.stride = read_stride;
+            rd.cap = room;
+            if (direct) {
+                rd.reads = reads + at * (size_t)read_stride;
+                rd.len = read_len + at;
+                rd.row = read_row ? read_row + at : nullptr;
+            }
+        }
+        rc = for_each_group(s, [&](size_t gi) -> int {
+            return site_group_run(s, s->groups[gi], pl, text + off[q0], rq, none, false, row_bits, false, false, &outs[gi], &rds[gi]);
+        });
+        if (rc) return rc;
+        // ---- the groups' cells at their places: cell (q, p) is cell (q, j) of the group that holds shard p as its j-th
+        size_t run = at;
+        for (size_t q = 0; q < mq; ++q)
+            for (size_t p = 0; p < S; ++p) {
+                const site_reads_out &rd = rds[where[p].first];
+                const size_t Sg = s->groups[where[p].first]->idx.size(), c = q * Sg + where[p].second;
+                const size_t lo = (size_t)rd.first[c], cnt = (size_t)(rd.first[c + 1] - rd.first[c]);
+                if (!direct && rd.stored && cnt && run + cnt <= cap_reads) {
+                    memcpy(reads + run * (size_t)read_stride, rd.bytes_v.data() + lo * (size_t)read_stride, cnt * (size_t)read_stride);
+                    memcpy(read_len + run, rd.len_v.data() + lo, cnt * 4);
+                    if (read_row) memcpy(read_row + run, rd.row_v.data() + lo, cnt * 8);
+                }
+                run += cnt;
+                first[(q0 + q) * S + p + 1] = run;
+            }
+        at = run;
+        for (const site_group_out &o : outs)
+            for (int i = 0; i < 9; ++i) work9[i] += o.work[i];
+    }
+    *total = at;
+    memcpy(site_reads_last_work, work9, sizeof work9);
+    return RSBWT_OK;
+}
+
 int read_file(const char *path, std::string *out) {
     FILE *f = fopen(path, "rb");
     if (!f) return fail(RSBWT_EIO, "cannot open %s", path);
@@ -4218,6 +4413,13 @@ struct register_meta_hooks {
         rsb::meta_engine_hooks.meta_bytes = rsbwt_set_meta_bytes;
     }
 } register_meta_hooks_now;
+// what service_slice.cpp reaches the site reads calls through (service.h)
+struct register_site_hooks {
+    register_site_hooks() {
+        rsb::site_engine_hooks.reads = rsbwt_set_site_reads;
+        rsb::site_engine_hooks.counts = rsbwt_set_site_read_counts;
+    }
+} register_site_hooks_now;
 }  // namespace
 
 extern "C" {
@@ -4434,6 +4636,47 @@ void rsbwt_set_site_last_work(uint64_t *work10) {
 
 void rsbwt_set_site_last_times(double *ms6) {
     if (ms6) memcpy(ms6, site_last_ms, sizeof site_last_ms);
+}
+
+int rsbwt_set_site_reads(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, const char *alt, const uint8_t *isalt,
+                         int32_t k, int32_t skip, uint64_t M, uint64_t *first, char *reads, uint32_t read_stride, uint32_t *read_len, uint64_t *read_row,
+                         size_t cap_reads, size_t *nreads) {
+    return guarded("rsbwt_set_site_reads", [&]() -> int {
+        if (!nreads || (!first && Q)) return fail(RSBWT_EINVAL, "null argument");
+        *nreads = 0;
+        if (read_stride == 0) return fail(RSBWT_EINVAL, "read_stride must be positive");
+        size_t total = 0;
+        int rc = set_site_reads_body(s, text, off, Q, pos, alt, isalt, k, skip, M, first, true, reads, read_stride, read_len, read_row, cap_reads, &total);
+        if (rc == RSBWT_OK) {
+            *nreads = total;
+            if (total > cap_reads) rc = fail(RSBWT_ERANGE, "%zu reads, room for %zu", total, cap_reads);
+            else if (total != 0 && (!reads || !read_len)) rc = fail(RSBWT_EINVAL, "null argument");
+        }
+        if (rc != RSBWT_OK)
+            for (uint64_t &w : site_reads_last_work) w = 0;
+        return rc;
+    });
+}
+
+int rsbwt_set_site_read_counts(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const uint64_t *pos, const char *alt,
+                               const uint8_t *isalt, int32_t k, int32_t skip, uint64_t M, uint64_t *counts) {
+    return guarded("rsbwt_set_site_read_counts", [&]() -> int {
+        if (!counts && Q) return fail(RSBWT_EINVAL, "null argument");
+        const size_t cells = s ? Q * s->shards.size() : 0;
+        std::vector<uint64_t> first(cells + 1, 0);
+        size_t total = 0;
+        const int rc = set_site_reads_body(s, text, off, Q, pos, alt, isalt, k, skip, M, first.data(), false, nullptr, 256, nullptr, nullptr, 0, &total);
+        if (rc != RSBWT_OK) {
+            for (uint64_t &w : site_reads_last_work) w = 0;
+            return rc;
+        }
+        for (size_t c = 0; c < cells; ++c) counts[c] = first[c + 1] - first[c];
+        return RSBWT_OK;
+    });
+}
+
+void rsbwt_set_site_reads_last_work(uint64_t *work9) {
+    if (work9) memcpy(work9, site_reads_last_work, sizeof site_reads_last_work);
 }
 
 int rsbwt_rccl_available(void) { return rccl().ok ? 1 : 0; }

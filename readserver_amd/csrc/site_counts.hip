@@ -6,6 +6,7 @@
 //   STAGE 2  one lane per row the span filter kept (gt_site_row: the filter's record with the row's ordinal):
 //     1. the head bit of its ordinal (one dword load).  A row on a copy that is no head is done: every copy of a string lies
 //        in the same leg intervals at the same offsets, so the head copy is among the kept rows whenever any copy is.
+//        (rsbwt_set_site_reads, site_reads.hip, has no sample table and skips this step: every kept row goes on.)
 //     2. (request << 40 | ordinal) goes into an open-addressing set, one region per shard (sample_counts.hip's regions and
 //        its discipline: EVERY access to a slot's key is the agent-scope 64-bit compare-and-swap itself, never a plain load
 //        that one XCD's L2 could serve stale).  Old value empty or equal: this is the entry's slot; another key: next slot.
@@ -79,6 +80,8 @@ site_region_rows_kernel(const gt_site_row *__restrict__ rows, const unsigned lon
     }
 }
 
+// HEADS: the counts call's rule, a row on a head copy of a shard with a sample table; else (rsbwt_set_site_reads) every row
+template <bool HEADS>
 __global__ void __launch_bounds__(256)
 site_rows_kernel(const gt_batch bt, const gt_leg *__restrict__ legs, const gt_site_row *__restrict__ rows, const unsigned long long *__restrict__ nrows,
                  uint64_t cap, const meta_view *__restrict__ meta, uint32_t S, const site_set set, unsigned long long *__restrict__ work) {
@@ -88,7 +91,9 @@ site_rows_kernel(const gt_batch bt, const gt_leg *__restrict__ legs, const gt_si
     if (t < n) {
         const gt_site_row r = rows[t];
         const uint64_t o = r.ordinal;
-        if (r.shard < S) {
+        if (!HEADS) {
+            head = r.shard < S && o <= ORDINAL_MASK;
+        } else if (r.shard < S) {
             const meta_view mv = meta[r.shard];
             head = mv.off && mv.heads && o < mv.num_strings && o <= ORDINAL_MASK && ((mv.heads[o >> 5] >> (o & 31u)) & 1u);
 #ifdef RSB_SITE_MUTANT_NO_HEAD_TEST
@@ -344,9 +349,10 @@ hipError_t launch_site_legs(const void *d_legs, size_t cells, unsigned long long
 }
 
 hipError_t launch_site_rows(const gt_batch &bt, const void *d_legs, const void *d_rows, const unsigned long long *d_nrows, uint64_t cap,
-                            const meta_view *d_meta, uint32_t S, bool tight, void *d_rows_of, const site_set &set, unsigned long long *d_work,
-                            hipStream_t stream) {
+                            const meta_view *d_meta, bool heads_only, uint32_t S, bool tight, void *d_rows_of, const site_set &set,
+                            unsigned long long *d_work, hipStream_t stream) {
     if (cap == 0) return hipSuccess;
+    if (heads_only && !d_meta) return hipErrorInvalidValue;  // (the head test needs the sample table: never a quiet "every row")
     hipError_t e = hipMemsetAsync(d_rows_of, 0, (size_t)S * 8, stream);
     if (e == hipSuccess) e = hipMemsetAsync(set.keys, 0xFF, set.nslots * 8, stream);
 #ifdef RSB_SITE_MUTANT_NEED_BY_MAX
@@ -360,8 +366,12 @@ hipError_t launch_site_rows(const gt_batch &bt, const void *d_legs, const void *
     if ((e = hipGetLastError()) != hipSuccess) return e;
     // (cap 0: the regions alone, from the counts just made)
     if ((e = launch_sample_regions(nullptr, nullptr, 0, 0, S, tight, d_rows_of, set.region, stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(site_rows_kernel, grid_of(cap), dim3(256), 0, stream, bt, (const gt_leg *)d_legs, (const gt_site_row *)d_rows, d_nrows, cap, d_meta,
-                       S, set, d_work);
+    if (heads_only)
+        hipLaunchKernelGGL(site_rows_kernel<true>, grid_of(cap), dim3(256), 0, stream, bt, (const gt_leg *)d_legs, (const gt_site_row *)d_rows, d_nrows, cap,
+                           d_meta, S, set, d_work);
+    else
+        hipLaunchKernelGGL(site_rows_kernel<false>, grid_of(cap), dim3(256), 0, stream, bt, (const gt_leg *)d_legs, (const gt_site_row *)d_rows, d_nrows, cap,
+                           d_meta, S, set, d_work);
     return hipGetLastError();
 }
 

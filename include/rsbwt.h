@@ -1073,6 +1073,73 @@ int rsbwt_set_sample_counts_dev(rsbwt_set_t *s, const void *d_text, const void *
 int rsbwt_sample_keys(const uint8_t *codes, size_t C, uint32_t size_of_sample, uint64_t *keys);
 void rsbwt_set_sample_last_work(uint64_t *work6);
 uint64_t rsbwt_set_meta_head_bytes(const rsbwt_set_t *s);
+/* Sample walks: "which way do THIS sample set's reads go?" -- the walk above with the support of a symbol counted over the
+ * reads of the samples a mask names, so that a walk follows one individual, family or population through the forks that
+ * every heterozygous site of anyone else puts into the all-sample graph.  Everything is composed of two definitions above.
+ *   From rsbwt_set_walk, unchanged: the seeds, ctx, the candidates x_c, rc(x), "invalid", flags bits 0 and 1, m =
+ *     max(min_count, 1), max_steps, and the outputs ext / steps / stop / support / last.
+ *   From rsbwt_set_sample_counts, unchanged: codes, C, size_of_sample, has_other_meta_data and max_locate_steps (max_steps
+ *     there: the limit of a row's walk to its read's start, 0 = 2^20), with the same RSBWT_EINVAL cases, "no sample table"
+ *     included.
+ *   mask      u8[C], one byte per code of the ascending dictionary; non-zero = the column counts.  The unknown-code column C
+ *             never counts.  An all-zero mask is legal: every valid seed stops with RSBWT_WALK_DEAD_END at 0 steps.
+ *   SC(x)     the row rsbwt_set_sample_counts gives for the one query x with the call's max_rows: strings[], copies[] and
+ *             matches, summed over distinct carrier strings per shard and over the shards as that call defines it.
+ *   msup      the MASKED SUPPORT of symbol c at string s: t(s, c) = the sum over the columns col with mask[col] != 0 of
+ *             SC(x_c).strings[col]; with RSBWT_WALK_BOTH_STRANDS the same sum for rc(x_c) is added (a read holding both
+ *             counts in each; a palindromic candidate counts twice, as the plain walk counts it).  With the flag
+ *             RSBWT_WALK_SAMPLE_COPIES (bit 2) SC(.).copies[col] is summed instead.  msup(s, c) = max(t(s, c), 0): copies can
+ *             be negative, and it is the total over the columns and both strands that is held at 0.
+ *   WIDE      max_rows is 1 .. 2^20 for these calls (0 and more: RSBWT_EINVAL); it bounds the scratch of a step at seeds x 8 x
+ *             max_rows rows.  If SC(.).matches of ANY of the (4, or 8 with both strands) candidate-strand queries of an
+ *             evaluation exceeds max_rows the evaluation is WIDE: its four supports are reported as 0, and a walk stops
+ *             there with RSBWT_WALK_WIDE and last = zeros.  A repeat is not walked through on a partial count.
+ *   rsbwt_set_extension_samples  the one-step primitive, on any set: msup u64[Q][4]; wide u8[Q] (1 = wide); matches
+ *             u64[Q][4], may be NULL: the unmasked rows of each candidate, both strands added (filled for a wide evaluation
+ *             too).  An invalid seed: zeros everywhere.
+ *   rsbwt_set_walk_samples       rsbwt_set_walk's loop with msup in place of sup and one more stop, looked at first:
+ *                           1. max_steps symbols appended: stop with RSBWT_WALK_LIMIT
+ *                           2. evaluate;  wide: stop with RSBWT_WALK_WIDE
+ *                           3. live = {c : msup(s, c) >= m}; empty: RSBWT_WALK_DEAD_END; two or more: RSBWT_WALK_BRANCH
+ *                           4. else append the one live symbol and note its masked support
+ *             last: zeros for LIMIT, INVALID and WIDE.  On a set on one device the host enqueues the whole walk -- per step a
+ *             fixed sequence of launches, max_steps times, each of which leaves at once when no seed still walks -- and
+ *             waits once; nothing but the outputs and the counters leaves the device (csrc/sample_walk.hip).  The seeds of a
+ *             call are walked in slices that keep a step's rows under 256 MiB of HBM (one seed at the least) and under 2,048
+ *             seeds.  Over several device groups every group evaluates its shards with rsbwt_set_extension_samples' launches,
+ *             the host adds, decides and goes again: the same outputs, one round trip per step.
+ *   rsbwt_set_walk_samples_dev   a set on ONE device (several: RSBWT_EINVAL): d_text, d_off, N and the outputs as
+ *             rsbwt_set_walk_dev takes them; d_keys u64[C] as rsbwt_sample_keys spells them and d_mask u8[C] in HBM, which the
+ *             call cannot check.  Everything is enqueued on `stream`, nothing is synchronised, every byte of every output is
+ *             written.  d_status8 u64[8] = {rows located, rows on a head ordinal, carriers, records read, appended symbols, LF
+ *             steps of the rows' walks, rows not located, wide evaluations}; status[6] > 0: the answers are not complete (the
+ *             host forms' RSBWT_EINVAL).  Q = 0 zeroes d_status8 and touches nothing else.
+ * A row that is not located within max_locate_steps fails the host forms with RSBWT_EINVAL.  A shard without terminators, or
+ * a set one of whose shards has no table entry for a read, is answered as rsbwt_set_sample_counts answers it: such reads
+ * carry nothing.  Q = 0, the range errors (ctx, max_steps, unknown flag bits, Q x max_steps >= 2^31) and "no device" follow
+ * rsbwt_set_walk; more than 1,024 shards on one device are RSBWT_EINVAL.  All arithmetic is in integers: the answers are
+ * bit-identical from run to run.
+ * rsbwt_set_walk_samples_last_work: the calling thread's last host-form call: {seeds, appended symbols, candidate searches,
+ * their LF steps, rows located, rows on a head ordinal, distinct carriers, records read, LF steps of the rows' walks, wide
+ * evaluations}.  rsbwt_set_walk_samples_last_times: while the environment holds RSBWT_SAMPLE_WALK_TIMES=1, the device time in
+ * ms of that thread's last rsbwt_set_walk_samples on a one-device set by kind of launch, from events round every launch: {init,
+ * search, plan, rows, locate, tally, decide}; zeros otherwise.  The events cost time of their own: a measurement aid. */
+#define RSBWT_WALK_SAMPLE_COPIES 4u
+#define RSBWT_WALK_WIDE 8
+int rsbwt_set_extension_samples(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint32_t flags,
+                                const uint8_t *codes, size_t C, uint32_t size_of_sample, int has_other_meta_data, const uint8_t *mask,
+                                uint64_t max_rows, uint32_t max_locate_steps, uint64_t *msup, uint8_t *wide, uint64_t *matches);
+int rsbwt_set_walk_samples(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint64_t min_count,
+                           uint32_t max_steps, uint32_t flags, const uint8_t *codes, size_t C, uint32_t size_of_sample,
+                           int has_other_meta_data, const uint8_t *mask, uint64_t max_rows, uint32_t max_locate_steps, char *ext,
+                           uint32_t *steps, uint8_t *stop, uint32_t *support, uint64_t *last);
+int rsbwt_set_walk_samples_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, size_t N, uint32_t ctx,
+                               uint64_t min_count, uint32_t max_steps, uint32_t flags, const void *d_keys, size_t C,
+                               uint32_t size_of_sample, int has_other_meta_data, const void *d_mask, uint64_t max_rows,
+                               uint32_t max_locate_steps, void *d_ext, void *d_steps, void *d_stop, void *d_support, void *d_last,
+                               void *d_status8, void *stream);
+void rsbwt_set_walk_samples_last_work(uint64_t *work10);
+void rsbwt_set_walk_samples_last_times(double *ms7);
 /* Site sample counts: which samples have reads supporting this allele, and how many -- the sum over the reads SiteMatch +
  * All returns one by one (the reference's /gt), made on the device.  Requests are exactly rsbwt_set_gt_aligned_reads' (w =
  * text[off[q] .. off[q+1]), pos, alt, isalt after GtTask::run's fix-up; k, skip, M); the dictionary and the record rules are

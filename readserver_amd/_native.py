@@ -247,6 +247,14 @@ SIGNATURES = {
                                               C.c_uint32, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rsbwt_sample_keys": (C.c_int, [_vp, C.c_size_t, C.c_uint32, _vp]),
     "rsbwt_set_sample_last_work": (None, [_u64p]),
+    "rsbwt_set_extension_samples": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, C.c_uint32, _vp, C.c_size_t, C.c_uint32, C.c_int, _vp,
+                                              C.c_uint64, C.c_uint32, _vp, _vp, _vp]),
+    "rsbwt_set_walk_samples": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_size_t, C.c_uint32,
+                                         C.c_int, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "rsbwt_set_walk_samples_dev": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _vp,
+                                             C.c_size_t, C.c_uint32, C.c_int, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsbwt_set_walk_samples_last_work": (None, [_u64p]),
+    "rsbwt_set_walk_samples_last_times": (None, [C.POINTER(C.c_double)]),
     "rsbwt_set_meta_head_bytes": (C.c_uint64, [_vp]),
     "rsbwt_set_site_sample_counts": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_uint64, _vp, C.c_size_t, C.c_uint32,
                                                C.c_int, _vp, _vp, _vp, _vp]),

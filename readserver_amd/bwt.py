@@ -26,6 +26,7 @@ WALK_DEAD_END, WALK_BRANCH, WALK_LIMIT, WALK_INVALID = 1, 2, 3, 4
 WALK_JOIN = 5  # rsbwt_set_unitigs alone: another path enters the node the side would enter
 # rsbwt_set_paths alone: a path reached its seed's target / the seed's evaluations ran out; and the seed states
 WALK_TARGET, WALK_BUDGET = 6, 7
+WALK_WIDE = 8  # rsbwt_set_walk_samples alone: a candidate of the evaluation has more rows than max_rows
 PATHS_COMPLETE, PATHS_MORE, PATHS_BUDGET, PATHS_INVALID = 1, 2, 3, 4
 
 
@@ -1112,6 +1113,79 @@ class ShardSet:
         w = np.zeros(6, np.uint64)
         lib().rsbwt_set_sample_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
         return dict(zip(("rows", "head_rows", "carriers", "records", "unknown", "lf_steps"), (int(x) for x in w)))
+
+    # -- sample walks (csrc/sample_walk.hip): rsbwt_set_extension_samples / rsbwt_set_walk_samples
+    @staticmethod
+    def _sample_mask(codes, size_of_sample, mask_codes):
+        """the dictionary in ascending order and the mask over it: (flat codes, n, mask u8[n])"""
+        cs = [bytes(c) for c in codes]
+        if any(len(c) != size_of_sample for c in cs):
+            raise ValueError("a code is not size_of_sample bytes long")
+        wanted = {bytes(c) for c in mask_codes}
+        if wanted - set(cs):
+            raise ValueError("a mask code is not in the dictionary")
+        order = sorted(range(len(cs)), key=lambda i: cs[i])
+        flat = np.frombuffer(b"".join(cs[i] for i in order) + b"\0", np.uint8).copy()
+        mask = np.array([1 if cs[i] in wanted else 0 for i in order] + [0], np.uint8)
+        return flat, len(cs), mask
+
+    def extension_samples(self, queries, ctx, codes, size_of_sample, mask_codes=(), has_other_meta_data=True, max_rows=4096, max_locate_steps=0,
+                          left=False, both_strands=False, copies=False):
+        """One evaluation of a sample walk (rsbwt_set_extension_samples).  codes: the sample dictionary in any order, as
+        sample_counts takes it; mask_codes: the codes of it whose reads count.  Returns a dict of msup (Q, 4) uint64 -- per
+        symbol, the distinct reads holding the query's context + symbol that list a masked sample (copies=True: the sum of
+        their c fields, at least 0), the reverse complement's added with both_strands --, wide (Q) uint8 -- 1 where a
+        candidate has more than max_rows rows: its supports are 0 -- and matches (Q, 4) uint64, the candidates' rows."""
+        flat, n, mask = self._sample_mask(codes, size_of_sample, mask_codes)
+        text, off = self._var_text(queries)
+        Q = len(queries)
+        msup, matches = np.zeros((max(Q, 1), 4), np.uint64), np.zeros((max(Q, 1), 4), np.uint64)
+        wide = np.zeros(max(Q, 1), np.uint8)
+        check(lib().rsbwt_set_extension_samples(self._s, _ptr(text), _ptr(off), Q, ctx, _walk_flags(left, both_strands) | (4 if copies else 0),
+                                                _ptr(flat), n, size_of_sample, 1 if has_other_meta_data else 0, _ptr(mask), max_rows,
+                                                max_locate_steps, _ptr(msup), _ptr(wide), _ptr(matches)))
+        return dict(msup=msup[:Q], wide=wide[:Q], matches=matches[:Q])
+
+    def walk_samples(self, seeds, ctx, codes, size_of_sample, mask_codes=(), has_other_meta_data=True, min_count=1, max_steps=256, max_rows=4096,
+                     max_locate_steps=0, left=False, both_strands=False, copies=False, supports=False):
+        """Walks every seed through the reads of the samples mask_codes names (rsbwt_set_walk_samples): walk() with the
+        support of a symbol counted over the distinct reads that hold the candidate and list a masked sample (copies=True:
+        the sum of their c fields).  Returns what walk() returns; stop may also be WALK_WIDE: a candidate of the evaluation
+        had more than max_rows rows (last is zeros then)."""
+        flat, n, mask = self._sample_mask(codes, size_of_sample, mask_codes)
+        text, off = self._var_text(seeds)
+        Q = len(seeds)
+        ext = np.zeros((max(Q, 1), max_steps), np.uint8)
+        steps, stop = np.zeros(max(Q, 1), np.uint32), np.zeros(max(Q, 1), np.uint8)
+        sup = np.zeros((max(Q, 1), max_steps), np.uint32) if supports else None
+        last = np.zeros((max(Q, 1), 4), np.uint64)
+        check(lib().rsbwt_set_walk_samples(self._s, _ptr(text), _ptr(off), Q, ctx, min_count, max_steps,
+                                           _walk_flags(left, both_strands) | (4 if copies else 0), _ptr(flat), n, size_of_sample,
+                                           1 if has_other_meta_data else 0, _ptr(mask), max_rows, max_locate_steps, _ptr(ext), _ptr(steps),
+                                           _ptr(stop), _ptr(sup) if supports else None, _ptr(last)))
+        out = []
+        for q in range(Q):
+            k = int(steps[q])
+            one = (ext[q, :k].tobytes().decode(), int(stop[q]), tuple(int(x) for x in last[q]))
+            out.append(one + (tuple(int(x) for x in sup[q, :k]),) if supports else one)
+        return out
+
+    @staticmethod
+    def walk_samples_last_work():
+        """{seeds, appended, searches, search_steps, rows, head_rows, carriers, records, lf_steps, wide} of this thread's last
+        walk_samples or extension_samples call"""
+        w = np.zeros(10, np.uint64)
+        lib().rsbwt_set_walk_samples_last_work(w.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return dict(zip(("seeds", "appended", "searches", "search_steps", "rows", "head_rows", "carriers", "records", "lf_steps", "wide"),
+                        (int(x) for x in w)))
+
+    @staticmethod
+    def walk_samples_last_times():
+        """{init, search, plan, rows, locate, tally, decide}: the device time in ms of this thread's last walk_samples call on a
+        one-device set by kind of launch, measured only while the environment holds RSBWT_SAMPLE_WALK_TIMES=1 (zeros otherwise)"""
+        t = (C.c_double * 7)()
+        lib().rsbwt_set_walk_samples_last_times(t)
+        return dict(zip(("init", "search", "plan", "rows", "locate", "tally", "decide"), (float(x) for x in t)))
 
     # -- site sample counts (csrc/site_counts.hip): rsbwt_set_site_sample_counts
     def site_sample_counts(self, queries, pos, alt, isalt, k, skip=0, max_interval_size=0, *, codes, size_of_sample, has_other_meta_data=True):

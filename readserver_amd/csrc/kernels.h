@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include <mutex>
+#include <vector>
 
 #include "launch_plan.h"
 #include "line_format.h"
@@ -296,10 +297,11 @@ hipError_t launch_extract_ragged(scratch_cache &scratch, const shard_view *d_sha
 // locate.hip: the LF walk of n (shard, row) entries to the row of their read's full suffix: d_shard_of u32[n] (nullptr:
 // one shard, every entry a row of it), d_rows u64[n] in any order; d_read_row / d_ordinal u64[n], d_offset u32[n], each
 // optional; max_steps 0 = 2^20.  d_work2 (optional, zeroed by the caller): [0] += rows that ended on '$', [1] += LF steps.
-// One launch walks all the shards, a wave one shard at a time.
+// One launch walks all the shards, a wave one shard at a time.  d_n (optional, u64 in HBM): the list ends at min(n, *d_n),
+// for a caller that enqueues the launch before the device has counted its rows (sample_walk.hip); n sizes the grid.
 hipError_t launch_locate(scratch_cache &scratch, const shard_view *d_shards, uint32_t nshards, const void *d_shard_of, const void *d_rows,
                          size_t n, uint32_t max_steps, void *d_read_row, void *d_ordinal, void *d_offset, unsigned long long *d_work2,
-                         int num_cus, hipStream_t stream);
+                         int num_cus, hipStream_t stream, const void *d_n = nullptr);
 // interval_rows.hip: {lower, upper} pairs [S][Q] -> the rows of the batch, with a limit on the rows of one query.
 //   launch_interval_totals: d_matches u64[Q] (every query's rows over the S shards), d_first u64[Q + 1] (exclusive scan of the
 //     totals of the queries at or under max_rows; 0 = no limit), *d_over (u64) = queries over it; d_kept: u64[Q + 1] scratch
@@ -441,6 +443,44 @@ struct paths_batch {
 size_t paths_frame_bytes(size_t Q, uint32_t max_steps, uint32_t max_evals);
 hipError_t launch_paths(const shard_view *d_shards, uint32_t nshards, const paths_batch &pb, void *d_frames, void *d_ext, void *d_steps, void *d_stop,
                         void *d_min_support, void *d_npaths, void *d_state, unsigned long long *d_work, hipStream_t stream);
+// sample_walk.hip: walks through one sample set's reads (include/rsbwt.h: the definition; sample_walk_rule.h: the host's
+// share).  One slice of seeds on one device: sample_walk_bytes() of scratch, then sample_walk_enqueue() puts the whole
+// walk on the stream -- init, then max_steps times {search, plan, rows, locate, tally, decide}, every launch leaving at
+// once when no seed of the slice still walks -- and waits for nothing.
+struct sample_walk_args {
+    const shard_view *views;  // [S]
+    const meta_view *meta;    // [S]
+    uint32_t S;
+    int num_cus;
+    walk_batch bt;  // the slice's seeds; flags may hold RSBWT_WALK_SAMPLE_COPIES
+    const uint64_t *keys;      // [C] ascending
+    const uint32_t *mask_bits;  // [ceil(C / 32)]
+    uint32_t C, size_of_sample, has_other;
+    uint64_t max_rows;           // 1 .. 2^20
+    uint32_t max_locate_steps;   // 0 = 2^20
+    // outputs of a walk (evaluate_only == 0): as launch_walk's; every byte written
+    void *ext, *steps, *stop, *support, *last;
+    // outputs of one evaluation (evaluate_only != 0): raw i64[Q][8] the masked sums per (base, strand), matches u64[Q][8],
+    // wide u8[Q] (this device's shards alone)
+    uint32_t evaluate_only;
+    void *raw, *matches8, *wide;
+    unsigned long long *work;  // SAMPLE_WALK_WORK counters, zeroed by the caller, added to
+    // measurement (optional, host side): an event is recorded on the stream when the enqueue starts and after every launch --
+    // init, then per step search, plan, rows, locate, tally, decide -- and appended here; the caller reads and destroys them
+    std::vector<hipEvent_t> *marks = nullptr;
+};
+constexpr int SAMPLE_WALK_KINDS = 7;  // init, search, plan, rows, locate, tally, decide
+enum {
+    SW_WORK_APPENDED = 0, SW_WORK_SEARCHES, SW_WORK_SEARCH_STEPS, SW_WORK_ROWS, SW_WORK_HEADS, SW_WORK_CARRIERS, SW_WORK_RECORDS,
+    SW_WORK_LOST, SW_WORK_WIDE, SW_WORK_LOCATED, SW_WORK_LOCATE_STEPS, SAMPLE_WALK_WORK
+};
+size_t sample_walk_bytes(size_t Q, uint32_t S, uint32_t max_steps, uint64_t max_rows);
+hipError_t sample_walk_enqueue(scratch_cache &scratch, const sample_walk_args &a, void *d_scratch, hipStream_t stream);
+// d_status8 = {rows located, rows on a head ordinal, carriers, records read, appended symbols, LF steps of the rows' walks,
+// rows not located, wide evaluations}
+hipError_t launch_sample_walk_status(const unsigned long long *d_work, void *d_status8, hipStream_t stream);
+// d_mask u8[C] -> d_bits u32[ceil(C / 32)], bit col of word col / 32 (sample_walk_rule.h, sample_walk_mask_bits)
+hipError_t launch_sample_walk_mask(const void *d_mask, size_t C, void *d_bits, hipStream_t stream);
 // ksw_align.hip: ksw_align of the reference's ksw.c and align_gt_read over it (ksw_pass.h), one lane per item.  A block is
 // one wave of 64 items and belongs to the LENGTH CLASS of its longest pass: at most 32, 64, 104, 160 or KSW_LDS_ROWS rows
 // -- the column lives in LDS, the launch's LDS sized for the class -- or more: the column lives in d_scratch

@@ -78,13 +78,18 @@ __device__ __forceinline__ void locate_store(uint64_t *__restrict__ read_row, ui
 
 // shard_of == nullptr: every entry is a row of shard 0 (nshards == 1).  pools: one counter per shard, POOL_STRIDE u64
 // apart, zeroed by the launcher.  row_chunk: entries per draw, a multiple of 64.  work (optional): [0] += rows that
-// ended on '$', [1] += LF steps.
+// ended on '$', [1] += LF steps.  n_dev (optional): the list ends at min(n, *n_dev) -- a count only the device knows.
 __global__ void __launch_bounds__(64 * LC_WAVES, RSB_WALK_MIN_WGS)
 locate_wave_kernel(const shard_view *__restrict__ shards, uint32_t nshards, const uint32_t *__restrict__ shard_of,
                    const uint64_t *__restrict__ rows, uint64_t n, uint32_t max_steps, uint64_t *__restrict__ read_row,
                    uint64_t *__restrict__ ordinal, uint32_t *__restrict__ offset, unsigned long long *__restrict__ pools,
-                   unsigned long long *__restrict__ work, uint32_t row_chunk) {
+                   unsigned long long *__restrict__ work, uint32_t row_chunk, const uint64_t *__restrict__ n_dev) {
     __shared__ uint4 s_stage[LC_WAVES][64 * SLOT_U4];
+    if (n_dev != nullptr) {  // (the same for every lane of the launch)
+        const uint64_t nd = *n_dev;
+        n = nd < n ? nd : n;
+        if (n == 0ull) return;
+    }
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint4 *stage = s_stage[wave];
     const uint32_t stage_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_void_ptr)stage);
@@ -279,7 +284,7 @@ locate_wave_kernel(const shard_view *__restrict__ shards, uint32_t nshards, cons
 
 hipError_t launch_locate(scratch_cache &scratch, const shard_view *d_shards, uint32_t nshards, const void *d_shard_of, const void *d_rows,
                          size_t n, uint32_t max_steps, void *d_read_row, void *d_ordinal, void *d_offset, unsigned long long *d_work2,
-                         int num_cus, hipStream_t stream) {
+                         int num_cus, hipStream_t stream, const void *d_n) {
     if (n == 0 || nshards == 0) return hipSuccess;
     if (!d_shard_of && nshards != 1) return hipErrorInvalidValue;
     pool_lease mem(scratch, stream, 0, 1, nshards);
@@ -291,7 +296,7 @@ hipError_t launch_locate(scratch_cache &scratch, const shard_view *d_shards, uin
     const uint32_t row_chunk = plan_draw(256, 64, waves_per_shard(g, LC_WAVES, nshards), 2, n);
     hipLaunchKernelGGL(locate_wave_kernel, dim3((unsigned)g), dim3(64 * LC_WAVES), 0, stream, d_shards, nshards, (const uint32_t *)d_shard_of,
                        (const uint64_t *)d_rows, (uint64_t)n, max_steps ? max_steps : LC_DEFAULT_STEPS, (uint64_t *)d_read_row,
-                       (uint64_t *)d_ordinal, (uint32_t *)d_offset, mem.pool(0, nshards), d_work2, row_chunk);
+                       (uint64_t *)d_ordinal, (uint32_t *)d_offset, mem.pool(0, nshards), d_work2, row_chunk, (const uint64_t *)d_n);
     return hipGetLastError();
 }
 

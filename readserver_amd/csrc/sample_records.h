@@ -92,6 +92,29 @@ __device__ __forceinline__ uint32_t tally_values(const tally_cells &a, const tal
     return unknown;
 }
 
+// The same division of labour for a caller that needs a SUM per carrier and no matrix (sample_walk.hip: hit or miss against
+// a mask of columns): value(p) is the number a record at p adds.  Every lane of the wave is here; a lane that holds a carrier
+// brings the nrec whole records of R bytes at val.  A short value's sum comes back in its own lane; a long value's is summed
+// over the wave and comes back in the holder's lane.
+template <class F>
+__device__ __forceinline__ long long record_sums(uint32_t R, uint32_t lane, uint64_t nrec, const uint8_t *val, F &&value) {
+    long long mine = 0;
+    if (nrec != 0ull && nrec <= TALLY_LANE_RECORDS)
+        for (uint32_t i = 0; i < (uint32_t)nrec; ++i) mine += value(val + (size_t)i * R);
+    uint64_t longs = __builtin_amdgcn_ballot_w64(nrec > TALLY_LANE_RECORDS);
+    while (longs) {
+        const int j = __builtin_ctzll(longs);
+        longs &= longs - 1ull;
+        const uint64_t wn = __shfl(nrec, j, 64);
+        const uint8_t *wv = reinterpret_cast<const uint8_t *>(__shfl((uint64_t)(uintptr_t)val, j, 64));
+        long long part = 0;
+        for (uint64_t i = lane; i < wn; i += 64u) part += value(wv + i * R);
+        for (int s = 32; s > 0; s >>= 1) part += __shfl_xor(part, s, 64);
+        if (lane == (uint32_t)j) mine = part;
+    }
+    return mine;
+}
+
 // counter += the sum over the wave of a small per-lane number: one atomic
 __device__ __forceinline__ void wave_count(unsigned long long *counter, uint32_t mine, uint32_t lane) {
     uint32_t v = mine;

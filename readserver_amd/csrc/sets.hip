@@ -33,6 +33,7 @@
 #include "meta_file.h"
 #include "paths_rule.h"
 #include "sample_codes.h"
+#include "sample_walk_rule.h"
 #include "service.h"
 #include "unitig_rule.h"
 
@@ -4405,6 +4406,285 @@ static void meta_free(rsbwt_set_t *s) {
     s->meta_head_bytes = 0;
 }
 
+// ---- sample walks (sample_walk.hip): seeds extended through one sample set's reads ----
+namespace {
+// the calling thread's last host-form call: seeds, appended symbols, candidate searches, their LF steps, rows located, rows
+// on a head ordinal, distinct carriers, records read, LF steps of the rows' walks, wide evaluations
+thread_local uint64_t sample_walk_last[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+// ... and, while RSBWT_SAMPLE_WALK_TIMES=1, the device time of its launches in ms by kind, from events round every launch on
+// the call's stream, summed over steps, slices and device groups: {init, search, plan, rows, locate, tally, decide}
+thread_local double sample_walk_ms[SAMPLE_WALK_KINDS] = {0, 0, 0, 0, 0, 0, 0};
+
+// (read at every call: a probe turns it on and off inside one process)
+bool sample_walk_times_on() {
+    const char *e = getenv("RSBWT_SAMPLE_WALK_TIMES");
+    return e && e[0] == '1' && e[1] == 0;
+}
+
+// the marks of one enqueue -> ms[kind] += ...; the events are destroyed.  After the stream has been waited for.
+void sample_walk_read_marks(std::vector<hipEvent_t> &marks, double *ms) {
+    for (size_t i = 1; i < marks.size(); ++i) {
+        float dt = 0;
+        if (hipEventElapsedTime(&dt, marks[i - 1], marks[i]) == hipSuccess) ms[i == 1 ? 0 : 1 + (i - 2) % 6] += dt;
+        else (void)hipGetLastError();
+    }
+    for (hipEvent_t ev : marks) (void)hipEventDestroy(ev);
+    marks.clear();
+}
+
+struct sample_walk_call {
+    sample_dict d;
+    std::vector<uint32_t> bits;  // the mask, a bit per column
+    uint64_t max_rows = 0;
+    uint32_t max_locate_steps = 0;
+};
+
+int sample_walk_shape_ok(const rsbwt_set_t *s, uint64_t max_rows) {
+    if (!sample_walk_rows_ok(max_rows)) return fail(RSBWT_EINVAL, "max_rows = %llu: 1 to 2^20 for a sample walk", (unsigned long long)max_rows);
+    for (const dev_group *g : s->groups)
+        if (g->idx.size() > SAMPLE_WALK_MAX_SHARDS) return fail(RSBWT_EINVAL, "%zu shards on one device: a sample walk takes at most 1,024", g->idx.size());
+    return RSBWT_OK;
+}
+
+int sample_walk_prepare(rsbwt_set_t *s, const uint8_t *codes, size_t C, uint32_t size_of_sample, int has_other, const uint8_t *mask, uint64_t max_rows,
+                        uint32_t max_locate_steps, sample_walk_call *c) {
+    int rc = sample_set_ok(s);
+    if (rc) return rc;
+    if ((rc = sample_dict_make(codes, C, size_of_sample, has_other, &c->d)) != RSBWT_OK) return rc;
+    if (!mask) return fail(RSBWT_EINVAL, "null argument: mask");
+    if ((rc = sample_walk_shape_ok(s, max_rows)) != RSBWT_OK) return rc;
+    c->bits.resize(sample_walk_mask_words(C));
+    sample_walk_mask_bits(mask, C, c->bits.data());
+    c->max_rows = max_rows;
+    c->max_locate_steps = max_locate_steps;
+    return RSBWT_OK;
+}
+
+void sample_walk_add_work(uint64_t *work10, const unsigned long long *dev) {
+    auto w = [&](int which) { return (uint64_t)dev[(size_t)which * TALLY_WORK_STRIDE]; };
+    work10[1] += w(SW_WORK_APPENDED);
+    work10[2] += w(SW_WORK_SEARCHES);
+    work10[3] += w(SW_WORK_SEARCH_STEPS);
+    work10[4] += w(SW_WORK_ROWS);
+    work10[5] += w(SW_WORK_HEADS);
+    work10[6] += w(SW_WORK_CARRIERS);
+    work10[7] += w(SW_WORK_RECORDS);
+    work10[8] += w(SW_WORK_LOCATE_STEPS);
+    work10[9] += w(SW_WORK_WIDE);
+}
+
+// What a host-form call runs on one device group on `gc`'s stream: the batch, the dictionary and the mask go up once, then
+// the seeds are walked (or evaluated once: evaluate) slice by slice -- sample_walk_slice_seeds -- each slice's launches
+// enqueued blind and its answers copied back; the stream is waited for once per slice, never between steps.
+// walk: ext, steps, stop, support (optional), last (optional).  evaluate: raw i64[Q][8], m8 u64[Q][8], wide u8[Q].
+int sample_walk_group(dev_group *g, group_call &gc, const char *t0, const uint64_t *rel, size_t Q, size_t N, uint32_t ctx, uint64_t m,
+                      uint32_t max_steps, uint32_t flags, const sample_walk_call &c, bool evaluate, char *ext, uint32_t *steps, uint8_t *stop,
+                      uint32_t *support, uint64_t *last, int64_t *raw, uint64_t *m8, uint8_t *wide, uint64_t *work10, double *ms = nullptr) {
+    if (Q == 0) return RSBWT_OK;
+    std::vector<hipEvent_t> marks;
+    struct drop_marks {  // (a call that leaves early: group_call's destructor has the stream waited for before the events go)
+        std::vector<hipEvent_t> &m;
+        ~drop_marks() {
+            for (hipEvent_t ev : m) (void)hipEventDestroy(ev);
+        }
+    } drop{marks};
+    hipStream_t st = gc.st;
+    const uint32_t S = (uint32_t)g->idx.size(), steps_n = evaluate ? 1u : max_steps;
+    const size_t per = std::min(Q, sample_walk_slice_seeds(c.max_rows, SAMPLE_WALK_BUDGET));
+    const size_t cells = per * (size_t)steps_n;
+    const size_t a_text = al256(N + 1), a_off = al256((Q + 1) * 8), a_keys = al256((size_t)c.d.C * 8), a_bits = al256(c.bits.size() * 4),
+                 a_work = al256(SAMPLE_WALK_WORK * TALLY_WORK_STRIDE * 8), a_ext = evaluate ? 0 : al256(cells), a_steps = evaluate ? 0 : al256(per * 4),
+                 a_stop = evaluate ? 0 : al256(per), a_sup = !evaluate && support ? al256(cells * 4) : 0, a_last = !evaluate && last ? al256(per * 32) : 0,
+                 a_raw = evaluate ? al256(per * 64) : 0, a_m8 = evaluate ? al256(per * 64) : 0, a_wide = evaluate ? al256(per) : 0;
+    hipError_t e = g->scratch.take(a_text + a_off + a_keys + a_bits + a_work + a_ext + a_steps + a_stop + a_sup + a_last + a_raw + a_m8 + a_wide +
+                                       sample_walk_bytes(per, S, steps_n, c.max_rows),
+                                   st, &gc.lb);
+    if (e != hipSuccess)
+        return fail(RSBWT_ENOMEM, "%zu seeds x %llu rows do not fit the device's free memory: %s", per, (unsigned long long)c.max_rows, hipGetErrorString(e));
+    uint8_t *d_text = (uint8_t *)gc.lb.p, *d_off = d_text + a_text, *d_keys = d_off + a_off, *d_bits = d_keys + a_keys, *d_work = d_bits + a_bits,
+            *d_ext = d_work + a_work, *d_steps = d_ext + a_ext, *d_stop = d_steps + a_steps, *d_sup = d_stop + a_stop, *d_last = d_sup + a_sup,
+            *d_raw = d_last + a_last, *d_m8 = d_raw + a_raw, *d_wide = d_m8 + a_m8, *d_scratch = d_wide + a_wide;
+    if (N) HIP_OK(hipMemcpyAsync(d_text, t0, N, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_off, rel, (Q + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_keys, c.d.keys.data(), (size_t)c.d.C * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_bits, c.bits.data(), c.bits.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(d_work, 0, a_work, st));
+    std::vector<unsigned long long> hwork(SAMPLE_WALK_WORK * TALLY_WORK_STRIDE);
+    for (size_t q0 = 0; q0 < Q; q0 += per) {
+        const size_t mq = std::min(per, Q - q0);
+        sample_walk_args a;
+        a.views = g->d_views;
+        a.meta = g->d_meta;
+        a.S = S;
+        a.num_cus = g->num_cus;
+        a.bt.text = (const char *)d_text;
+        a.bt.off = (const uint64_t *)d_off + q0;
+        a.bt.Q = mq;
+        a.bt.N = N;
+        a.bt.ctx = ctx;
+        a.bt.max_steps = steps_n;
+        a.bt.min_count = m;
+        a.bt.flags = flags;
+        a.keys = (const uint64_t *)d_keys;
+        a.mask_bits = (const uint32_t *)d_bits;
+        a.C = c.d.C;
+        a.size_of_sample = c.d.size_of_sample;
+        a.has_other = c.d.has_other;
+        a.max_rows = c.max_rows;
+        a.max_locate_steps = c.max_locate_steps;
+        a.ext = d_ext;
+        a.steps = d_steps;
+        a.stop = d_stop;
+        a.support = a_sup ? d_sup : nullptr;
+        a.last = a_last ? d_last : nullptr;
+        a.evaluate_only = evaluate ? 1u : 0u;
+        a.raw = d_raw;
+        a.matches8 = d_m8;
+        a.wide = d_wide;
+        a.work = (unsigned long long *)d_work;
+        a.marks = ms ? &marks : nullptr;
+        if ((e = sample_walk_enqueue(g->scratch, a, d_scratch, st)) != hipSuccess) return fail_hip(e, "sample walk launches");
+        if (evaluate) {
+            HIP_OK(hipMemcpyAsync(raw + q0 * 8, d_raw, mq * 64, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(m8 + q0 * 8, d_m8, mq * 64, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(wide + q0, d_wide, mq, hipMemcpyDeviceToHost, st));
+        } else {
+            HIP_OK(hipMemcpyAsync(ext + q0 * (size_t)max_steps, d_ext, mq * (size_t)max_steps, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(steps + q0, d_steps, mq * 4, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(stop + q0, d_stop, mq, hipMemcpyDeviceToHost, st));
+            if (support) HIP_OK(hipMemcpyAsync(support + q0 * (size_t)max_steps, d_sup, mq * (size_t)max_steps * 4, hipMemcpyDeviceToHost, st));
+            if (last) HIP_OK(hipMemcpyAsync(last + q0 * 4, d_last, mq * 32, hipMemcpyDeviceToHost, st));
+        }
+        HIP_OK(hipMemcpyAsync(hwork.data(), d_work, hwork.size() * 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        if (ms) sample_walk_read_marks(marks, ms);
+        if (hwork[(size_t)SW_WORK_LOST * TALLY_WORK_STRIDE] != 0)
+            return fail(RSBWT_EINVAL, "%llu rows whose walk to their read's start does not end within max_locate_steps (a corrupt index, or a read longer than the limit)",
+                        (unsigned long long)hwork[(size_t)SW_WORK_LOST * TALLY_WORK_STRIDE]);
+    }
+    sample_walk_add_work(work10, hwork.data());
+    return RSBWT_OK;
+}
+
+// One evaluation of every seed over every device group: the groups' masked sums and rows added on the host, WIDE decided
+// over the whole set's rows, the strands added.  msup u64[Q][4], wide u8[Q], matches u64[Q][4] (optional).
+int extension_samples_groups(rsbwt_set_t *s, const char *t0, const uint64_t *rel, size_t Q, size_t N, uint32_t ctx, uint32_t flags,
+                             const sample_walk_call &c, uint64_t *msup, uint8_t *wide, uint64_t *matches, uint64_t *work10) {
+    struct group_out {
+        std::vector<int64_t> raw;
+        std::vector<uint64_t> m8;
+        std::vector<uint8_t> wide;
+        uint64_t work[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    };
+    std::vector<group_out> outs(s->groups.size());
+    int rc = for_each_group(s, [&](size_t gi) -> int {
+        group_out &o = outs[gi];
+        o.raw.assign(Q * 8, 0);
+        o.m8.assign(Q * 8, 0);
+        o.wide.assign(Q, 0);
+        group_call gc(s->groups[gi], true);
+        if (gc.rc) return gc.rc;
+        return sample_walk_group(gc.g, gc, t0, rel, Q, N, ctx, 1ull, 1u, flags, c, true, nullptr, nullptr, nullptr, nullptr, nullptr, o.raw.data(),
+                                 o.m8.data(), o.wide.data(), o.work);
+    });
+    if (rc) return rc;
+    for (const group_out &o : outs)
+        for (int i = 1; i < 10; ++i) work10[i] += o.work[i];
+    for (size_t q = 0; q < Q; ++q) {
+        uint64_t m8[8];
+        int64_t raw[8];
+        for (uint32_t l = 0; l < 8u; ++l) {
+            m8[l] = 0;
+            raw[l] = 0;
+            for (const group_out &o : outs) {
+                m8[l] += o.m8[q * 8 + l];
+                raw[l] += o.raw[q * 8 + l];
+            }
+        }
+        const bool w = sample_walk_wide(m8, c.max_rows);
+        wide[q] = w ? 1u : 0u;
+        for (uint32_t b = 0; b < 4u; ++b) {
+            msup[q * 4 + b] = w ? 0ull : sample_walk_support(raw[2 * b], raw[2 * b + 1]);
+            if (matches) matches[q * 4 + b] = m8[2 * b] + m8[2 * b + 1];
+        }
+    }
+    return RSBWT_OK;
+}
+
+// The sample walk of a set over several device groups: walk_by_steps with extension_samples_groups as its evaluation.
+int walk_samples_by_steps(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint64_t m, uint32_t max_steps,
+                          uint32_t flags, const sample_walk_call &c, char *ext, uint32_t *steps, uint8_t *stop, uint32_t *support, uint64_t *last,
+                          uint64_t *work10) {
+    const bool left = (flags & RSBWT_WALK_LEFT) != 0u;
+    memset(ext, 0, Q * (size_t)max_steps);
+    if (support) memset(support, 0, Q * (size_t)max_steps * 4);
+    std::vector<std::string> cur(Q);
+    std::vector<size_t> live;
+    for (size_t q = 0; q < Q; ++q) {
+        const uint64_t Lq = off[q + 1] - off[q];
+        bool valid = Lq >= ctx;
+        if (valid) {
+            cur[q].assign(left ? text + off[q] : text + off[q + 1] - ctx, ctx);
+            for (char ch : cur[q]) valid = valid && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
+        }
+        steps[q] = 0;
+        stop[q] = valid ? 0 : (uint8_t)RSBWT_WALK_INVALID;
+        if (last)
+            for (int b = 0; b < 4; ++b) last[4 * q + b] = 0;
+        if (valid) live.push_back(q);
+    }
+    std::string t;
+    std::vector<uint64_t> rel, msup;
+    std::vector<uint8_t> wide;
+    while (!live.empty()) {  // (every seed of `live` has fewer than max_steps symbols appended)
+        const size_t nl = live.size();
+        t.clear();
+        rel.resize(nl + 1);
+        for (size_t i = 0; i < nl; ++i) {
+            rel[i] = (uint64_t)i * ctx;
+            t += cur[live[i]];
+        }
+        rel[nl] = (uint64_t)nl * ctx;
+        if (rel[nl] >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu seeds x %u context symbols: under 2^31 in one call", nl, ctx);
+        msup.assign(nl * 4, 0);
+        wide.assign(nl, 0);
+        const int rc = extension_samples_groups(s, t.data(), rel.data(), nl, (size_t)rel[nl], ctx, flags, c, msup.data(), wide.data(), nullptr, work10);
+        if (rc) return rc;
+        std::vector<size_t> next;
+        for (size_t i = 0; i < nl; ++i) {
+            const size_t q = live[i];
+            const uint64_t *sup = msup.data() + i * 4;
+            uint32_t pick = 0;
+            uint32_t why = sample_walk_step(sup, wide[i] != 0, m, &pick);
+            if (why == SAMPLE_WALK_GO) {
+                const size_t at = q * (size_t)max_steps + steps[q];
+                ext[at] = "ACGT"[pick];
+                if (support) support[at] = sup[pick] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)sup[pick];
+                work10[1] += 1;
+                if (left) cur[q] = std::string(1, "ACGT"[pick]) + cur[q].substr(0, ctx - 1);
+                else cur[q] = cur[q].substr(1) + "ACGT"[pick];
+                if (++steps[q] == max_steps) why = SAMPLE_WALK_LIMIT;
+            }
+            if (why == SAMPLE_WALK_GO) {
+                next.push_back(q);
+                continue;
+            }
+            stop[q] = (uint8_t)why;
+            if (last && why != SAMPLE_WALK_LIMIT && why != SAMPLE_WALK_WIDE)
+                for (int b = 0; b < 4; ++b) last[4 * q + b] = sup[b];
+        }
+        live.swap(next);
+    }
+    return RSBWT_OK;
+}
+
+int sample_walk_flags_ok(uint32_t ctx, uint32_t flags, const uint32_t *max_steps, size_t Q) {
+    // (the walk's own checks, with the one flag a sample walk adds)
+    if (flags & ~(uint32_t)(RSBWT_WALK_LEFT | RSBWT_WALK_BOTH_STRANDS | RSBWT_WALK_SAMPLE_COPIES)) return fail(RSBWT_EINVAL, "unknown flag bits 0x%x", flags);
+    return walk_check_args(ctx, flags & ~(uint32_t)RSBWT_WALK_SAMPLE_COPIES, max_steps, Q);
+}
+}  // namespace
+
 namespace {
 // the service code's way in (service.h: service_slice.cpp is also linked into host harnesses without the engine)
 struct register_meta_hooks {
@@ -4677,6 +4957,142 @@ int rsbwt_set_site_read_counts(rsbwt_set_t *s, const char *text, const uint64_t 
 
 void rsbwt_set_site_reads_last_work(uint64_t *work9) {
     if (work9) memcpy(work9, site_reads_last_work, sizeof site_reads_last_work);
+}
+
+int rsbwt_set_extension_samples(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint32_t flags, const uint8_t *codes,
+                                size_t C, uint32_t size_of_sample, int has_other_meta_data, const uint8_t *mask, uint64_t max_rows,
+                                uint32_t max_locate_steps, uint64_t *msup, uint8_t *wide, uint64_t *matches) {
+    return guarded("rsbwt_set_extension_samples", [&]() -> int {
+        for (uint64_t &w : sample_walk_last) w = 0;
+        int rc = walk_set_check(s);
+        if (rc) return rc;
+        if ((rc = sample_walk_flags_ok(ctx, flags, nullptr, Q)) != RSBWT_OK) return rc;
+        sample_walk_call c;
+        if ((rc = sample_walk_prepare(s, codes, C, size_of_sample, has_other_meta_data, mask, max_rows, max_locate_steps, &c)) != RSBWT_OK) return rc;
+        std::vector<uint64_t> rel;
+        size_t N = 0;
+        if ((rc = match_check_batch(text, off, Q, &rel, &N)) != RSBWT_OK) return rc;
+        if (Q == 0) return RSBWT_OK;
+        if (!msup || !wide) return fail(RSBWT_EINVAL, "null argument");
+        uint64_t work10[10] = {Q, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        rc = extension_samples_groups(s, N ? text + off[0] : nullptr, rel.data(), Q, N, ctx, flags, c, msup, wide, matches, work10);
+        if (rc) return rc;
+        memcpy(sample_walk_last, work10, sizeof work10);
+        return RSBWT_OK;
+    });
+}
+
+int rsbwt_set_walk_samples(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint64_t min_count, uint32_t max_steps,
+                           uint32_t flags, const uint8_t *codes, size_t C, uint32_t size_of_sample, int has_other_meta_data, const uint8_t *mask,
+                           uint64_t max_rows, uint32_t max_locate_steps, char *ext, uint32_t *steps, uint8_t *stop, uint32_t *support,
+                           uint64_t *last) {
+    return guarded("rsbwt_set_walk_samples", [&]() -> int {
+        for (uint64_t &w : sample_walk_last) w = 0;
+        for (double &t : sample_walk_ms) t = 0;
+        int rc = walk_set_check(s);
+        if (rc) return rc;
+        if ((rc = sample_walk_flags_ok(ctx, flags, &max_steps, Q)) != RSBWT_OK) return rc;
+        sample_walk_call c;
+        if ((rc = sample_walk_prepare(s, codes, C, size_of_sample, has_other_meta_data, mask, max_rows, max_locate_steps, &c)) != RSBWT_OK) return rc;
+        std::vector<uint64_t> rel;
+        size_t N = 0;
+        if ((rc = match_check_batch(text, off, Q, &rel, &N)) != RSBWT_OK) return rc;
+        if (Q == 0) return RSBWT_OK;
+        if (!ext || !steps || !stop) return fail(RSBWT_EINVAL, "null argument");
+        const uint64_t m = min_count ? min_count : 1ull;
+        const char *t0 = N ? text + off[0] : nullptr;
+        uint64_t work10[10] = {Q, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (s->groups.size() == 1) {  // the whole walk enqueued at once, slice by slice
+            group_call gc(s->groups[0], true);
+            if (gc.rc) return gc.rc;
+            rc = sample_walk_group(gc.g, gc, t0, rel.data(), Q, N, ctx, m, max_steps, flags, c, false, ext, steps, stop, support, last, nullptr, nullptr,
+                                   nullptr, work10, sample_walk_times_on() ? sample_walk_ms : nullptr);
+        } else {
+            rc = walk_samples_by_steps(s, t0, rel.data(), Q, ctx, m, max_steps, flags, c, ext, steps, stop, support, last, work10);
+        }
+        if (rc) return rc;
+        memcpy(sample_walk_last, work10, sizeof work10);
+        return RSBWT_OK;
+    });
+}
+
+// one-device set, the caller's buffers and stream, nothing synchronised
+int rsbwt_set_walk_samples_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, size_t N, uint32_t ctx, uint64_t min_count,
+                               uint32_t max_steps, uint32_t flags, const void *d_keys, size_t C, uint32_t size_of_sample, int has_other_meta_data,
+                               const void *d_mask, uint64_t max_rows, uint32_t max_locate_steps, void *d_ext, void *d_steps, void *d_stop,
+                               void *d_support, void *d_last, void *d_status8, void *stream) {
+    return guarded("rsbwt_set_walk_samples_dev", [&]() -> int {
+        dev_group *g = nullptr;
+        int rc = one_device_group(s, &g);
+        if (rc) return rc;
+        if ((rc = sample_walk_flags_ok(ctx, flags, &max_steps, Q)) != RSBWT_OK) return rc;
+        if ((rc = sample_set_ok(s)) != RSBWT_OK) return rc;
+        if ((rc = sample_shape_ok(C, size_of_sample)) != RSBWT_OK) return rc;
+        if ((rc = sample_walk_shape_ok(s, max_rows)) != RSBWT_OK) return rc;
+        if (!d_keys || !d_mask || !d_status8) return fail(RSBWT_EINVAL, "null argument");
+        hipStream_t st = (hipStream_t)stream;
+        if (Q == 0) {
+            HIP_OK(hipMemsetAsync(d_status8, 0, 64, st));
+            return RSBWT_OK;
+        }
+        if (!d_text || !d_off || !d_ext || !d_steps || !d_stop) return fail(RSBWT_EINVAL, "null argument");
+        if (N >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu positions in one call: at most 2^31 - 1", N);
+        const uint32_t S = (uint32_t)g->idx.size();
+        const size_t per = std::min(Q, sample_walk_slice_seeds(max_rows, SAMPLE_WALK_BUDGET));
+        const size_t a_bits = al256(sample_walk_mask_words(C) * 4), a_work = al256(SAMPLE_WALK_WORK * TALLY_WORK_STRIDE * 8);
+        scratch_cache::lease mem;
+        hipError_t e = g->scratch.take(a_bits + a_work + sample_walk_bytes(per, S, max_steps, max_rows), st, &mem);
+        if (e != hipSuccess) return fail_hip(e, "scratch for a sample walk");
+        uint8_t *d_bits = (uint8_t *)mem.p, *d_work = d_bits + a_bits, *d_scratch = d_work + a_work;
+        rc = [&]() -> int {
+            if ((e = launch_sample_walk_mask(d_mask, C, d_bits, st)) != hipSuccess) return fail_hip(e, "mask kernel launch");
+            HIP_OK(hipMemsetAsync(d_work, 0, a_work, st));
+            for (size_t q0 = 0; q0 < Q; q0 += per) {  // (the slices share the scratch: stream order keeps them apart)
+                const size_t mq = std::min(per, Q - q0);
+                sample_walk_args a;
+                a.views = g->d_views;
+                a.meta = g->d_meta;
+                a.S = S;
+                a.num_cus = g->num_cus;
+                a.bt.text = (const char *)d_text;
+                a.bt.off = (const uint64_t *)d_off + q0;
+                a.bt.Q = mq;
+                a.bt.N = N;
+                a.bt.ctx = ctx;
+                a.bt.max_steps = max_steps;
+                a.bt.min_count = min_count ? min_count : 1ull;
+                a.bt.flags = flags;
+                a.keys = (const uint64_t *)d_keys;
+                a.mask_bits = (const uint32_t *)d_bits;
+                a.C = (uint32_t)C;
+                a.size_of_sample = size_of_sample;
+                a.has_other = has_other_meta_data ? 1u : 0u;
+                a.max_rows = max_rows;
+                a.max_locate_steps = max_locate_steps;
+                a.ext = (char *)d_ext + q0 * (size_t)max_steps;
+                a.steps = (uint32_t *)d_steps + q0;
+                a.stop = (uint8_t *)d_stop + q0;
+                a.support = d_support ? (uint32_t *)d_support + q0 * (size_t)max_steps : nullptr;
+                a.last = d_last ? (uint64_t *)d_last + q0 * 4 : nullptr;
+                a.evaluate_only = 0u;
+                a.raw = a.matches8 = a.wide = nullptr;
+                a.work = (unsigned long long *)d_work;
+                if ((e = sample_walk_enqueue(g->scratch, a, d_scratch, st)) != hipSuccess) return fail_hip(e, "sample walk launches");
+            }
+            if ((e = launch_sample_walk_status((const unsigned long long *)d_work, d_status8, st)) != hipSuccess) return fail_hip(e, "status kernel launch");
+            return RSBWT_OK;
+        }();
+        g->scratch.give(mem, st);
+        return rc;
+    });
+}
+
+void rsbwt_set_walk_samples_last_work(uint64_t *work10) {
+    if (work10) memcpy(work10, sample_walk_last, sizeof sample_walk_last);
+}
+
+void rsbwt_set_walk_samples_last_times(double *ms7) {
+    if (ms7) memcpy(ms7, sample_walk_ms, sizeof sample_walk_ms);
 }
 
 int rsbwt_rccl_available(void) { return rccl().ok ? 1 : 0; }

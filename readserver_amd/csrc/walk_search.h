@@ -48,9 +48,9 @@ struct walk_cand {
 };
 
 // The rows of findInterval(candidate) in shard *sv (0 when `live` is false), for the 64 candidates of a wave at once.
-// Every lane of the wave must be in the call.
+// Every lane of the wave must be in the call.  lower (optional): the interval's first row where the rows are not 0.
 __device__ __forceinline__ uint64_t walk_search(const shard_view *sv, bool live, const walk_cand &cd, uint32_t lane, uint32_t stage_lds,
-                                                const staged_line &L, walk_tally &tally) {
+                                                const staged_line &L, walk_tally &tally, uint64_t *lower = nullptr) {
     const char *lines_bytes = reinterpret_cast<const char *>(sv->lines);
     const uint32_t S = sv->sp.S, nlines = (uint32_t)sv->nlines;
     const double inv = sv->sp.inv;
@@ -95,6 +95,7 @@ __device__ __forceinline__ uint64_t walk_search(const shard_view *sv, bool live,
         if (active && !pending) {
             if (j >= K) {
                 rows = hi - lo + 1ull;  // the whole candidate: its interval is proper
+                if (lower) *lower = lo;
                 active = false;
             } else {
                 c = cd.at(K - 1u - j);

@@ -1,4 +1,4 @@
-// capi_internal.h -- what the C-ABI translation units (capi.hip, sets.hip) share: the handle
+// capi_internal.h -- what the C-ABI translation units (capi.hip, sets.hip, set_graph.hip) share: the handle
 // structs behind include/rsbwt.h's opaque types, per-call contexts, and the search launcher.
 #ifndef RSBWT_CAPI_INTERNAL_H
 #define RSBWT_CAPI_INTERNAL_H
@@ -139,7 +139,7 @@ int overlap_host_views(scratch_cache &scratch, hipStream_t st, const shard_view 
                        size_t N, uint32_t min_overlap, uint32_t max_overlap, uint64_t *pairs, std::vector<rsbwt_overlap> *recs, uint64_t *work5);
 void overlap_set_last_work(const uint64_t work6[6]);
 void overlap_get_last_work(uint64_t work6[6]);
-// walk.hip: what the host-buffer extension and walk calls share (capi.hip: one handle; sets.hip: a set); batches are
+// walk.hip: what the host-buffer extension and walk calls share (capi.hip: one handle; set_graph.hip: a set); batches are
 // checked by match_check_batch and walk_check_args (ctx, flags and -- where max_steps is given -- max_steps and Q x max_steps).
 //   extension_host_views  one device's share on `st` (synchronised before it returns): counts u64[S][Q][4]; work6[2..5] += the
 //                         launch's counters
@@ -164,7 +164,7 @@ int unitig_host_views(scratch_cache &scratch, hipStream_t st, const shard_view *
                       uint32_t *support, uint64_t *last, uint64_t *work8);
 void unitig_set_last_work(const uint64_t work8[8]);
 void unitig_get_last_work(uint64_t work8[8]);
-// paths.hip: what the path calls share (sets.hip).
+// paths.hip: what the path calls share (set_graph.hip).
 //   paths_check_args      ctx, flags, max_steps, max_paths, max_evals and Q x max_paths x max_steps
 //   paths_host_views      a whole paths call on one device on `st` (synchronised before it returns): trel (the targets'
 //                         offsets from toff[0], TN symbols at tt0) may be null = no targets, min_support is optional;

@@ -1,5 +1,5 @@
 // paths_rule.h -- the decisions of rsbwt_set_paths' depth-first search from a seed (include/rsbwt.h: the definition), for the
-// device (paths.hip, paths_kernel), the host (sets.hip, a set over several device groups) and, as a program of its own,
+// device (paths.hip, paths_kernel), the host (graph_steps.h, a set over several device groups) and, as a program of its own,
 // tests/native/paths_rule_host.cpp.
 //
 // A seed's search holds the current path, the evaluations made so far and a FRAME STORE: a stack with one frame per depth

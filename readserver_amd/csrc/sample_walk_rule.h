@@ -1,5 +1,5 @@
 // sample_walk_rule.h -- what the host decides about a sample walk (include/rsbwt.h: the definition), for the device
-// (sample_walk.hip), the host (sets.hip) and, as a program of its own, tests/native/sample_walk_rule_host.cpp.
+// (sample_walk.hip), the host (set_graph.hip, graph_steps.h) and, as a program of its own, tests/native/sample_walk_rule_host.cpp.
 //
 //   MASK    u8[C], one byte per code of the ascending dictionary -> one bit per column (bit col of word col / 32).  The
 //           unknown-code column C has no bit: it never counts.

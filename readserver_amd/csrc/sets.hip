@@ -31,25 +31,15 @@
 #include "capi_internal.h"
 #include "gt_span_rule.h"
 #include "meta_file.h"
-#include "paths_rule.h"
 #include "sample_codes.h"
-#include "sample_walk_rule.h"
 #include "service.h"
-#include "unitig_rule.h"
-
-using namespace rsb;
+#include "set_internal.h"
 
 #ifndef RSB_1MM_TABLE_PREPASS_DEFAULT
 #define RSB_1MM_TABLE_PREPASS_DEFAULT true
 #endif
 
 namespace {
-
-#define HIP_OK(x)                                              \
-    do {                                                       \
-        hipError_t _e = (x);                                   \
-        if (_e != hipSuccess) return fail_hip(_e, #x);         \
-    } while (0)
 
 struct rccl_api {
     void *lib = nullptr;
@@ -97,71 +87,6 @@ sum_rows_kernel(const uint64_t *__restrict__ rows, uint32_t S, size_t m, uint64_
     for (uint32_t r = 0; r < S; ++r) s += rows[(size_t)r * m + i];
     sum[i] = s;
 }
-
-}  // namespace
-
-// the shards of one device
-struct dev_group : search_meter {
-    int device = 0;   // the GPU
-    int logical = 0;  // the device number its shards were opened with: what groups them (= device outside tests, capi.hip resolve_device)
-    int num_cus = 256;
-    std::vector<size_t> idx;         // positions in the set, ascending
-    shard_view *d_views = nullptr;   // [idx.size()] in HBM: what the searches read (written by make_groups and when tables are attached, never else)
-    shard_view *d_xviews = nullptr;  // the same WITH the shards' select samples, for the fused extraction: a second array, made once
-    std::atomic<bool> xviews_ready{false};
-    uint64_t *d_ktab = nullptr;      // the interleaved k-mer tables of the shards this set gave one
-    meta_view *d_meta = nullptr;     // [idx.size()] in HBM: the shards' sample tables (rsbwt_set_meta_*), made with the first build
-    ctx_pool pool;
-    ncclComm_t comm = nullptr;
-    // the gather without RCCL (peer copies issued on the root's stream): "the block is ready" on this group's stream,
-    // "the block has been read" back onto it
-    hipEvent_t peer_ready = nullptr, peer_done = nullptr;
-    // side streams for calls that let the group's shards work side by side (small 1-mismatch batches: one shard's
-    // launch does not fill the GPU), forked from and joined to the caller's stream with events; made on first use
-    static constexpr int FORK = 8;
-    hipStream_t fork_st[FORK] = {};
-    hipEvent_t fork_ev = nullptr, join_ev[FORK] = {};
-    std::mutex fork_mu;
-    int ensure_fork() {
-        if (fork_ev) return RSBWT_OK;  // (set last: everything below exists)
-        // each stream / event is made once, whatever a previous, partly failed attempt left behind
-        for (int i = 0; i < FORK; ++i) {
-            if ((!fork_st[i] && hipStreamCreateWithFlags(&fork_st[i], hipStreamNonBlocking) != hipSuccess) ||
-                (!join_ev[i] && hipEventCreateWithFlags(&join_ev[i], hipEventDisableTiming) != hipSuccess)) {
-                (void)hipGetLastError();
-                return fail(RSBWT_EHIP, "cannot create the side streams of a shard set");
-            }
-        }
-        if (hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming) != hipSuccess) {
-            fork_ev = nullptr;
-            return fail(RSBWT_EHIP, "cannot create an event");
-        }
-        return RSBWT_OK;
-    }
-};
-
-struct rsbwt_set {
-    std::vector<rsbwt_t *> shards;
-    bool owns = false;
-    std::vector<dev_group *> groups;
-    bool comms_tried = false, comms_ok = false;
-    std::mutex mu;
-    // Collectives on the set's communicators are enqueued by one thread at a time: two callers
-    // interleaving their group calls could reach the communicators in different orders.
-    std::mutex comm_mu;
-    // the per-read sample table (rsbwt_set_meta_*): shard i's off u64[num_strings + 1] / value bytes, on shard i's device;
-    // empty = no table.  Written by build / load / clear only, which must not run beside a lookup.
-    // d_heads: one bit per ordinal, set at the first ordinal of every string a pair named (rsbwt_set_sample_counts)
-    struct meta_shard {
-        uint64_t *d_off = nullptr;
-        uint8_t *d_bytes = nullptr;
-        uint32_t *d_heads = nullptr;
-    };
-    std::vector<meta_shard> meta;
-    uint64_t meta_bytes = 0, meta_head_bytes = 0;
-};
-
-namespace {
 
 int publish_views(rsbwt_set_t *s) {
     for (dev_group *g : s->groups) {
@@ -233,25 +158,6 @@ bool group_is_narrow(const rsbwt_set_t *s, const dev_group *g, uint32_t k) {
     return !g->idx.empty();
 }
 
-// runs fn(group index) for every device group, concurrently when there are several
-template <class F>
-int for_each_group(rsbwt_set_t *s, F &&fn) {
-    const size_t G = s->groups.size();
-    if (G == 1) return fn(0);
-    std::vector<int> rcs(G, RSBWT_OK);
-    std::vector<std::string> errs(G);
-    std::vector<std::thread> th;
-    for (size_t g = 0; g < G; ++g)
-        th.emplace_back([&, g] {
-            rcs[g] = fn(g);
-            if (rcs[g]) errs[g] = rsbwt_last_error();  // the message is thread-local: carry it over
-        });
-    for (auto &t : th) t.join();
-    for (size_t g = 0; g < G; ++g)
-        if (rcs[g]) return fail(rcs[g], "%s", errs[g].c_str());
-    return RSBWT_OK;
-}
-
 // Inside for_each_group, for calls that answer [num_shards][Q] arrays in the set's shard order (b: an optional second
 // array): fn(g, a', b') does group gi's work into [S_g][Q] blocks.  When the group's shards sit next to each other in
 // the set (the usual map: shard s -> GPU s / 8) those blocks ARE the caller's rows; else they are temporaries whose
@@ -271,40 +177,6 @@ int group_scatter(rsbwt_set_t *s, size_t gi, size_t Q, uint64_t *a, uint64_t *b,
     }
     return RSBWT_OK;
 }
-
-// What every device-resident call of a set starts with: they serve a set whose shards all sit on one device.
-int one_device_group(rsbwt_set_t *s, dev_group **g) {
-    if (!s) return fail(RSBWT_EINVAL, "null set");
-    if (s->groups.size() != 1) return fail(RSBWT_EINVAL, "the set spans %zu devices: device-resident calls need one", s->groups.size());
-    *g = s->groups[0];
-    return use_device((*g)->device);
-}
-
-// A call context on g's device for the duration of one host-buffer call; rc says whether there is one.  The capped
-// calls also lease their scratch through it (la, lb): their launches may still run when such a call leaves early, so
-// the destructor waits for the stream before the leases go back.  A call without leases waits for nothing here.
-struct group_call {
-    dev_group *const g;
-    const bool leases;
-    int rc;
-    call_ctx *c = nullptr;
-    hipStream_t st = nullptr;
-    scratch_cache::lease la, lb;
-    explicit group_call(dev_group *grp, bool with_leases = false) : g(grp), leases(with_leases), rc(use_device(grp->device)) {
-        if (rc == RSBWT_OK && !(c = g->pool.acquire())) rc = fail(RSBWT_EHIP, "cannot create a HIP stream");
-        if (c) st = c->st[0];
-    }
-    group_call(const group_call &) = delete;
-    ~group_call() {
-        if (!c) return;
-        if (leases) {
-            (void)hipStreamSynchronize(st);
-            g->scratch.give(la, st);
-            g->scratch.give(lb, st);
-        }
-        g->pool.release(c);
-    }
-};
 
 // Group g's share of the caller's (shard_of, rows): the shards as the group numbers them, their rows, and where each
 // entry stands in the caller's arrays (ascending)
@@ -2482,553 +2354,6 @@ void rsbwt_set_overlap_last_work(uint64_t *work6) {
     if (work6) overlap_get_last_work(work6);
 }
 
-// ---- extension counts and walks (walk.hip): what the reads say comes next, over every shard ----
-namespace {
-int walk_set_check(rsbwt_set_t *s) {
-    // (no set can be had on a box without a GPU: the call says so instead of blaming the argument)
-    if (!s && rsbwt_device_count() == 0) return fail(RSBWT_ENODEV, "no HIP device is visible: the popBWT engine has no CPU fallback");
-    if (!s) return fail(RSBWT_EINVAL, "null set");
-    for (rsbwt_t *h : s->shards)
-        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
-    return RSBWT_OK;
-}
-
-// One evaluation of every seed in every shard: each device group counts its shards' rows of counts[S][Q][4], side by
-// side; the host only puts group gi's row j at row idx[j].  work6[2..5] += the launches' counters.
-int extension_groups(rsbwt_set_t *s, const char *t0, const uint64_t *rel, size_t Q, size_t N, uint32_t ctx, uint32_t flags, uint64_t *counts,
-                     uint64_t *work6) {
-    struct group_out {
-        std::vector<uint64_t> counts;
-        uint64_t work[6] = {0, 0, 0, 0, 0, 0};
-    };
-    std::vector<group_out> outs(s->groups.size());
-    const size_t row = Q * 4;
-    int rc = for_each_group(s, [&](size_t gi) -> int {
-        dev_group *g = s->groups[gi];
-        group_call gc(g);
-        if (gc.rc) return gc.rc;
-        group_out &o = outs[gi];
-        const size_t Sg = g->idx.size();
-        // (a group whose shards sit next to each other in the set answers straight into the caller's rows)
-        uint64_t *dst = counts + g->idx.front() * row;
-        if (g->idx.back() - g->idx.front() + 1 != Sg) {
-            o.counts.resize(Sg * row);
-            dst = o.counts.data();
-        }
-        return extension_host_views(g->scratch, gc.st, g->d_views, (uint32_t)Sg, t0, rel, Q, N, ctx, flags, dst, o.work);
-    });
-    if (rc) return rc;
-    for (size_t gi = 0; gi < outs.size(); ++gi) {
-        const dev_group *g = s->groups[gi];
-        const group_out &o = outs[gi];
-        for (size_t j = 0; !o.counts.empty() && j < g->idx.size(); ++j) memcpy(counts + g->idx[j] * row, o.counts.data() + j * row, row * 8);
-        for (int i = 2; i < 6; ++i) work6[i] += o.work[i];
-    }
-    return RSBWT_OK;
-}
-
-// The walk of a set over several device groups: per step the groups evaluate the seeds still walking (their contexts
-// alone are sent), the host sums over the shards, applies the rule and goes again -- walk_kernel's decision, on the host.
-int walk_by_steps(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint64_t m, uint32_t max_steps, uint32_t flags,
-                  char *ext, uint32_t *steps, uint8_t *stop, uint32_t *support, uint64_t *last, uint64_t *work6) {
-    const bool left = (flags & RSBWT_WALK_LEFT) != 0u;
-    const size_t S = s->shards.size();
-    memset(ext, 0, Q * (size_t)max_steps);
-    if (support) memset(support, 0, Q * (size_t)max_steps * 4);
-    std::vector<std::string> cur(Q);
-    std::vector<size_t> live;
-    for (size_t q = 0; q < Q; ++q) {
-        const uint64_t Lq = off[q + 1] - off[q];
-        bool valid = Lq >= ctx;
-        if (valid) {
-            cur[q].assign(left ? text + off[q] : text + off[q + 1] - ctx, ctx);
-            for (char ch : cur[q]) valid = valid && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
-        }
-        steps[q] = 0;
-        stop[q] = valid ? 0 : (uint8_t)RSBWT_WALK_INVALID;
-        if (last)
-            for (int c = 0; c < 4; ++c) last[4 * q + c] = 0;
-        if (valid) live.push_back(q);
-    }
-    std::string t;
-    std::vector<uint64_t> rel, counts;
-    while (!live.empty()) {  // (every seed of `live` has fewer than max_steps symbols appended)
-        const size_t nl = live.size();
-        t.clear();
-        rel.resize(nl + 1);
-        for (size_t i = 0; i < nl; ++i) {
-            rel[i] = (uint64_t)i * ctx;
-            t += cur[live[i]];
-        }
-        rel[nl] = (uint64_t)nl * ctx;
-        if (rel[nl] >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu seeds x %u context symbols: under 2^31 in one call", nl, ctx);
-        counts.assign(S * nl * 4, 0);
-        const int rc = extension_groups(s, t.data(), rel.data(), nl, (size_t)rel[nl], ctx, flags, counts.data(), work6);
-        if (rc) return rc;
-        std::vector<size_t> next;
-        for (size_t i = 0; i < nl; ++i) {
-            const size_t q = live[i];
-            uint64_t sup[4] = {0, 0, 0, 0};
-            uint32_t nlive = 0, pick = 0;
-            for (uint32_t c = 0; c < 4; ++c) {
-                for (size_t p = 0; p < S; ++p) sup[c] += counts[(p * nl + i) * 4 + c];
-                if (sup[c] >= m) {
-                    ++nlive;
-                    pick = c;
-                }
-            }
-            uint32_t why = 0;
-            if (nlive == 1) {
-                const size_t at = q * (size_t)max_steps + steps[q];
-                ext[at] = "ACGT"[pick];
-                if (support) support[at] = sup[pick] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)sup[pick];
-                work6[1] += 1;
-                if (left) cur[q] = std::string(1, "ACGT"[pick]) + cur[q].substr(0, ctx - 1);
-                else cur[q] = cur[q].substr(1) + "ACGT"[pick];
-                if (++steps[q] == max_steps) why = RSBWT_WALK_LIMIT;
-            } else {
-                why = nlive == 0 ? RSBWT_WALK_DEAD_END : RSBWT_WALK_BRANCH;
-            }
-            if (why == 0) {
-                next.push_back(q);
-                continue;
-            }
-            stop[q] = (uint8_t)why;
-            if (last && why != RSBWT_WALK_LIMIT)
-                for (int c = 0; c < 4; ++c) last[4 * q + c] = sup[c];
-        }
-        live.swap(next);
-    }
-    return RSBWT_OK;
-}
-
-// The unitigs of a set over several device groups: per step the groups evaluate the onward contexts of the items still
-// walking, the right-walking ones in one call and the left-walking ones in another (a call has one direction); the host
-// sums over the shards and applies unitig_rule.h's onward half; the nodes entered are then evaluated in the opposite
-// direction, and the host sums and decides -- unitig_kernel's step, on the host.  work8 as unitig_host_views'.
-int unitigs_by_steps(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint64_t m, uint32_t max_steps, uint32_t flags,
-                     char *ext, uint32_t *steps, uint8_t *stop, uint32_t *support, uint64_t *last, uint64_t *work8) {
-    const size_t S = s->shards.size(), items = 2 * Q;
-    memset(ext, 0, items * (size_t)max_steps);
-    if (support) memset(support, 0, items * (size_t)max_steps * 4);
-    if (last) memset(last, 0, items * 64);
-    std::vector<std::string> cur(items);  // an item's context
-    std::vector<size_t> live;
-    for (size_t i = 0; i < items; ++i) {
-        const size_t q = i >> 1;
-        const bool left = (i & 1) != 0;
-        bool valid = off[q + 1] - off[q] >= ctx;
-        if (valid) {
-            cur[i].assign(left ? text + off[q] : text + off[q + 1] - ctx, ctx);
-            for (char ch : cur[i]) valid = valid && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
-        }
-        steps[i] = 0;
-        stop[i] = valid ? 0 : (uint8_t)RSBWT_WALK_INVALID;
-        if (valid) live.push_back(i);
-    }
-    // sums[k][0..3] of the strings str[k] (ctx symbols each) of items `who`, in `who`'s own direction or the opposite one
-    std::string t;
-    std::vector<uint64_t> rel, counts;
-    auto evaluate = [&](const std::vector<size_t> &who, const std::vector<std::string> &str, bool opposite, std::vector<uint64_t> &sums) -> int {
-        sums.assign(who.size() * 4, 0);
-        for (int side = 0; side < 2; ++side) {
-            std::vector<size_t> part;
-            for (size_t k = 0; k < who.size(); ++k)
-                if ((int)(who[k] & 1) == side) part.push_back(k);
-            const size_t np = part.size();
-            if (np == 0) continue;
-            if ((uint64_t)np * ctx >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu sides x %u context symbols: under 2^31 in one call", np, ctx);
-            t.clear();
-            rel.resize(np + 1);
-            for (size_t j = 0; j < np; ++j) {
-                rel[j] = (uint64_t)j * ctx;
-                t += str[part[j]];
-            }
-            rel[np] = (uint64_t)np * ctx;
-            const bool left = (side != 0) != opposite;
-            counts.assign(S * np * 4, 0);
-            const int rc = extension_groups(s, t.data(), rel.data(), np, (size_t)rel[np], ctx, flags | (left ? RSBWT_WALK_LEFT : 0u), counts.data(), work8);
-            if (rc) return rc;
-            for (size_t j = 0; j < np; ++j)
-                for (uint32_t c = 0; c < 4; ++c)
-                    for (size_t p = 0; p < S; ++p) sums[part[j] * 4 + c] += counts[(p * np + j) * 4 + c];
-        }
-        return RSBWT_OK;
-    };
-    std::vector<uint64_t> onward, back;
-    std::vector<size_t> tent, tent_at, next;
-    std::vector<std::string> ctxs, nodes;
-    std::vector<uint32_t> picks;
-    while (!live.empty()) {  // (every item of `live` has fewer than max_steps symbols appended)
-        const size_t nl = live.size();
-        ctxs.clear();
-        for (size_t i : live) ctxs.push_back(cur[i]);
-        int rc = evaluate(live, ctxs, false, onward);
-        if (rc) return rc;
-        work8[6] += nl;
-        tent.clear(), tent_at.clear(), nodes.clear(), picks.clear(), next.clear();
-        for (size_t k = 0; k < nl; ++k) {
-            const size_t i = live[k];
-            uint32_t pick = 0;
-            const uint32_t why = unitig_onward(&onward[k * 4], m, steps[i], max_steps, &pick);
-            if (why != UNITIG_GO) {
-                stop[i] = (uint8_t)why;
-                if (last)
-                    for (int c = 0; c < 4; ++c) last[8 * i + c] = onward[k * 4 + c];
-                continue;
-            }
-            tent.push_back(i);
-            tent_at.push_back(k);
-            picks.push_back(pick);
-            nodes.push_back((i & 1) ? std::string(1, "ACGT"[pick]) + cur[i].substr(0, ctx - 1) : cur[i].substr(1) + "ACGT"[pick]);
-        }
-        if (tent.empty()) break;  // (every item stopped)
-        if ((rc = evaluate(tent, nodes, true, back)) != RSBWT_OK) return rc;
-        work8[7] += tent.size();
-        for (size_t k = 0; k < tent.size(); ++k) {
-            const size_t i = tent[k];
-            const uint64_t *on = &onward[tent_at[k] * 4];
-            if (unitig_return(&back[k * 4], m) != UNITIG_GO) {
-                stop[i] = (uint8_t)RSBWT_WALK_JOIN;
-                if (last)
-                    for (int c = 0; c < 4; ++c) last[8 * i + c] = on[c], last[8 * i + 4 + c] = back[k * 4 + c];
-                continue;
-            }
-            const size_t at = i * (size_t)max_steps + steps[i];
-            ext[at] = "ACGT"[picks[k]];
-            if (support) support[at] = unitig_saturate(on[picks[k]]);
-            work8[1] += 1;
-            cur[i] = nodes[k];
-            if (++steps[i] == max_steps) stop[i] = (uint8_t)RSBWT_WALK_LIMIT;
-            else next.push_back(i);
-        }
-        live.swap(next);
-    }
-    return RSBWT_OK;
-}
-
-// The paths of a set over several device groups: per round the groups evaluate the current node of every seed still
-// searching (its context alone is sent), the host sums over the shards and takes the writer lane's decisions with
-// paths_rule.h -- paths_kernel's round, on the host.  tt / trel: the targets, trel null = none.  work8 as paths_host_views'.
-int paths_by_steps(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const char *tt, const uint64_t *trel, uint32_t ctx, uint64_t m,
-                   uint32_t max_steps, uint32_t max_paths, uint32_t max_evals, uint32_t flags, char *ext, uint32_t *steps, uint8_t *stop,
-                   uint32_t *min_support, uint32_t *npaths, uint8_t *state, uint64_t *work8) {
-    const bool left = (flags & RSBWT_WALK_LEFT) != 0u;
-    const size_t S = s->shards.size(), slots = Q * (size_t)max_paths;
-    memset(ext, 0, slots * max_steps);
-    memset(steps, 0, slots * 4);
-    memset(stop, 0, slots);
-    if (min_support) memset(min_support, 0, slots * 4);
-    struct search {
-        std::string seed_ctx, path, target;
-        std::vector<paths_frame> frames;
-        uint32_t nframes = 0, evals = 0, min_cur = PATHS_NO_SUPPORT;
-    };
-    std::vector<search> st(Q);
-    // the ctx symbols at the walking end of seed + path (reverse(path) + seed)
-    auto context = [&](const search &a) {
-        if (left) return (std::string(a.path.rbegin(), a.path.rend()) + a.seed_ctx).substr(0, ctx);
-        const std::string all = a.seed_ctx + a.path;
-        return all.substr(all.size() - ctx);
-    };
-    auto at_target = [&](const search &a) {
-        if (a.target.empty()) return false;
-        const std::string c = context(a);
-        return left ? c.compare(0, a.target.size(), a.target) == 0 : c.compare(ctx - a.target.size(), a.target.size(), a.target) == 0;
-    };
-    std::vector<size_t> live;
-    for (size_t q = 0; q < Q; ++q) {
-        bool valid = off[q + 1] - off[q] >= ctx;
-        if (valid) {
-            st[q].seed_ctx.assign(left ? text + off[q] : text + off[q + 1] - ctx, ctx);
-            for (char ch : st[q].seed_ctx) valid = valid && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
-        }
-        npaths[q] = 0;
-        state[q] = valid ? 0 : (uint8_t)PATHS_INVALID;
-        if (!valid) continue;
-        if (trel) st[q].target.assign(tt + trel[q], (size_t)(trel[q + 1] - trel[q]));
-        st[q].frames.resize(paths_frames(max_steps, max_evals));
-        live.push_back(q);
-    }
-    std::string t;
-    std::vector<uint64_t> rel, counts;
-    while (!live.empty()) {  // (every seed of `live` has a node to evaluate: its end test said so)
-        const size_t nl = live.size();
-        t.clear();
-        rel.resize(nl + 1);
-        for (size_t i = 0; i < nl; ++i) {
-            rel[i] = (uint64_t)i * ctx;
-            t += context(st[live[i]]);
-        }
-        rel[nl] = (uint64_t)nl * ctx;
-        if (rel[nl] >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu seeds x %u context symbols: under 2^31 in one call", nl, ctx);
-        counts.assign(S * nl * 4, 0);
-        const int rc = extension_groups(s, t.data(), rel.data(), nl, (size_t)rel[nl], ctx, flags, counts.data(), work8);
-        if (rc) return rc;
-        std::vector<size_t> next;
-        for (size_t i = 0; i < nl; ++i) {
-            const size_t q = live[i];
-            search &a = st[q];
-            uint64_t sup[4] = {0, 0, 0, 0};
-            for (uint32_t c = 0; c < 4; ++c)
-                for (size_t p = 0; p < S; ++p) sup[c] += counts[(p * nl + i) * 4 + c];
-            ++a.evals;
-            work8[6] += 1;
-            const uint32_t mask = paths_live(sup, m);
-            uint32_t why = PATHS_DEAD_END;
-            if (mask != 0u) {
-                a.path += "ACGT"[paths_advance(a.frames.data(), &a.nframes, (uint32_t)a.path.size(), mask, sup, &a.min_cur)];
-                work8[1] += 1;
-                why = paths_end(at_target(a), (uint32_t)a.path.size(), max_steps, a.evals, max_evals);
-            }
-            bool searching = true;
-            while (why != PATHS_GO) {  // (max_paths times at the most: every turn puts a path out)
-                const size_t at = q * (size_t)max_paths + npaths[q];
-                memcpy(ext + at * max_steps, a.path.data(), a.path.size());
-                steps[at] = (uint32_t)a.path.size();
-                stop[at] = (uint8_t)why;
-                if (min_support) min_support[at] = paths_min_out((uint32_t)a.path.size(), a.min_cur);
-                ++npaths[q];
-                work8[7] += 1;
-                const uint32_t done = paths_done(why, a.nframes, npaths[q], max_paths);
-                if (done != PATHS_GO) {
-                    state[q] = (uint8_t)done;
-                    searching = false;
-                    break;
-                }
-                uint32_t d = 0;
-                const uint32_t c = paths_backtrack(a.frames.data(), &a.nframes, &d, &a.min_cur);
-                a.path.resize(d);
-                a.path += "ACGT"[c];
-                work8[1] += 1;
-                why = paths_end(at_target(a), (uint32_t)a.path.size(), max_steps, a.evals, max_evals);
-            }
-            if (searching) next.push_back(q);
-        }
-        live.swap(next);
-    }
-    return RSBWT_OK;
-}
-}  // namespace
-
-int rsbwt_set_extensions(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint32_t flags, uint64_t *counts) {
-    return guarded("rsbwt_set_extensions", [&]() -> int {
-        walk_set_last_work(nullptr);
-        int rc = walk_set_check(s);
-        if (rc) return rc;
-        if ((rc = walk_check_args(ctx, flags, nullptr, Q)) != RSBWT_OK) return rc;
-        std::vector<uint64_t> rel;
-        size_t N = 0;
-        if ((rc = match_check_batch(text, off, Q, &rel, &N)) != RSBWT_OK) return rc;
-        if (Q == 0) return RSBWT_OK;
-        if (!counts) return fail(RSBWT_EINVAL, "null argument");
-        uint64_t work6[6] = {Q, 0, 0, 0, 0, 0};
-        rc = extension_groups(s, N ? text + off[0] : nullptr, rel.data(), Q, N, ctx, flags, counts, work6);
-        if (rc) return rc;
-        walk_set_last_work(work6);
-        return RSBWT_OK;
-    });
-}
-
-int rsbwt_set_walk(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint64_t min_count, uint32_t max_steps,
-                   uint32_t flags, char *ext, uint32_t *steps, uint8_t *stop, uint32_t *support, uint64_t *last) {
-    return guarded("rsbwt_set_walk", [&]() -> int {
-        walk_set_last_work(nullptr);
-        int rc = walk_set_check(s);
-        if (rc) return rc;
-        if ((rc = walk_check_args(ctx, flags, &max_steps, Q)) != RSBWT_OK) return rc;
-        std::vector<uint64_t> rel;
-        size_t N = 0;
-        if ((rc = match_check_batch(text, off, Q, &rel, &N)) != RSBWT_OK) return rc;
-        if (Q == 0) return RSBWT_OK;
-        if (!ext || !steps || !stop) return fail(RSBWT_EINVAL, "null argument");
-        const uint64_t m = min_count ? min_count : 1ull;
-        const char *t0 = N ? text + off[0] : nullptr;
-        uint64_t work6[6] = {Q, 0, 0, 0, 0, 0};
-        if (s->groups.size() == 1) {  // the whole walk in one launch
-            dev_group *g = s->groups[0];
-            group_call gc(g);
-            if (gc.rc) return gc.rc;
-            rc = walk_host_views(g->scratch, gc.st, g->d_views, (uint32_t)g->idx.size(), t0, rel.data(), Q, N, ctx, m, max_steps, flags, ext, steps,
-                                 stop, support, last, work6);
-        } else {
-            rc = walk_by_steps(s, t0, rel.data(), Q, ctx, m, max_steps, flags, ext, steps, stop, support, last, work6);
-        }
-        if (rc) return rc;
-        walk_set_last_work(work6);
-        return RSBWT_OK;
-    });
-}
-
-int rsbwt_set_walk_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, size_t N, uint32_t ctx, uint64_t min_count,
-                       uint32_t max_steps, uint32_t flags, void *d_ext, void *d_steps, void *d_stop, void *d_support, void *d_last,
-                       void *stream) {
-    dev_group *g = nullptr;
-    int rc = one_device_group(s, &g);
-    if (rc) return rc;
-    if ((rc = walk_check_args(ctx, flags, &max_steps, Q)) != RSBWT_OK) return rc;
-    if (Q == 0) return RSBWT_OK;
-    if (!d_text || !d_off || !d_ext || !d_steps || !d_stop) return fail(RSBWT_EINVAL, "null argument");
-    if (N >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu positions in one call: at most 2^31 - 1", N);
-    for (rsbwt_t *h : s->shards)
-        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
-    walk_batch bt;
-    bt.text = (const char *)d_text;
-    bt.off = (const uint64_t *)d_off;
-    bt.Q = Q;
-    bt.N = N;
-    bt.ctx = ctx;
-    bt.max_steps = max_steps;
-    bt.min_count = min_count ? min_count : 1ull;
-    bt.flags = flags;
-    const hipError_t e = launch_walk(g->d_views, (uint32_t)g->idx.size(), bt, d_ext, d_steps, d_stop, d_support, d_last, nullptr, (hipStream_t)stream);
-    return e == hipSuccess ? RSBWT_OK : fail_hip(e, "walk kernel launch");
-}
-
-void rsbwt_set_walk_last_work(uint64_t *work6) {
-    if (work6) walk_get_last_work(work6);
-}
-
-int rsbwt_set_unitigs(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint64_t min_count, uint32_t max_steps,
-                      uint32_t flags, char *ext, uint32_t *steps, uint8_t *stop, uint32_t *support, uint64_t *last) {
-    return guarded("rsbwt_set_unitigs", [&]() -> int {
-        unitig_set_last_work(nullptr);
-        int rc = walk_set_check(s);
-        if (rc) return rc;
-        if ((rc = unitig_check_args(ctx, flags, max_steps, Q)) != RSBWT_OK) return rc;
-        std::vector<uint64_t> rel;
-        size_t N = 0;
-        if ((rc = match_check_batch(text, off, Q, &rel, &N)) != RSBWT_OK) return rc;
-        if (Q == 0) return RSBWT_OK;
-        if (!ext || !steps || !stop) return fail(RSBWT_EINVAL, "null argument");
-        const uint64_t m = min_count ? min_count : 1ull;
-        const char *t0 = N ? text + off[0] : nullptr;
-        uint64_t work8[8] = {Q, 0, 0, 0, 0, 0, 0, 0};
-        if (s->groups.size() == 1) {  // both sides of every seed in one launch
-            dev_group *g = s->groups[0];
-            group_call gc(g);
-            if (gc.rc) return gc.rc;
-            rc = unitig_host_views(g->scratch, gc.st, g->d_views, (uint32_t)g->idx.size(), t0, rel.data(), Q, N, ctx, m, max_steps, flags, ext, steps,
-                                   stop, support, last, work8);
-        } else {
-            rc = unitigs_by_steps(s, t0, rel.data(), Q, ctx, m, max_steps, flags, ext, steps, stop, support, last, work8);
-        }
-        if (rc) return rc;
-        unitig_set_last_work(work8);
-        return RSBWT_OK;
-    });
-}
-
-int rsbwt_set_unitigs_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, size_t N, uint32_t ctx, uint64_t min_count,
-                          uint32_t max_steps, uint32_t flags, void *d_ext, void *d_steps, void *d_stop, void *d_support, void *d_last,
-                          void *stream) {
-    dev_group *g = nullptr;
-    int rc = one_device_group(s, &g);
-    if (rc) return rc;
-    if ((rc = unitig_check_args(ctx, flags, max_steps, Q)) != RSBWT_OK) return rc;
-    if (Q == 0) return RSBWT_OK;
-    if (!d_text || !d_off || !d_ext || !d_steps || !d_stop) return fail(RSBWT_EINVAL, "null argument");
-    if (N >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu positions in one call: at most 2^31 - 1", N);
-    for (rsbwt_t *h : s->shards)
-        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
-    walk_batch bt;
-    bt.text = (const char *)d_text;
-    bt.off = (const uint64_t *)d_off;
-    bt.Q = Q;
-    bt.N = N;
-    bt.ctx = ctx;
-    bt.max_steps = max_steps;
-    bt.min_count = min_count ? min_count : 1ull;
-    bt.flags = flags;
-    const hipError_t e = launch_unitigs(g->d_views, (uint32_t)g->idx.size(), bt, d_ext, d_steps, d_stop, d_support, d_last, nullptr, (hipStream_t)stream);
-    return e == hipSuccess ? RSBWT_OK : fail_hip(e, "unitig kernel launch");
-}
-
-void rsbwt_set_unitig_last_work(uint64_t *work8) {
-    if (work8) unitig_get_last_work(work8);
-}
-
-int rsbwt_set_paths(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, const char *ttext, const uint64_t *toff, uint32_t ctx,
-                    uint64_t min_count, uint32_t max_steps, uint32_t max_paths, uint32_t max_evals, uint32_t flags, char *ext, uint32_t *steps,
-                    uint8_t *stop, uint32_t *min_support, uint32_t *npaths, uint8_t *state) {
-    return guarded("rsbwt_set_paths", [&]() -> int {
-        paths_set_last_work(nullptr);
-        int rc = walk_set_check(s);
-        if (rc) return rc;
-        if ((rc = paths_check_args(ctx, flags, max_steps, max_paths, max_evals, Q)) != RSBWT_OK) return rc;
-        std::vector<uint64_t> rel, trel;
-        size_t N = 0, TN = 0;
-        if ((rc = match_check_batch(text, off, Q, &rel, &N)) != RSBWT_OK) return rc;
-        if (Q == 0) return RSBWT_OK;
-        if (!ext || !steps || !stop || !npaths || !state) return fail(RSBWT_EINVAL, "null argument");
-        if ((ttext == nullptr) != (toff == nullptr)) return fail(RSBWT_EINVAL, "targets: ttext and toff come together or not at all");
-        const bool targets = toff != nullptr;
-        if (targets) {
-            if ((rc = match_check_batch(ttext, toff, Q, &trel, &TN)) != RSBWT_OK) return rc;
-            for (size_t q = 0; q < Q; ++q)
-                if (trel[q + 1] - trel[q] > ctx)
-                    return fail(RSBWT_EINVAL, "target %zu: %llu symbols, at most ctx = %u", q, (unsigned long long)(trel[q + 1] - trel[q]), ctx);
-        }
-        const uint64_t m = min_count ? min_count : 1ull;
-        const char *t0 = N ? text + off[0] : nullptr, *tt0 = targets ? ttext + toff[0] : nullptr;
-        uint64_t work8[8] = {Q, 0, 0, 0, 0, 0, 0, 0};
-        if (s->groups.size() == 1) {  // every seed's whole search in one launch
-            dev_group *g = s->groups[0];
-            group_call gc(g);
-            if (gc.rc) return gc.rc;
-            rc = paths_host_views(g->scratch, gc.st, g->d_views, (uint32_t)g->idx.size(), t0, rel.data(), Q, N, tt0, targets ? trel.data() : nullptr, TN,
-                                  ctx, m, max_steps, max_paths, max_evals, flags, ext, steps, stop, min_support, npaths, state, work8);
-        } else {
-            rc = paths_by_steps(s, t0, rel.data(), Q, tt0, targets ? trel.data() : nullptr, ctx, m, max_steps, max_paths, max_evals, flags, ext, steps,
-                                stop, min_support, npaths, state, work8);
-        }
-        if (rc) return rc;
-        paths_set_last_work(work8);
-        return RSBWT_OK;
-    });
-}
-
-int rsbwt_set_paths_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, size_t N, const void *d_ttext, const void *d_toff,
-                        size_t TN, uint32_t ctx, uint64_t min_count, uint32_t max_steps, uint32_t max_paths, uint32_t max_evals, uint32_t flags,
-                        void *d_ext, void *d_steps, void *d_stop, void *d_min_support, void *d_npaths, void *d_state, void *stream) {
-    dev_group *g = nullptr;
-    int rc = one_device_group(s, &g);
-    if (rc) return rc;
-    if ((rc = paths_check_args(ctx, flags, max_steps, max_paths, max_evals, Q)) != RSBWT_OK) return rc;
-    if (Q == 0) return RSBWT_OK;
-    if (!d_text || !d_off || !d_ext || !d_steps || !d_stop || !d_npaths || !d_state) return fail(RSBWT_EINVAL, "null argument");
-    if ((d_ttext == nullptr) != (d_toff == nullptr)) return fail(RSBWT_EINVAL, "targets: d_ttext and d_toff come together or not at all");
-    if (N >= (1ull << 31) || TN >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu positions in one call: at most 2^31 - 1", N > TN ? N : TN);
-    for (rsbwt_t *h : s->shards)
-        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
-    paths_batch pb;
-    pb.seeds.text = (const char *)d_text;
-    pb.seeds.off = (const uint64_t *)d_off;
-    pb.seeds.Q = Q;
-    pb.seeds.N = N;
-    pb.seeds.ctx = ctx;
-    pb.seeds.max_steps = max_steps;
-    pb.seeds.min_count = min_count ? min_count : 1ull;
-    pb.seeds.flags = flags;
-    pb.ttext = (const char *)d_ttext;
-    pb.toff = (const uint64_t *)d_toff;
-    pb.TN = d_toff ? TN : 0;
-    pb.max_paths = max_paths;
-    pb.max_evals = max_evals;
-    // the frame store: leased for the launch and handed back in stream order, so nothing is waited for
-    scratch_cache::lease mem;
-    hipError_t e = g->scratch.take(paths_frame_bytes(Q, max_steps, max_evals) + 256, (hipStream_t)stream, &mem);
-    if (e != hipSuccess) return fail(RSBWT_ENOMEM, "the frame store of %zu seeds does not fit the device's free memory: %s", Q, hipGetErrorString(e));
-    e = launch_paths(g->d_views, (uint32_t)g->idx.size(), pb, mem.p, d_ext, d_steps, d_stop, d_min_support, d_npaths, d_state, nullptr,
-                     (hipStream_t)stream);
-    g->scratch.give(mem, (hipStream_t)stream);
-    return e == hipSuccess ? RSBWT_OK : fail_hip(e, "paths kernel launch");
-}
-
-void rsbwt_set_paths_last_work(uint64_t *work8) {
-    if (work8) paths_get_last_work(work8);
-}
-
 static size_t hits_1mm_scratch_one(const rsbwt_set_t *s, size_t m, uint32_t k) {
     size_t need = 0;
     for (rsbwt_t *h : s->shards) need = std::max(need, rsbwt_hits_1mm_scratch_bytes(h, m, k));
@@ -3193,10 +2518,6 @@ namespace {
 thread_local uint64_t meta_last_work[4] = {0, 0, 0, 0};
 
 inline size_t meta_head_words(uint64_t num_strings) { return (size_t)((num_strings + 31) / 32); }
-
-int meta_required(const rsbwt_set_t *s) {
-    return s->meta.empty() ? fail(RSBWT_EINVAL, "the set has no sample table (rsbwt_set_meta_build / rsbwt_set_meta_load)") : RSBWT_OK;
-}
 
 // what a build allocates on the way and lets go of when it leaves, however it leaves
 struct dev_tmp {
@@ -3535,44 +2856,6 @@ int set_read_meta_var_body(rsbwt_set_t *s, const char *text, const uint64_t *off
 // the calling thread's last call: candidate rows, rows on a head ordinal, distinct carriers, records added, records with an
 // unknown code, LF steps of the rows' walks (counting mode only)
 thread_local uint64_t sample_last_work[6] = {0, 0, 0, 0, 0, 0};
-
-struct sample_dict {
-    std::vector<uint64_t> keys;  // (host form; the device form brings them in HBM)
-    uint32_t C = 0, size_of_sample = 0, has_other = 0;
-};
-
-int sample_shape_ok(size_t C, uint32_t size_of_sample) {
-    if (size_of_sample < 1u || size_of_sample > SAMPLE_CODE_MAX) return fail(RSBWT_EINVAL, "size_of_sample %u: 1 to 8 bytes", size_of_sample);
-    if (C == 0) return fail(RSBWT_EINVAL, "an empty sample dictionary");
-    if (C >= (1ull << 31)) return fail(RSBWT_EINVAL, "%zu sample codes: at most 2^31 - 1", C);
-    return RSBWT_OK;
-}
-
-int sample_dict_make(const uint8_t *codes, size_t C, uint32_t size_of_sample, int has_other, sample_dict *d) {
-    const int rc = sample_shape_ok(C, size_of_sample);
-    if (rc) return rc;
-    size_t bad = 0;
-    switch (sample_codes_check(codes, C, size_of_sample, &d->keys, &bad)) {
-    case SAMPLE_CODES_OK: break;
-    case SAMPLE_CODES_ORDER: return fail(RSBWT_EINVAL, "sample code %zu is not above code %zu: the dictionary must be strictly ascending", bad, bad - 1);
-    default: return fail(RSBWT_EINVAL, "null argument");
-    }
-    d->C = (uint32_t)C;
-    d->size_of_sample = size_of_sample;
-    d->has_other = has_other ? 1u : 0u;
-    return RSBWT_OK;
-}
-
-int sample_set_ok(const rsbwt_set_t *s) {
-    if (!s) return fail(RSBWT_EINVAL, "null set");
-    const int rc = meta_required(s);
-    if (rc) return rc;
-    for (const rsbwt_t *h : s->shards) {
-        if (h->view.n == 0) return fail(RSBWT_EINVAL, "empty index in the set");
-        if (h->view.C[1] >= (1ull << 40)) return fail(RSBWT_EINVAL, "a shard of %llu strings: sample counts take fewer than 2^40", (unsigned long long)h->view.C[1]);
-    }
-    return RSBWT_OK;
-}
 
 // (read at every call: a test turns it on and off inside one process)
 bool sample_tight_set() {
@@ -4406,285 +3689,6 @@ static void meta_free(rsbwt_set_t *s) {
     s->meta_head_bytes = 0;
 }
 
-// ---- sample walks (sample_walk.hip): seeds extended through one sample set's reads ----
-namespace {
-// the calling thread's last host-form call: seeds, appended symbols, candidate searches, their LF steps, rows located, rows
-// on a head ordinal, distinct carriers, records read, LF steps of the rows' walks, wide evaluations
-thread_local uint64_t sample_walk_last[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-// ... and, while RSBWT_SAMPLE_WALK_TIMES=1, the device time of its launches in ms by kind, from events round every launch on
-// the call's stream, summed over steps, slices and device groups: {init, search, plan, rows, locate, tally, decide}
-thread_local double sample_walk_ms[SAMPLE_WALK_KINDS] = {0, 0, 0, 0, 0, 0, 0};
-
-// (read at every call: a probe turns it on and off inside one process)
-bool sample_walk_times_on() {
-    const char *e = getenv("RSBWT_SAMPLE_WALK_TIMES");
-    return e && e[0] == '1' && e[1] == 0;
-}
-
-// the marks of one enqueue -> ms[kind] += ...; the events are destroyed.  After the stream has been waited for.
-void sample_walk_read_marks(std::vector<hipEvent_t> &marks, double *ms) {
-    for (size_t i = 1; i < marks.size(); ++i) {
-        float dt = 0;
-        if (hipEventElapsedTime(&dt, marks[i - 1], marks[i]) == hipSuccess) ms[i == 1 ? 0 : 1 + (i - 2) % 6] += dt;
-        else (void)hipGetLastError();
-    }
-    for (hipEvent_t ev : marks) (void)hipEventDestroy(ev);
-    marks.clear();
-}
-
-struct sample_walk_call {
-    sample_dict d;
-    std::vector<uint32_t> bits;  // the mask, a bit per column
-    uint64_t max_rows = 0;
-    uint32_t max_locate_steps = 0;
-};
-
-int sample_walk_shape_ok(const rsbwt_set_t *s, uint64_t max_rows) {
-    if (!sample_walk_rows_ok(max_rows)) return fail(RSBWT_EINVAL, "max_rows = %llu: 1 to 2^20 for a sample walk", (unsigned long long)max_rows);
-    for (const dev_group *g : s->groups)
-        if (g->idx.size() > SAMPLE_WALK_MAX_SHARDS) return fail(RSBWT_EINVAL, "%zu shards on one device: a sample walk takes at most 1,024", g->idx.size());
-    return RSBWT_OK;
-}
-
-int sample_walk_prepare(rsbwt_set_t *s, const uint8_t *codes, size_t C, uint32_t size_of_sample, int has_other, const uint8_t *mask, uint64_t max_rows,
-                        uint32_t max_locate_steps, sample_walk_call *c) {
-    int rc = sample_set_ok(s);
-    if (rc) return rc;
-    if ((rc = sample_dict_make(codes, C, size_of_sample, has_other, &c->d)) != RSBWT_OK) return rc;
-    if (!mask) return fail(RSBWT_EINVAL, "null argument: mask");
-    if ((rc = sample_walk_shape_ok(s, max_rows)) != RSBWT_OK) return rc;
-    c->bits.resize(sample_walk_mask_words(C));
-    sample_walk_mask_bits(mask, C, c->bits.data());
-    c->max_rows = max_rows;
-    c->max_locate_steps = max_locate_steps;
-    return RSBWT_OK;
-}
-
-void sample_walk_add_work(uint64_t *work10, const unsigned long long *dev) {
-    auto w = [&](int which) { return (uint64_t)dev[(size_t)which * TALLY_WORK_STRIDE]; };
-    work10[1] += w(SW_WORK_APPENDED);
-    work10[2] += w(SW_WORK_SEARCHES);
-    work10[3] += w(SW_WORK_SEARCH_STEPS);
-    work10[4] += w(SW_WORK_ROWS);
-    work10[5] += w(SW_WORK_HEADS);
-    work10[6] += w(SW_WORK_CARRIERS);
-    work10[7] += w(SW_WORK_RECORDS);
-    work10[8] += w(SW_WORK_LOCATE_STEPS);
-    work10[9] += w(SW_WORK_WIDE);
-}
-
-// What a host-form call runs on one device group on `gc`'s stream: the batch, the dictionary and the mask go up once, then
-// the seeds are walked (or evaluated once: evaluate) slice by slice -- sample_walk_slice_seeds -- each slice's launches
-// enqueued blind and its answers copied back; the stream is waited for once per slice, never between steps.
-// walk: ext, steps, stop, support (optional), last (optional).  evaluate: raw i64[Q][8], m8 u64[Q][8], wide u8[Q].
-int sample_walk_group(dev_group *g, group_call &gc, const char *t0, const uint64_t *rel, size_t Q, size_t N, uint32_t ctx, uint64_t m,
-                      uint32_t max_steps, uint32_t flags, const sample_walk_call &c, bool evaluate, char *ext, uint32_t *steps, uint8_t *stop,
-                      uint32_t *support, uint64_t *last, int64_t *raw, uint64_t *m8, uint8_t *wide, uint64_t *work10, double *ms = nullptr) {
-    if (Q == 0) return RSBWT_OK;
-    std::vector<hipEvent_t> marks;
-    struct drop_marks {  // (a call that leaves early: group_call's destructor has the stream waited for before the events go)
-        std::vector<hipEvent_t> &m;
-        ~drop_marks() {
-            for (hipEvent_t ev : m) (void)hipEventDestroy(ev);
-        }
-    } drop{marks};
-    hipStream_t st = gc.st;
-    const uint32_t S = (uint32_t)g->idx.size(), steps_n = evaluate ? 1u : max_steps;
-    const size_t per = std::min(Q, sample_walk_slice_seeds(c.max_rows, SAMPLE_WALK_BUDGET));
-    const size_t cells = per * (size_t)steps_n;
-    const size_t a_text = al256(N + 1), a_off = al256((Q + 1) * 8), a_keys = al256((size_t)c.d.C * 8), a_bits = al256(c.bits.size() * 4),
-                 a_work = al256(SAMPLE_WALK_WORK * TALLY_WORK_STRIDE * 8), a_ext = evaluate ? 0 : al256(cells), a_steps = evaluate ? 0 : al256(per * 4),
-                 a_stop = evaluate ? 0 : al256(per), a_sup = !evaluate && support ? al256(cells * 4) : 0, a_last = !evaluate && last ? al256(per * 32) : 0,
-                 a_raw = evaluate ? al256(per * 64) : 0, a_m8 = evaluate ? al256(per * 64) : 0, a_wide = evaluate ? al256(per) : 0;
-    hipError_t e = g->scratch.take(a_text + a_off + a_keys + a_bits + a_work + a_ext + a_steps + a_stop + a_sup + a_last + a_raw + a_m8 + a_wide +
-                                       sample_walk_bytes(per, S, steps_n, c.max_rows),
-                                   st, &gc.lb);
-    if (e != hipSuccess)
-        return fail(RSBWT_ENOMEM, "%zu seeds x %llu rows do not fit the device's free memory: %s", per, (unsigned long long)c.max_rows, hipGetErrorString(e));
-    uint8_t *d_text = (uint8_t *)gc.lb.p, *d_off = d_text + a_text, *d_keys = d_off + a_off, *d_bits = d_keys + a_keys, *d_work = d_bits + a_bits,
-            *d_ext = d_work + a_work, *d_steps = d_ext + a_ext, *d_stop = d_steps + a_steps, *d_sup = d_stop + a_stop, *d_last = d_sup + a_sup,
-            *d_raw = d_last + a_last, *d_m8 = d_raw + a_raw, *d_wide = d_m8 + a_m8, *d_scratch = d_wide + a_wide;
-    if (N) HIP_OK(hipMemcpyAsync(d_text, t0, N, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_off, rel, (Q + 1) * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_keys, c.d.keys.data(), (size_t)c.d.C * 8, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(d_bits, c.bits.data(), c.bits.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemsetAsync(d_work, 0, a_work, st));
-    std::vector<unsigned long long> hwork(SAMPLE_WALK_WORK * TALLY_WORK_STRIDE);
-    for (size_t q0 = 0; q0 < Q; q0 += per) {
-        const size_t mq = std::min(per, Q - q0);
-        sample_walk_args a;
-        a.views = g->d_views;
-        a.meta = g->d_meta;
-        a.S = S;
-        a.num_cus = g->num_cus;
-        a.bt.text = (const char *)d_text;
-        a.bt.off = (const uint64_t *)d_off + q0;
-        a.bt.Q = mq;
-        a.bt.N = N;
-        a.bt.ctx = ctx;
-        a.bt.max_steps = steps_n;
-        a.bt.min_count = m;
-        a.bt.flags = flags;
-        a.keys = (const uint64_t *)d_keys;
-        a.mask_bits = (const uint32_t *)d_bits;
-        a.C = c.d.C;
-        a.size_of_sample = c.d.size_of_sample;
-        a.has_other = c.d.has_other;
-        a.max_rows = c.max_rows;
-        a.max_locate_steps = c.max_locate_steps;
-        a.ext = d_ext;
-        a.steps = d_steps;
-        a.stop = d_stop;
-        a.support = a_sup ? d_sup : nullptr;
-        a.last = a_last ? d_last : nullptr;
-        a.evaluate_only = evaluate ? 1u : 0u;
-        a.raw = d_raw;
-        a.matches8 = d_m8;
-        a.wide = d_wide;
-        a.work = (unsigned long long *)d_work;
-        a.marks = ms ? &marks : nullptr;
-        if ((e = sample_walk_enqueue(g->scratch, a, d_scratch, st)) != hipSuccess) return fail_hip(e, "sample walk launches");
-        if (evaluate) {
-            HIP_OK(hipMemcpyAsync(raw + q0 * 8, d_raw, mq * 64, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipMemcpyAsync(m8 + q0 * 8, d_m8, mq * 64, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipMemcpyAsync(wide + q0, d_wide, mq, hipMemcpyDeviceToHost, st));
-        } else {
-            HIP_OK(hipMemcpyAsync(ext + q0 * (size_t)max_steps, d_ext, mq * (size_t)max_steps, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipMemcpyAsync(steps + q0, d_steps, mq * 4, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipMemcpyAsync(stop + q0, d_stop, mq, hipMemcpyDeviceToHost, st));
-            if (support) HIP_OK(hipMemcpyAsync(support + q0 * (size_t)max_steps, d_sup, mq * (size_t)max_steps * 4, hipMemcpyDeviceToHost, st));
-            if (last) HIP_OK(hipMemcpyAsync(last + q0 * 4, d_last, mq * 32, hipMemcpyDeviceToHost, st));
-        }
-        HIP_OK(hipMemcpyAsync(hwork.data(), d_work, hwork.size() * 8, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        if (ms) sample_walk_read_marks(marks, ms);
-        if (hwork[(size_t)SW_WORK_LOST * TALLY_WORK_STRIDE] != 0)
-            return fail(RSBWT_EINVAL, "%llu rows whose walk to their read's start does not end within max_locate_steps (a corrupt index, or a read longer than the limit)",
-                        (unsigned long long)hwork[(size_t)SW_WORK_LOST * TALLY_WORK_STRIDE]);
-    }
-    sample_walk_add_work(work10, hwork.data());
-    return RSBWT_OK;
-}
-
-// One evaluation of every seed over every device group: the groups' masked sums and rows added on the host, WIDE decided
-// over the whole set's rows, the strands added.  msup u64[Q][4], wide u8[Q], matches u64[Q][4] (optional).
-int extension_samples_groups(rsbwt_set_t *s, const char *t0, const uint64_t *rel, size_t Q, size_t N, uint32_t ctx, uint32_t flags,
-                             const sample_walk_call &c, uint64_t *msup, uint8_t *wide, uint64_t *matches, uint64_t *work10) {
-    struct group_out {
-        std::vector<int64_t> raw;
-        std::vector<uint64_t> m8;
-        std::vector<uint8_t> wide;
-        uint64_t work[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    };
-    std::vector<group_out> outs(s->groups.size());
-    int rc = for_each_group(s, [&](size_t gi) -> int {
-        group_out &o = outs[gi];
-        o.raw.assign(Q * 8, 0);
-        o.m8.assign(Q * 8, 0);
-        o.wide.assign(Q, 0);
-        group_call gc(s->groups[gi], true);
-        if (gc.rc) return gc.rc;
-        return sample_walk_group(gc.g, gc, t0, rel, Q, N, ctx, 1ull, 1u, flags, c, true, nullptr, nullptr, nullptr, nullptr, nullptr, o.raw.data(),
-                                 o.m8.data(), o.wide.data(), o.work);
-    });
-    if (rc) return rc;
-    for (const group_out &o : outs)
-        for (int i = 1; i < 10; ++i) work10[i] += o.work[i];
-    for (size_t q = 0; q < Q; ++q) {
-        uint64_t m8[8];
-        int64_t raw[8];
-        for (uint32_t l = 0; l < 8u; ++l) {
-            m8[l] = 0;
-            raw[l] = 0;
-            for (const group_out &o : outs) {
-                m8[l] += o.m8[q * 8 + l];
-                raw[l] += o.raw[q * 8 + l];
-            }
-        }
-        const bool w = sample_walk_wide(m8, c.max_rows);
-        wide[q] = w ? 1u : 0u;
-        for (uint32_t b = 0; b < 4u; ++b) {
-            msup[q * 4 + b] = w ? 0ull : sample_walk_support(raw[2 * b], raw[2 * b + 1]);
-            if (matches) matches[q * 4 + b] = m8[2 * b] + m8[2 * b + 1];
-        }
-    }
-    return RSBWT_OK;
-}
-
-// The sample walk of a set over several device groups: walk_by_steps with extension_samples_groups as its evaluation.
-int walk_samples_by_steps(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint64_t m, uint32_t max_steps,
-                          uint32_t flags, const sample_walk_call &c, char *ext, uint32_t *steps, uint8_t *stop, uint32_t *support, uint64_t *last,
-                          uint64_t *work10) {
-    const bool left = (flags & RSBWT_WALK_LEFT) != 0u;
-    memset(ext, 0, Q * (size_t)max_steps);
-    if (support) memset(support, 0, Q * (size_t)max_steps * 4);
-    std::vector<std::string> cur(Q);
-    std::vector<size_t> live;
-    for (size_t q = 0; q < Q; ++q) {
-        const uint64_t Lq = off[q + 1] - off[q];
-        bool valid = Lq >= ctx;
-        if (valid) {
-            cur[q].assign(left ? text + off[q] : text + off[q + 1] - ctx, ctx);
-            for (char ch : cur[q]) valid = valid && (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T');
-        }
-        steps[q] = 0;
-        stop[q] = valid ? 0 : (uint8_t)RSBWT_WALK_INVALID;
-        if (last)
-            for (int b = 0; b < 4; ++b) last[4 * q + b] = 0;
-        if (valid) live.push_back(q);
-    }
-    std::string t;
-    std::vector<uint64_t> rel, msup;
-    std::vector<uint8_t> wide;
-    while (!live.empty()) {  // (every seed of `live` has fewer than max_steps symbols appended)
-        const size_t nl = live.size();
-        t.clear();
-        rel.resize(nl + 1);
-        for (size_t i = 0; i < nl; ++i) {
-            rel[i] = (uint64_t)i * ctx;
-            t += cur[live[i]];
-        }
-        rel[nl] = (uint64_t)nl * ctx;
-        if (rel[nl] >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu seeds x %u context symbols: under 2^31 in one call", nl, ctx);
-        msup.assign(nl * 4, 0);
-        wide.assign(nl, 0);
-        const int rc = extension_samples_groups(s, t.data(), rel.data(), nl, (size_t)rel[nl], ctx, flags, c, msup.data(), wide.data(), nullptr, work10);
-        if (rc) return rc;
-        std::vector<size_t> next;
-        for (size_t i = 0; i < nl; ++i) {
-            const size_t q = live[i];
-            const uint64_t *sup = msup.data() + i * 4;
-            uint32_t pick = 0;
-            uint32_t why = sample_walk_step(sup, wide[i] != 0, m, &pick);
-            if (why == SAMPLE_WALK_GO) {
-                const size_t at = q * (size_t)max_steps + steps[q];
-                ext[at] = "ACGT"[pick];
-                if (support) support[at] = sup[pick] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)sup[pick];
-                work10[1] += 1;
-                if (left) cur[q] = std::string(1, "ACGT"[pick]) + cur[q].substr(0, ctx - 1);
-                else cur[q] = cur[q].substr(1) + "ACGT"[pick];
-                if (++steps[q] == max_steps) why = SAMPLE_WALK_LIMIT;
-            }
-            if (why == SAMPLE_WALK_GO) {
-                next.push_back(q);
-                continue;
-            }
-            stop[q] = (uint8_t)why;
-            if (last && why != SAMPLE_WALK_LIMIT && why != SAMPLE_WALK_WIDE)
-                for (int b = 0; b < 4; ++b) last[4 * q + b] = sup[b];
-        }
-        live.swap(next);
-    }
-    return RSBWT_OK;
-}
-
-int sample_walk_flags_ok(uint32_t ctx, uint32_t flags, const uint32_t *max_steps, size_t Q) {
-    // (the walk's own checks, with the one flag a sample walk adds)
-    if (flags & ~(uint32_t)(RSBWT_WALK_LEFT | RSBWT_WALK_BOTH_STRANDS | RSBWT_WALK_SAMPLE_COPIES)) return fail(RSBWT_EINVAL, "unknown flag bits 0x%x", flags);
-    return walk_check_args(ctx, flags & ~(uint32_t)RSBWT_WALK_SAMPLE_COPIES, max_steps, Q);
-}
-}  // namespace
-
 namespace {
 // the service code's way in (service.h: service_slice.cpp is also linked into host harnesses without the engine)
 struct register_meta_hooks {
@@ -4957,142 +3961,6 @@ int rsbwt_set_site_read_counts(rsbwt_set_t *s, const char *text, const uint64_t 
 
 void rsbwt_set_site_reads_last_work(uint64_t *work9) {
     if (work9) memcpy(work9, site_reads_last_work, sizeof site_reads_last_work);
-}
-
-int rsbwt_set_extension_samples(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint32_t flags, const uint8_t *codes,
-                                size_t C, uint32_t size_of_sample, int has_other_meta_data, const uint8_t *mask, uint64_t max_rows,
-                                uint32_t max_locate_steps, uint64_t *msup, uint8_t *wide, uint64_t *matches) {
-    return guarded("rsbwt_set_extension_samples", [&]() -> int {
-        for (uint64_t &w : sample_walk_last) w = 0;
-        int rc = walk_set_check(s);
-        if (rc) return rc;
-        if ((rc = sample_walk_flags_ok(ctx, flags, nullptr, Q)) != RSBWT_OK) return rc;
-        sample_walk_call c;
-        if ((rc = sample_walk_prepare(s, codes, C, size_of_sample, has_other_meta_data, mask, max_rows, max_locate_steps, &c)) != RSBWT_OK) return rc;
-        std::vector<uint64_t> rel;
-        size_t N = 0;
-        if ((rc = match_check_batch(text, off, Q, &rel, &N)) != RSBWT_OK) return rc;
-        if (Q == 0) return RSBWT_OK;
-        if (!msup || !wide) return fail(RSBWT_EINVAL, "null argument");
-        uint64_t work10[10] = {Q, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        rc = extension_samples_groups(s, N ? text + off[0] : nullptr, rel.data(), Q, N, ctx, flags, c, msup, wide, matches, work10);
-        if (rc) return rc;
-        memcpy(sample_walk_last, work10, sizeof work10);
-        return RSBWT_OK;
-    });
-}
-
-int rsbwt_set_walk_samples(rsbwt_set_t *s, const char *text, const uint64_t *off, size_t Q, uint32_t ctx, uint64_t min_count, uint32_t max_steps,
-                           uint32_t flags, const uint8_t *codes, size_t C, uint32_t size_of_sample, int has_other_meta_data, const uint8_t *mask,
-                           uint64_t max_rows, uint32_t max_locate_steps, char *ext, uint32_t *steps, uint8_t *stop, uint32_t *support,
-                           uint64_t *last) {
-    return guarded("rsbwt_set_walk_samples", [&]() -> int {
-        for (uint64_t &w : sample_walk_last) w = 0;
-        for (double &t : sample_walk_ms) t = 0;
-        int rc = walk_set_check(s);
-        if (rc) return rc;
-        if ((rc = sample_walk_flags_ok(ctx, flags, &max_steps, Q)) != RSBWT_OK) return rc;
-        sample_walk_call c;
-        if ((rc = sample_walk_prepare(s, codes, C, size_of_sample, has_other_meta_data, mask, max_rows, max_locate_steps, &c)) != RSBWT_OK) return rc;
-        std::vector<uint64_t> rel;
-        size_t N = 0;
-        if ((rc = match_check_batch(text, off, Q, &rel, &N)) != RSBWT_OK) return rc;
-        if (Q == 0) return RSBWT_OK;
-        if (!ext || !steps || !stop) return fail(RSBWT_EINVAL, "null argument");
-        const uint64_t m = min_count ? min_count : 1ull;
-        const char *t0 = N ? text + off[0] : nullptr;
-        uint64_t work10[10] = {Q, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        if (s->groups.size() == 1) {  // the whole walk enqueued at once, slice by slice
-            group_call gc(s->groups[0], true);
-            if (gc.rc) return gc.rc;
-            rc = sample_walk_group(gc.g, gc, t0, rel.data(), Q, N, ctx, m, max_steps, flags, c, false, ext, steps, stop, support, last, nullptr, nullptr,
-                                   nullptr, work10, sample_walk_times_on() ? sample_walk_ms : nullptr);
-        } else {
-            rc = walk_samples_by_steps(s, t0, rel.data(), Q, ctx, m, max_steps, flags, c, ext, steps, stop, support, last, work10);
-        }
-        if (rc) return rc;
-        memcpy(sample_walk_last, work10, sizeof work10);
-        return RSBWT_OK;
-    });
-}
-
-// one-device set, the caller's buffers and stream, nothing synchronised
-int rsbwt_set_walk_samples_dev(rsbwt_set_t *s, const void *d_text, const void *d_off, size_t Q, size_t N, uint32_t ctx, uint64_t min_count,
-                               uint32_t max_steps, uint32_t flags, const void *d_keys, size_t C, uint32_t size_of_sample, int has_other_meta_data,
-                               const void *d_mask, uint64_t max_rows, uint32_t max_locate_steps, void *d_ext, void *d_steps, void *d_stop,
-                               void *d_support, void *d_last, void *d_status8, void *stream) {
-    return guarded("rsbwt_set_walk_samples_dev", [&]() -> int {
-        dev_group *g = nullptr;
-        int rc = one_device_group(s, &g);
-        if (rc) return rc;
-        if ((rc = sample_walk_flags_ok(ctx, flags, &max_steps, Q)) != RSBWT_OK) return rc;
-        if ((rc = sample_set_ok(s)) != RSBWT_OK) return rc;
-        if ((rc = sample_shape_ok(C, size_of_sample)) != RSBWT_OK) return rc;
-        if ((rc = sample_walk_shape_ok(s, max_rows)) != RSBWT_OK) return rc;
-        if (!d_keys || !d_mask || !d_status8) return fail(RSBWT_EINVAL, "null argument");
-        hipStream_t st = (hipStream_t)stream;
-        if (Q == 0) {
-            HIP_OK(hipMemsetAsync(d_status8, 0, 64, st));
-            return RSBWT_OK;
-        }
-        if (!d_text || !d_off || !d_ext || !d_steps || !d_stop) return fail(RSBWT_EINVAL, "null argument");
-        if (N >= (1ull << 31)) return fail(RSBWT_ERANGE, "%zu positions in one call: at most 2^31 - 1", N);
-        const uint32_t S = (uint32_t)g->idx.size();
-        const size_t per = std::min(Q, sample_walk_slice_seeds(max_rows, SAMPLE_WALK_BUDGET));
-        const size_t a_bits = al256(sample_walk_mask_words(C) * 4), a_work = al256(SAMPLE_WALK_WORK * TALLY_WORK_STRIDE * 8);
-        scratch_cache::lease mem;
-        hipError_t e = g->scratch.take(a_bits + a_work + sample_walk_bytes(per, S, max_steps, max_rows), st, &mem);
-        if (e != hipSuccess) return fail_hip(e, "scratch for a sample walk");
-        uint8_t *d_bits = (uint8_t *)mem.p, *d_work = d_bits + a_bits, *d_scratch = d_work + a_work;
-        rc = [&]() -> int {
-            if ((e = launch_sample_walk_mask(d_mask, C, d_bits, st)) != hipSuccess) return fail_hip(e, "mask kernel launch");
-            HIP_OK(hipMemsetAsync(d_work, 0, a_work, st));
-            for (size_t q0 = 0; q0 < Q; q0 += per) {  // (the slices share the scratch: stream order keeps them apart)
-                const size_t mq = std::min(per, Q - q0);
-                sample_walk_args a;
-                a.views = g->d_views;
-                a.meta = g->d_meta;
-                a.S = S;
-                a.num_cus = g->num_cus;
-                a.bt.text = (const char *)d_text;
-                a.bt.off = (const uint64_t *)d_off + q0;
-                a.bt.Q = mq;
-                a.bt.N = N;
-                a.bt.ctx = ctx;
-                a.bt.max_steps = max_steps;
-                a.bt.min_count = min_count ? min_count : 1ull;
-                a.bt.flags = flags;
-                a.keys = (const uint64_t *)d_keys;
-                a.mask_bits = (const uint32_t *)d_bits;
-                a.C = (uint32_t)C;
-                a.size_of_sample = size_of_sample;
-                a.has_other = has_other_meta_data ? 1u : 0u;
-                a.max_rows = max_rows;
-                a.max_locate_steps = max_locate_steps;
-                a.ext = (char *)d_ext + q0 * (size_t)max_steps;
-                a.steps = (uint32_t *)d_steps + q0;
-                a.stop = (uint8_t *)d_stop + q0;
-                a.support = d_support ? (uint32_t *)d_support + q0 * (size_t)max_steps : nullptr;
-                a.last = d_last ? (uint64_t *)d_last + q0 * 4 : nullptr;
-                a.evaluate_only = 0u;
-                a.raw = a.matches8 = a.wide = nullptr;
-                a.work = (unsigned long long *)d_work;
-                if ((e = sample_walk_enqueue(g->scratch, a, d_scratch, st)) != hipSuccess) return fail_hip(e, "sample walk launches");
-            }
-            if ((e = launch_sample_walk_status((const unsigned long long *)d_work, d_status8, st)) != hipSuccess) return fail_hip(e, "status kernel launch");
-            return RSBWT_OK;
-        }();
-        g->scratch.give(mem, st);
-        return rc;
-    });
-}
-
-void rsbwt_set_walk_samples_last_work(uint64_t *work10) {
-    if (work10) memcpy(work10, sample_walk_last, sizeof sample_walk_last);
-}
-
-void rsbwt_set_walk_samples_last_times(double *ms7) {
-    if (ms7) memcpy(ms7, sample_walk_ms, sizeof sample_walk_ms);
 }
 
 int rsbwt_rccl_available(void) { return rccl().ok ? 1 : 0; }

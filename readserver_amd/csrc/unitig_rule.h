@@ -1,5 +1,5 @@
 // unitig_rule.h -- the decision of one step of a unitig side (include/rsbwt.h: the definition), for the device
-// (walk.hip, unitig_kernel), the host (sets.hip, a set over several device groups) and, as a program of its own,
+// (walk.hip, unitig_kernel), the host (graph_steps.h, a set over several device groups) and, as a program of its own,
 // tests/native/unitig_rule_host.cpp.
 //
 // A step has eight sums: the four ONWARD supports of the side's string in its own direction, and -- looked at only where

@@ -26,7 +26,7 @@
 //     shard (fewer shards than waves) writes zeros and reaches both barriers.  The loop runs max_steps times at the
 //     most, whatever the data says.
 // extension_kernel is the evaluation without the decision: a wave owns (8 seeds, one shard) and writes that shard's
-// counts.  Sets over several device groups walk with it, one round trip per step (sets.hip).
+// counts.  Sets over several device groups walk with it, one round trip per step (set_graph.hip).
 // unitig_kernel is the walk both ways with the joins looked at: the unit of work is the item (seed, side), and a step
 // evaluates onward and then, in the opposite direction, the node the one live symbol enters (unitig_rule.h: the decision).
 #include <hip/hip_runtime.h>

@@ -1,7 +1,7 @@
 // paths_rule_host.cpp -- readserver_amd/csrc/paths_rule.h as a program of its own, for the address and undefined-behaviour
 // sanitizers (tests/test_paths_reference.py builds and runs it, and restates the search in Python).
 //
-// The header's decisions drive the depth-first search exactly as the host loop of sets.hip and the writer lane of
+// The header's decisions drive the depth-first search exactly as the host loop of graph_steps.h and the writer lane of
 // paths_kernel do, over a graph that is a function of the path alone: the supports of path p from seed s are FNV-1a hashes
 // of "<s>:" + p + symbol, mapped onto a small table that holds zeros, small counts and counts at and past 32 bits.  The
 // frame store is allocated at exactly paths_frames(max_steps, max_evals) frames, so a push past it is a heap overflow

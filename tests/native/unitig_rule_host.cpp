@@ -1,5 +1,5 @@
 // unitig_rule_host.cpp -- readserver_amd/csrc/unitig_rule.h (the decision of one step of a unitig side, shared by
-// csrc/walk.hip's unitig_kernel and csrc/sets.hip's walk by steps) as a program of its own, for
+// csrc/walk.hip's unitig_kernel and csrc/graph_steps.h, the loop of a set over several device groups) as a program of its own, for
 // tests/test_unitig_reference.py to build with -fsanitize=address,undefined and run.  Input: m and max_steps.  Output:
 // one line "steps s0 .. s7 stop pick halves saturated" for every pattern of (sum >= m) over the eight sums -- a live sum
 // is m + its index, a dead one m - 1 -- at steps 0, max_steps - 1 and max_steps; `stop` and `pick` are unitig_rule's (pick

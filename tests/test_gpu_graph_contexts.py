@@ -1,6 +1,6 @@
 """The k-mer graph kernels at the context lengths where the search and the rings change behaviour (-m gpu):
 rsbwt_set_extensions / rsbwt_extensions / rsbwt_set_walk / rsbwt_set_unitigs / rsbwt_set_paths / _dev (csrc/walk_search.h,
-csrc/walk.hip, csrc/paths.hip, csrc/sets.hip) held bit-exactly, work counters included, to walk_reference, unitig_reference
+csrc/walk.hip, csrc/paths.hip, csrc/set_graph.hip) held bit-exactly, work counters included, to walk_reference, unitig_reference
 and paths_reference over the oracle:
 
   * AROUND THE TABLE DEPTH.  walk_search takes a table start only when the candidate, K = ctx + 1 symbols, is no shorter
@@ -270,7 +270,7 @@ def test_gpu_paths_device_resident_form_at_dense_forks(rsb, oracle):
 
 
 def test_gpu_paths_and_unitigs_on_two_logical_devices_at_these_lengths(rsb, oracle, monkeypatch):
-    """the host loop of a set over two device groups (csrc/sets.hip over paths_rule.h and unitig_rule.h) at K == T and at
+    """the host loop of a set over two device groups (csrc/graph_steps.h under csrc/set_graph.hip) at K == T and at
     dense forks: the answers and the counters of the one-device set"""
     L = rsb.lib()
     cases = [(5, P.WIDE), (5, P.TIGHT), (2, X.DENSE_FULL)]

@@ -1,4 +1,4 @@
-"""Paths on the GPU (-m gpu): rsbwt_set_paths / _dev (csrc/paths.hip's paths_kernel, csrc/sets.hip) held bit-exactly to
+"""Paths on the GPU (-m gpu): rsbwt_set_paths / _dev (csrc/paths.hip's paths_kernel, csrc/set_graph.hip) held bit-exactly to
 tests/paths_reference.py, the definition stated over the oracle: ext, steps, stop, min_support, npaths and state of every
 seed, and all eight work counters.  The fixture is the walk tests': the gt read set as it is and with every other read
 reverse-complemented, dealt to 1, 2, 3, 5 and 9 shards (workgroups of 1, 2 and 4 waves; one round, rounds, a last round
@@ -286,6 +286,16 @@ def test_gpu_paths_on_two_logical_devices(rsb, oracle, monkeypatch):
                 assert rsb.ShardSet.paths_last_work() == counters[(ctx, m, left, both, limits, targets)], (ctx, m, left, both, limits, targets)
                 if m == 1 and ctx == 12:
                     _check_work(rsb, side, ref, sds, left, both, 6, ("two devices", left, both))
+        # min_support null: ext, steps, stop, npaths and state of the call that has it
+        pv = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
+        text, off = ss._var_text(W.seeds(12))
+        Q, (mx, mp, me) = len(W.seeds(12)), P.WIDE
+        full = [np.full((Q, mp, mx), 77, np.uint8), np.full((Q, mp), 77, np.uint32), np.full((Q, mp), 77, np.uint8), np.zeros((Q, mp), np.uint32),
+                np.full(Q, 77, np.uint32), np.full(Q, 77, np.uint8)]
+        bare = [a.copy() for a in full]
+        assert L.rsbwt_set_paths(ss._s, pv(text), pv(off), Q, None, None, 12, 1, mx, mp, me, 0, *[pv(a) for a in full]) == 0
+        assert L.rsbwt_set_paths(ss._s, pv(text), pv(off), Q, None, None, 12, 1, mx, mp, me, 0, *[pv(a) if i != 3 else None for i, a in enumerate(bare)]) == 0
+        assert all((a == b).all() for i, (a, b) in enumerate(zip(full, bare)) if i != 3) and full[3].any() and (full[4] >= 2).any()
         assert L.rsbwt_set_paths_dev(ss._s, None, None, 0, 0, None, None, 0, 12, 1, 4, 2, 16, 0, None, None, None, None, None, None, None) == -1
         assert b"devices" in L.rsbwt_last_error()
     finally:

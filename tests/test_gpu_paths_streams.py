@@ -1,4 +1,4 @@
-"""Paths on the GPU beyond the gt fixture (-m gpu): rsbwt_set_paths (csrc/paths.hip's paths_kernel, csrc/sets.hip) held
+"""Paths on the GPU beyond the gt fixture (-m gpu): rsbwt_set_paths (csrc/paths.hip's paths_kernel, csrc/set_graph.hip) held
 bit-exactly to tests/paths_reference.py's statement over the oracle on tests/stream_reference.py's inputs: run streams in
 the shapes that broke other kernels, the degenerate ones -- on the '$'-less stream a step of a search can leave the
 wrapped interval (0, 2^64 - 1), which counts 0 -- and the `repeat` and `ragged` read sets, on the builder's own span,

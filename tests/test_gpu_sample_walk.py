@@ -1,5 +1,5 @@
 """Sample walks on the GPU (-m gpu): rsbwt_set_extension_samples / rsbwt_set_walk_samples / _dev (csrc/sample_walk.hip,
-csrc/sets.hip) held bit-exactly to tests/sample_walk_reference.py, the definition restated over
+csrc/set_graph.hip) held bit-exactly to tests/sample_walk_reference.py, the definition restated over
 sample_reference.counts_plain -- no BWT.  tests/test_sample_walk_reference.py holds that restatement to the one over the
 oracle on the CPU and shows that the inputs reach what the kernels can get wrong."""
 import ctypes as C
@@ -264,6 +264,18 @@ def test_gpu_walk_samples_on_two_logical_devices(rsb, monkeypatch):
         want = [SW.evaluate(c.side("plain", False), s, c.ctx, False, True, 4096) for s in c.seeds]
         assert [tuple(int(x) for x in r) for r in got["msup"]] == [w[0] for w in want]
         assert [tuple(int(x) for x in r) for r in got["matches"]] == [w[2] for w in want]
+        # support and last null: ext, steps and stop of the call that has them
+        pv = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        flat, n, mask = rsb.ShardSet._sample_mask(c.codes, c.ss, c.mask)
+        text, off = rsb.ShardSet._var_text(c.seeds)
+        Q, mx = len(c.seeds), c.max_steps
+        full = [np.full((Q, mx), 77, np.uint8), np.full(Q, 77, np.uint32), np.full(Q, 77, np.uint8)]
+        bare = [a.copy() for a in full]
+        sup, last = np.zeros((Q, mx), np.uint32), np.zeros((Q, 4), np.uint64)
+        args = (ss._s, pv(text), pv(off), Q, 12, 1, mx, 0, pv(flat), n, c.ss, 1 if c.other else 0, pv(mask), 4096, 0)
+        assert L.rsbwt_set_walk_samples(*args, *[pv(a) for a in full], pv(sup), pv(last)) == 0, L.rsbwt_last_error()
+        assert L.rsbwt_set_walk_samples(*args, *[pv(a) for a in bare], None, None) == 0, L.rsbwt_last_error()
+        assert all((a == b).all() for a, b in zip(full, bare)) and full[1].any() and (sup != 0).sum() == full[1].sum()
     finally:
         _close(ss, gs)
 

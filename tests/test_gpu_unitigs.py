@@ -1,4 +1,4 @@
-"""Unitigs on the GPU (-m gpu): rsbwt_set_unitigs / _dev (csrc/walk.hip's unitig_kernel, csrc/sets.hip) held bit-exactly to
+"""Unitigs on the GPU (-m gpu): rsbwt_set_unitigs / _dev (csrc/walk.hip's unitig_kernel, csrc/set_graph.hip) held bit-exactly to
 tests/unitig_reference.py, the definition stated over the oracle: ext, steps, stop, support and last of both sides of every
 seed, and all eight work counters.  The fixture is the walk tests': the gt read set as it is and with every other read
 reverse-complemented, dealt to 1, 2, 3, 5 and 9 shards (workgroups of 1, 2 and 4 waves; one round, rounds, a last round
@@ -309,6 +309,16 @@ def test_gpu_unitigs_on_two_logical_devices(rsb, oracle, monkeypatch):
             assert rsb.ShardSet.unitigs_last_work() == counters[(ctx, m, both)], (ctx, m, both)
             if m == 1 and ctx == 12 and both:
                 _check_work(rsb, side, us, sds, both, 6, ("two devices", both))
+        # support and last null: ext, steps and stop of the call that has them
+        pv = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
+        text, off = ss._var_text(U.seeds(12))
+        Q, mx = len(U.seeds(12)), W.MAX_STEPS
+        full = [np.full((Q, 2, mx), 77, np.uint8), np.full((Q, 2), 77, np.uint32), np.full((Q, 2), 77, np.uint8)]
+        bare = [a.copy() for a in full]
+        sup, last = np.zeros((Q, 2, mx), np.uint32), np.zeros((Q, 2, 8), np.uint64)
+        assert L.rsbwt_set_unitigs(ss._s, pv(text), pv(off), Q, 12, 1, mx, 0, *[pv(a) for a in full], pv(sup), pv(last)) == 0
+        assert L.rsbwt_set_unitigs(ss._s, pv(text), pv(off), Q, 12, 1, mx, 0, *[pv(a) for a in bare], None, None) == 0
+        assert all((a == b).all() for a, b in zip(full, bare)) and full[1].any() and sup.any() and last.any()
         assert L.rsbwt_set_unitigs_dev(ss._s, None, None, 0, 0, 12, 1, 4, 0, None, None, None, None, None, None) == -1
         assert b"devices" in L.rsbwt_last_error()
     finally:

@@ -1,5 +1,5 @@
 """Extension counts and walks on the GPU (-m gpu): rsbwt_set_extensions / rsbwt_extensions / rsbwt_set_walk / _dev
-(csrc/walk.hip, csrc/sets.hip, csrc/capi.hip) held bit-exactly to tests/walk_reference.py, the definition restated over
+(csrc/walk.hip, csrc/set_graph.hip, csrc/capi.hip) held bit-exactly to tests/walk_reference.py, the definition restated over
 the oracle: the per-shard counts on every seed and on every walk's last state; ext, steps, stop, support and last of the
 walks; the work counters.  The fixture is the gt tests' read set as it is and with every other read reverse-complemented,
 dealt to 1, 2, 3, 5 and 9 shards (workgroups of 1, 2 and 4 waves; one round, rounds, a last round that is not full);
@@ -269,6 +269,16 @@ def test_gpu_walk_on_two_logical_devices(rsb, oracle, monkeypatch):
             if m == 1 and ctx == 12:
                 _check_work(rsb, side, ws, sds, left, both, 6, ("two devices", left, both))
                 _check_extensions(ss, side, sds + [w.final for w in ws], ctx, left, both, "two devices")
+        # support and last null: ext, steps and stop of the call that has them
+        pv = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
+        text, off = ss._var_text(W.seeds(12))
+        Q, mx = len(W.seeds(12)), W.MAX_STEPS
+        full = [np.full((Q, mx), 77, np.uint8), np.full(Q, 77, np.uint32), np.full(Q, 77, np.uint8)]
+        bare = [a.copy() for a in full]
+        sup, last = np.zeros((Q, mx), np.uint32), np.zeros((Q, 4), np.uint64)
+        assert L.rsbwt_set_walk(ss._s, pv(text), pv(off), Q, 12, 1, mx, 0, *[pv(a) for a in full], pv(sup), pv(last)) == 0
+        assert L.rsbwt_set_walk(ss._s, pv(text), pv(off), Q, 12, 1, mx, 0, *[pv(a) for a in bare], None, None) == 0
+        assert all((a == b).all() for a, b in zip(full, bare)) and full[1].any() and sup.any() and last.any()
         assert L.rsbwt_set_walk_dev(ss._s, None, None, 0, 0, 12, 1, 4, 0, None, None, None, None, None, None) == -1
         assert b"devices" in L.rsbwt_last_error()
     finally:

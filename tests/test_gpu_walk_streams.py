@@ -1,5 +1,5 @@
 """Extension counts and walks on the GPU beyond the gt fixture (-m gpu): rsbwt_set_extensions / rsbwt_extensions /
-rsbwt_set_walk (csrc/walk.hip, csrc/sets.hip, csrc/capi.hip) held bit-exactly to tests/walk_reference.py's restatement over
+rsbwt_set_walk (csrc/walk.hip, csrc/set_graph.hip, csrc/capi.hip) held bit-exactly to tests/walk_reference.py's restatement over
 the oracle on tests/stream_reference.py's inputs: run streams in the shapes that broke other kernels, the degenerate ones
 -- on the '$'-less stream the first step of a search can leave the wrapped interval (0, 2^64 - 1), which counts 0 -- and
 the `repeat` and `ragged` read sets, on the builder's own span, with spill chunks and at the widest span, behind a k-mer
